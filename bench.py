@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py -- full-graph GraphSAGE on an ogbn-products-shaped graph (BASELINE.json's metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the JSON line (`value`, `ms_per_step`
+and the roofline of the g-SpMM launches recorded inside those timed steps).  --full adds every other measurement listed
+below (the reference-module epochs and exact variants, `secondary`, the control graphs, the counter passes, the scaling
+model, the CPU baseline); each of them can still be skipped with its --no-* switch.  --dump-outputs DIR writes what the
+last timed step computed (loss, log-probabilities of the training rows, gradients and updated parameters) as DIR/<name>.npy.
 
 N > 1: one rank per GPU over RCCL.  The driver launches it as `python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N ...`; a plain `python bench.py --gpus N` (no WORLD_SIZE in the environment) starts those N ranks
@@ -13,7 +19,7 @@ E = 123,718,280 directed, D = 100 -> 64 -> 64 -> 47, fp32).  `value` = aggregate
 g-SpMMs) * E / epoch time, whole job.  N > 1 partitions the SAME graph (edge-cut + RCCL all_to_all halo exchange):
 strong scaling.
 
-The JSON line also carries
+The JSON line also carries (plain run: roofline without traffic / controls; the rest with --full)
   roofline      the dominant hot-path kernel (copy_u/sum g-SpMM at D = 64, 4 launches per epoch): algorithmic bytes
                 (4(N+1) + 4E + 4ND + 4ND; the two backward launches accumulate into the self gradient and so
                 read the output rows as well: + 4ND for them) / its mean launch duration, measured live with HIP events on
@@ -220,6 +226,30 @@ def profile_avg_us(tag=None):
     return out
 
 
+DUMP_LOG_PROBS_BYTES = 48 << 20  # of the 64 MB a dump may take; parameters and gradients are a few hundred KB
+
+
+def dump_outputs(out_dir, log_probs, loss, model):
+    """--dump-outputs: what the last timed step gave its caller, as <out_dir>/<name>.npy -- `loss` (float64 [1]), the training rows'
+    `log_probs_train_rows` (float32 [rows, classes]; a fixed seeded sample of rows, in order, when the whole would exceed
+    DUMP_LOG_PROBS_BYTES; with N > 1 rank 0's own rows), and per parameter its gradient (`grad.<name>`) and its value after the
+    optimizer step (`param.<name>`), float32.  Inputs are seeded, so two builds given the same arguments compare output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    lp = log_probs.float()
+    row_bytes = max(1, lp[0].numel() * 4) if lp.shape[0] else 1
+    if lp.shape[0] * row_bytes > DUMP_LOG_PROBS_BYTES:
+        pick = np.sort(np.random.default_rng(0).choice(lp.shape[0], size=DUMP_LOG_PROBS_BYTES // row_bytes, replace=False))
+        lp = lp[torch.from_numpy(pick).to(lp.device)]
+    arrays = {"loss": np.array([loss], dtype=np.float64), "log_probs_train_rows": lp.cpu().numpy().astype(np.float32)}
+    for name, prm in model.named_parameters():
+        arrays["param." + name] = prm.detach().float().cpu().numpy()
+        if prm.grad is not None:
+            arrays["grad." + name] = prm.grad.detach().float().cpu().numpy()
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher: start N ranks as child processes (torch.distributed.run) and exit
     with their status.  Runs before anything in this process has initialised the GPU (device_count() does not)."""
@@ -293,16 +323,23 @@ def main():
     p.add_argument("--emulate-ranks", default=None, metavar="P[,P...]",
                    help="N = 1 only: run every rank of a P-way partition of the same graph one at a time on this GPU (mi355x_graph/"
                         "emulate.py) and put the scaling model into config.partition.predicted; given explicitly it also skips the "
-                        "plain-model / controls / counter / CPU legs.  Default for a plain N = 1 run: 2,4,8")
+                        "plain-model / controls / counter / CPU legs.  Default for an N = 1 --full run: 2,4,8")
     p.add_argument("--no-scale-model", action="store_true", help="skip the emulated-ranks scaling model")
     p.add_argument("--report", default=None, help="with --emulate-ranks: also write the human-readable table to this file")
     p.add_argument("--tune-dense", action="store_true",
                    help="experiment, with --emulate-ranks: PyTorch TunableOp chooses the dense GEMMs of the per-rank shapes in the warm-up")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beside the headline (reference-module epochs, exact variants, secondary configs, "
+                        "control graphs, counter passes, scaling model, CPU baseline); a plain run times the headline steps only")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, < 64 MB)")
     args = p.parse_args()
     if args.emulate_ranks is not None:
         args.no_plain = args.no_controls = args.no_pmc = args.no_cpu_baseline = args.no_secondary = True
-    elif not args.no_scale_model and args.gpus == 1:
+    elif args.full and not args.no_scale_model and args.gpus == 1:
         args.emulate_ranks = "2,4,8"
+    if not args.full:  # a plain run: the headline alone
+        args.no_plain = args.no_controls = args.no_pmc = args.no_cpu_baseline = args.no_secondary = args.no_variants = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)  # does not return
@@ -430,7 +467,8 @@ def main():
         del src, dst
     opt = torch.optim.Adam(model.parameters(), lr=cfg["lr"])
 
-    def make_step(model, opt, bucket):
+    def make_step(model, opt, bucket, keep=None):
+        """`keep`: a dict that receives each step's log-probabilities of the training rows (--dump-outputs)."""
         model.rows_are_distinct = True  # train_idx = nonzero() of a mask
 
         def step():
@@ -443,9 +481,13 @@ def main():
             y_train = y[train_idx]  # main_dgl_product_sage.py:106 gathers the labels inside train()
             # default model: log_softmax on the train rows only (row-wise, so the same numbers); plain: the reference's line
             if model.plain:
-                loss = F.nll_loss(model(g, x)[train_idx], y_train, reduction="sum") / total_train
+                out = model(g, x)[train_idx]
+                loss = F.nll_loss(out, y_train, reduction="sum") / total_train
             else:
-                loss = ops.nll_sum(model(g, x, rows=train_idx), y_train) / total_train
+                out = model(g, x, rows=train_idx)
+                loss = ops.nll_sum(out, y_train) / total_train
+            if keep is not None:
+                keep["log_probs_train_rows"] = out.detach()
             loss.backward()
             if bucket is not None:
                 bucket.all_reduce()
@@ -492,7 +534,8 @@ def main():
         return elapsed, loss, records
 
     progress("starting warm-up + timed steps")
-    elapsed, loss, records = timed(make_step(model, opt, bucket), args.steps, args.warmup, True)
+    kept = {} if args.dump_outputs else None
+    elapsed, loss, records = timed(make_step(model, opt, bucket, kept), args.steps, args.warmup, True)
     progress("timed region done")
     if world > 1:
         tr = g._comm.trace or []  # the timed steps' exchanges (set in timed(), after the warm-up)
@@ -514,6 +557,8 @@ def main():
         lt = torch.tensor([loss], dtype=torch.float64, device=device)  # each rank holds its share of the global mean
         mdist.all_reduce(lt, op=dist.ReduceOp.SUM)
         loss = float(lt.item())
+    if kept is not None and rank == 0:
+        dump_outputs(args.dump_outputs, kept.pop("log_probs_train_rows"), loss, model)
 
     # ---- roofline: every copy_u g-SpMM shape of the epoch from the live HIP-event records; the headline entry is the
     # dominant one, D = hidden (4 of the 5 launches per epoch)
@@ -788,7 +833,7 @@ def main():
                 if "traffic_detail" in head:
                     roofline["traffic_detail"] = head["traffic_detail"]
         elif roofline is not None:
-            roofline["traffic_source"] = "not collected (N > 1, --no-pmc or another dataset)"
+            roofline["traffic_source"] = "not collected (a plain run, N > 1, --no-pmc or another dataset; --full collects it)"
     line["roofline"] = roofline
 
     if single and not args.no_cpu_baseline:

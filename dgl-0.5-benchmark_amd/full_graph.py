@@ -83,7 +83,7 @@ class SAGEConv(nn.Module):
 class GraphSAGE(nn.Module):
     """`plain=True` is the reference's module graph verbatim in structure -- torch.nn.Linear, F.relu, nn.Dropout,
     nn.BatchNorm1d, `fc_self(h) + fc_neigh(neigh)` as two GEMMs and an add (main_dgl_product_sage.py:15-99): only the
-    aggregation inside update_all() is this package's.  bench.py reports its epoch beside the default's."""
+    aggregation inside update_all() is this package's.  bench.py --full reports its epoch beside the default's."""
 
     def __init__(self, in_feats, hidden_feats, out_feats, num_layers, dropout, batch_norm=False, neigh_bias=True, plain=False):
         super(GraphSAGE, self).__init__()

@@ -1,4 +1,4 @@
-"""The BASELINE.json configurations other than the headline, timed inside bench.py's default N = 1 run (`secondary` in the JSON line).
+"""The BASELINE.json configurations other than the headline, timed inside bench.py's N = 1 --full run (`secondary` in the JSON line).
 
 VERDICT r04 item 2: arxiv SAGE (configs[1], main_dgl_arxiv_sage.py:141-148), the 2-layer 8-head GAT on the reddit shape with the
 README's 11.6 M edges (configs[2]) and the reference script's own 3 x 1-head GAT on DGL's 114.6 M-edge reddit

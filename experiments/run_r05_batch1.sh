@@ -8,7 +8,7 @@ mkdir -p "$O"
 cd "$R"
 timeout 900 python3 -m pytest tests -m gpu -x -q > $O/r05_b1_pytest.log 2>&1; echo "pytest rc $?" >> $O/r05_b1_pytest.log
 tail -3 $O/r05_b1_pytest.log
-timeout 600 python3 bench.py --steps 10 --warmup 3 > $O/r05_b1_bench_line.json 2> $O/r05_b1_bench_line.err; echo "bench rc $?"
+timeout 600 python3 bench.py --full --steps 10 --warmup 3 > $O/r05_b1_bench_line.json 2> $O/r05_b1_bench_line.err; echo "bench rc $?"
 timeout 300 python3 experiments/exp_d100_split.py > $O/r05_d100_split.txt 2>&1; echo "d100 rc $?"
 timeout 400 python3 experiments/exp_packed_rows.py > $O/r05_sparse_row_bound.txt 2>&1; echo "packed rc $?"
 cd /tmp && export TMPDIR=/tmp
