@@ -32,7 +32,7 @@ import torch.nn.functional as F  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dgl  # noqa: E402
 import dgl.function as fn  # noqa: E402
-from dgl.nn.pytorch import GATConv, Linear, BatchNorm1d  # noqa: E402
+from dgl.nn.pytorch import GATConv, Linear, BatchNorm1d, RelGraphConv  # noqa: E402
 from mi355x_graph import config, ops  # noqa: E402
 from dgl.utils import expand_as_pair  # noqa: E402
 
@@ -203,6 +203,54 @@ def sage_train_step(model, g, feats, labels, train_idx, optimizer):
     return loss.item()
 
 
+class RGCN(nn.Module):
+    """The edge-weighted relational model of main_dgl_proteins_rgcn_for.py:62-97 over dgl.nn.pytorch.RelGraphConv: num_layers layers,
+    the hidden ones with activation and dropout, the last one bare.  `gnn_layers` as there, so a state_dict moves across."""
+
+    def __init__(self, num_layers, in_feats, hidden_feats, out_feats, num_relations, activation=F.relu, dropout=0., layer=None):
+        super(RGCN, self).__init__()
+        layer = layer or RelGraphConv
+        widths = [in_feats] + [hidden_feats] * (num_layers - 1) + [out_feats]
+        self.gnn_layers = nn.ModuleList()
+        for i in range(num_layers):
+            last = i == num_layers - 1
+            self.gnn_layers.append(layer(widths[i], widths[i + 1], num_relations, activation=None if last else activation,
+                                         dropout=0. if last else dropout))
+
+    def reset_parameters(self):
+        for gnn in self.gnn_layers:
+            gnn.reset_parameters()
+
+    def forward(self, g, node_feats, edge_weights):
+        for gnn in self.gnn_layers:
+            node_feats = gnn(g, node_feats, edge_weights)
+        return node_feats
+
+
+def rgcn_train_step(model, g, node_feats, edge_weights, y_true, train_idx, optimizer):
+    """main_dgl_proteins_rgcn_for.py:99-109: BCE-with-logits on the training rows, loss.item() as the host sync."""
+    model.train()
+    optimizer.zero_grad()
+    out = model(g, node_feats, edge_weights)[train_idx]
+    loss = F.binary_cross_entropy_with_logits(out, y_true[train_idx].to(torch.float))
+    loss.backward()
+    optimizer.step()
+    return loss.item()
+
+
+def build_rgcn(device, scale=1.0, num_layers=3, hidden=32, dropout=0., lr=0.01):
+    """The proteins leg (main_dgl_proteins_rgcn_for.py:151-175): a column of ones as node features, the 8 edge-feature columns as the
+    relations' prior weights (slices of one device matrix, as the script builds them)."""
+    from mi355x_graph.datasets import ProteinsLike
+    data = ProteinsLike(device=device, scale=scale)
+    g = data.graph.int().formats(["csr", "csc"]).to(device)
+    node_feats = torch.ones((g.number_of_nodes(), 1), device=device)
+    edge_weights = [data.edge_feat[:, t:t + 1] for t in range(data.edge_feat.shape[-1])]
+    model = RGCN(num_layers, 1, hidden, data.num_tasks, len(edge_weights), dropout=dropout).to(device)
+    opt = torch.optim.Adam(model.parameters(), lr=lr)
+    return data, g, node_feats, edge_weights, model, opt
+
+
 def gat_train_step(model, feats, labels, train_mask, optimizer, loss_fcn):
     """main_dgl_reddit_gat.py:155-168."""
     model.train()
@@ -265,7 +313,8 @@ def spmm_edges_per_epoch(num_layers, num_edges):
 
 def main():
     p = argparse.ArgumentParser("full-graph training on the MI355X message-passing backend")
-    p.add_argument("--model", default="sage", choices=["sage", "gat"])
+    p.add_argument("--model", default="sage", choices=["sage", "gat", "rgcn"],
+                   help="rgcn: the edge-weighted relational model on the proteins stand-in (--dataset is not read)")
     p.add_argument("--dataset", default="products")
     p.add_argument("--epochs", type=int, default=10)
     p.add_argument("--scale", type=float, default=1.0)
@@ -300,6 +349,17 @@ def main():
                 dur.append(time.time() - t0)
             print("epoch %d loss %.4f time %.4f" % (epoch, loss, time.time() - t0))
         edges = spmm_edges_per_epoch(cfg["num_layers"], g.number_of_edges())
+    elif args.model == "rgcn":
+        data, g, node_feats, edge_weights, model, opt = build_rgcn(
+            device, args.scale, num_layers=args.num_layers or 3, hidden=args.num_hidden or 32, dropout=args.dropout or 0.)
+        print(g)
+        for epoch in range(1, args.epochs + 1):
+            t0 = time.time()
+            loss = rgcn_train_step(model, g, node_feats, edge_weights, data.y_true, data.train_idx, opt)
+            if epoch >= 3:
+                dur.append(time.time() - t0)
+            print("epoch %d loss %.4f time %.4f" % (epoch, loss, time.time() - t0))
+        edges = spmm_edges_per_epoch(len(model.gnn_layers), g.number_of_edges())
     else:
         from mi355x_graph.datasets import NodeData
         data = NodeData(args.dataset, device=device, scale=args.scale)

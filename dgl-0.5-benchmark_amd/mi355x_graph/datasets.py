@@ -124,6 +124,23 @@ class NodeData(object):
         return 1
 
 
+class ProteinsLike(object):
+    """ogbn-proteins-shaped stand-in for the relational full-graph workload (main_dgl_proteins_rgcn_for.py:151-161): the graph of
+    SHAPES["proteins"] (N 132,534, 79.1 M directed edges), `edge_feat` [E, 8] in U[0, 1) -- one prior weight per relation, as the real
+    edata['feat'] --, `y_true` [N, 112] binary targets and a `train_idx` of ~65 % of the nodes (OGB's species split trains on 86,619)."""
+
+    def __init__(self, device="cpu", scale=1.0, num_relations=8):
+        base = NodeData("proteins", device=device, scale=scale)
+        self.graph, self.num_nodes, self.num_tasks, self.num_relations = base.graph, base.num_nodes, SHAPES["proteins"]["classes"], num_relations
+        device = torch.device(device)
+        gen = torch.Generator(device=device)
+        gen.manual_seed(SHAPES["proteins"]["seed"] + 200)
+        self.edge_feat = torch.rand(self.graph.number_of_edges(), num_relations, generator=gen, device=device)
+        self.y_true = (torch.rand(self.num_nodes, self.num_tasks, generator=gen, device=device) < 0.3).to(torch.int64)
+        self.train_idx = torch.nonzero(torch.rand(self.num_nodes, generator=gen, device=device) < 0.65).flatten()
+        self.graph.edata["feat"] = self.edge_feat
+
+
 def RedditDataset(self_loop=False, **kw):
     from . import diskio
     d = diskio.find_dataset("reddit")  # the real files when MGX_DATA_ROOT holds them

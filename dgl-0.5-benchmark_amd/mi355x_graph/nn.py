@@ -6,6 +6,7 @@
 Parameter names, shapes and initialisation follow DGL v0.6.x so state_dicts and the scripts'
 reset_parameters() calls (main_dgl_reddit_gat.py:57-59) line up.
 """
+import math
 import os
 
 import torch
@@ -294,6 +295,44 @@ class SAGEConv(nn.Module):
             if self.norm is not None:
                 rst = self.norm(rst)
             return rst
+
+
+class RelGraphConv(nn.Module):
+    """Edge-weighted relational graph convolution, the layer of main_dgl_proteins_rgcn_for.py:14-60 (every pair of connected nodes
+    carries an edge of every relation, each with a prior weight):
+
+        h_v = act( sum_r (mean_{e: u -> v} w[e, r] * x_u) W_r  +  skip(x_v) ),  then dropout.
+
+    Parameters are the script's -- `_rel_fcs`, R matrices [in, out] with kaiming_uniform_(a = sqrt(5)), and `_skip` = Linear(in, out)
+    -- so a state_dict moves across.  The R aggregations are ONE ops.rel_gspmm over the graph, and the R products with their sum are one
+    GEMM [N, R * in] x [R * in, out] against the stacked `_rel_fcs` (the sum over relations is the GEMM's K dimension)."""
+
+    def __init__(self, in_feats, out_feats, num_relations, activation=None, dropout=0.):
+        super(RelGraphConv, self).__init__()
+        self._num_relations, self._in_feats, self._out_feats = num_relations, in_feats, out_feats
+        self._rel_fcs = nn.ParameterList([nn.Parameter(torch.empty(in_feats, out_feats)) for _ in range(num_relations)])
+        self._skip = nn.Linear(in_feats, out_feats, bias=True)
+        self._activation = activation
+        self._dropout = nn.Dropout(dropout)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for rel_fc in self._rel_fcs:
+            nn.init.kaiming_uniform_(rel_fc, a=math.sqrt(5))
+        self._skip.reset_parameters()
+
+    def forward(self, g, node_feats, edge_weights):
+        """edge_weights: an [E, R] matrix in edge-id order, or the script's list of R [E, 1] columns."""
+        w = ops.rel_weight_matrix(g, edge_weights)
+        if w.shape[1] != self._num_relations:
+            raise DGLError("RelGraphConv: %d relations, got edge weights of %d" % (self._num_relations, w.shape[1]))
+        agg = ops.rel_gspmm(g, node_feats, w, "mean")                          # [N_dst, R, in]
+        stacked = torch.cat(list(self._rel_fcs), 0)                            # [R * in, out]
+        h_dst = node_feats[:agg.shape[0]]
+        h = torch.matmul(agg.reshape(agg.shape[0], -1), stacked) + self._skip(h_dst)
+        if self._activation:
+            h = self._activation(h)
+        return self._dropout(h)
 
 
 class GraphConv(nn.Module):

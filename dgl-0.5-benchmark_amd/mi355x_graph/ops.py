@@ -19,7 +19,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "segment_reduce", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "segment_reduce", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -1357,6 +1357,142 @@ def gspmm(g, op, reduce_op, lhs_data, rhs_data):
     out = GSpMM.apply(gidx, op, reduce_op, X, Y)
     squeeze = (expand_l or X is None) and (expand_r or Y is None) and (expand_l or expand_r)
     return out.squeeze(-1) if squeeze else out
+
+
+class RelWeightCache(object):
+    """The [E, R] edge weights of a multi-relation g-SpMM permuted into the position order of a graph's in-CSR (forward) and out-CSR
+    (reverse walk): for ogbn-proteins they are constant data, so the two permutations are paid once.  Keyed on the tensor's storage
+    (data_ptr, shape, strides), its version counter and the graph index, the way CatBuffer and the slot tags are: an in-place write to
+    the weights, another tensor or another graph drops both copies."""
+
+    def __init__(self):
+        self._key, self._gidx, self._held, self._perm = None, None, None, {}
+
+    @staticmethod
+    def _key_of(w):
+        return (w.data_ptr(), int(w._version), tuple(w.shape), tuple(w.stride()), w.device)
+
+    def get(self, gidx, w, side):
+        """w in the order of gidx.csc() (side "in") or gidx.csr() (side "out"); [nnz, R] contiguous."""
+        key = self._key_of(w)
+        if key != self._key or self._gidx is not gidx:
+            self._key, self._gidx, self._held, self._perm = key, gidx, w, {}  # (`_held` keeps the storage, and so its address, alive)
+        if side not in self._perm:
+            self._perm[side] = _permute_rel_weights(gidx.csc() if side == "in" else gidx.csr(), w)
+        return self._perm[side]
+
+    def holds(self, gidx, w, side):
+        return self._gidx is gidx and self._key == self._key_of(w) and side in self._perm
+
+
+def _permute_rel_weights(csr, w):
+    with torch.no_grad():
+        w = w.detach()
+        if csr.eids is None:
+            return w.contiguous()
+        return sparse.backend_for(w).gather_rows(w, csr.eids)
+
+
+def rel_weight_cache_for(g):
+    """The RelWeightCache kept on a graph's index: every layer of a model passes the same edge weights, so they share one."""
+    gidx = _gidx(g)
+    cache = gidx.__dict__.get("_rel_weights")
+    if cache is None:
+        cache = gidx.__dict__["_rel_weights"] = RelWeightCache()
+    return cache
+
+
+class RelGSpMM(torch.autograd.Function):
+    """out[v, r, :] = sum | mean_{e: u -> v} w[e, r] * x[u, :] in one walk of the in-CSR (csrc/spmm_rel.hip); the gradient with respect
+    to x in one walk of the out-CSR.  w is constant here (rel_gspmm sends weights that need a gradient to gspmm)."""
+
+    @staticmethod
+    def forward(ctx, gidx, reduce_op, x, w, cache):
+        csc = gidx.csc()
+        be = sparse.backend_for(x)
+        w_in = cache.get(gidx, w, "in") if cache is not None else _permute_rel_weights(csc, w)
+        ctx.backward_cache = gidx, reduce_op, cache
+        ctx.save_for_backward(w)
+        return be.spmm_rel(csc, reduce_op, w_in, x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dZ):
+        gidx, reduce_op, cache = ctx.backward_cache
+        w, = ctx.saved_tensors
+        if not ctx.needs_input_grad[2]:
+            return None, None, None, None, None
+        rev = gidx.csr()  # rows = src: the reversed graph's in-CSR
+        w_out = cache.get(gidx, w, "out") if cache is not None else _permute_rel_weights(rev, w)
+        inv = gidx.csc().inv_degrees() if reduce_op == "mean" else None  # the 1 / deg of `mean`, per gathered row of dZ
+        dX = sparse.backend_for(dZ).spmm_rel_grad(rev, w_out, dZ.contiguous(), dst_scale=inv)
+        return None, None, dX, None, None
+
+
+def rel_weight_matrix(g, edge_weights):
+    """The [E, R] weight matrix of a relational layer from what its caller holds: the matrix itself, or the list of R [E, 1] columns the
+    reference script builds (main_dgl_proteins_rgcn_for.py:159-161).  Columns that are views of one matrix -- slices feat[:, t:t+1] of
+    an edge-feature matrix already on the device -- give that matrix back as a view (same storage and version counter, nothing copied);
+    any other list is concatenated once and kept on the graph until one of its tensors changes."""
+    if torch.is_tensor(edge_weights):
+        if edge_weights.dim() != 2:
+            raise DGLError("edge_weights: expected an [E, R] matrix or a list of R [E, 1] columns, got shape %s" % (tuple(edge_weights.shape),))
+        return edge_weights
+    cols = list(edge_weights)
+    if not cols:
+        raise DGLError("edge_weights: empty list")
+    first, R = cols[0], len(cols)
+    for c in cols:
+        if not torch.is_tensor(c) or c.shape[0] != first.shape[0] or c.numel() != c.shape[0] or c.dtype != first.dtype or c.device != first.device:
+            raise DGLError("edge_weights: expected R columns of one length, dtype and device")
+    if R == 1:
+        return first.reshape(-1, 1)
+    E, step, size = int(first.shape[0]), int(first.stride(0)), first.element_size()
+    store = first.untyped_storage().data_ptr()
+    if (E > 0 and step >= R and not any(c.requires_grad for c in cols)
+            and all(c.untyped_storage().data_ptr() == store and int(c.stride(0)) == step and c.data_ptr() == first.data_ptr() + r * size
+                    for r, c in enumerate(cols))):
+        return torch.as_strided(first, (E, R), (step, 1))
+    if any(c.requires_grad for c in cols):
+        return torch.cat([c.reshape(-1, 1) for c in cols], 1)
+    gidx = _gidx(g)
+    key = tuple((c.data_ptr(), int(c._version)) for c in cols)
+    held = gidx.__dict__.get("_rel_weight_cat")
+    if held is None or held[0] != key:
+        held = gidx.__dict__["_rel_weight_cat"] = (key, cols, torch.cat([c.reshape(-1, 1) for c in cols], 1))
+    return held[2]
+
+
+def rel_gspmm_fused(g, x, w):
+    """True when rel_gspmm(g, x, w) runs the one-pass kernels (else it is gspmm's (N, 1, D) x (E, R, 1) broadcast)."""
+    gidx = _gidx(g)
+    if (not torch.is_tensor(x) or not torch.is_tensor(w) or x.dim() != 2 or w.dim() != 2 or w.requires_grad or not x.is_cuda or not w.is_cuda
+            or x.dtype != torch.float32 or w.dtype != torch.float32 or x.device != w.device or x.device.type not in sparse._BACKENDS
+            or _torch_ops() is not None or capture_path()):
+        return False
+    be = sparse.backend_for(x)
+    if not hasattr(be, "spmm_rel") or x.shape[0] != gidx.num_src or w.shape[0] != gidx.num_edges() or gidx.num_edges() == 0:
+        return False
+    return be.spmm_rel_supported(gidx.csc(), x, int(w.shape[1]))
+
+
+def rel_gspmm(g, x, w, reduce="mean", cache=None):
+    """Multi-relation g-SpMM: out[v, r, :] = reduce_{e: u -> v} w[e, r] * x[u, :] for all R relations at once.
+
+    x: [N_src, D], w: [E, R] in edge-id order, result [N_dst, R, D]; reduce: "sum" or "mean".  This is the R update_all(fn.u_mul_e,
+    fn.mean) calls of the edge-weighted relational layer (main_dgl_proteins_rgcn_for.py:50-53) in one pass over the graph.  fp32 device
+    operands with 1 <= R <= 16 and D a power of two up to 128 run csrc/spmm_rel.hip (forward and the gradient with respect to x);
+    weights that need a gradient, and every other operand, take gspmm(g, "mul", reduce, x[:, None, :], w[:, :, None]) -- the same values
+    through the broadcast kernels.  cache: a RelWeightCache for the permuted weights (default: the one kept on the graph; False: none)."""
+    if reduce not in ("sum", "mean"):
+        raise DGLError("rel_gspmm: reduce must be 'sum' or 'mean', got %r" % (reduce,))
+    if x.dim() != 2 or w.dim() != 2:
+        raise DGLError("rel_gspmm: expected x [N_src, D] and w [E, R], got shapes %s and %s" % (tuple(x.shape), tuple(w.shape)))
+    if not rel_gspmm_fused(g, x, w):
+        return gspmm(g, "mul", reduce, x.unsqueeze(1), w.unsqueeze(-1))
+    if cache is None:
+        cache = rel_weight_cache_for(g)
+    return RelGSpMM.apply(_gidx(g), reduce, x, w, cache if cache is not False else None)
 
 
 def gsddmm(g, op, lhs_data, rhs_data, lhs_target="u", rhs_target="v"):

@@ -615,6 +615,51 @@ class HipBackend(object):
                 PROFILE.append(rec)
         return out2d
 
+    @staticmethod
+    def spmm_rel_supported(csr, x2d, R):
+        """True when mgx_spmm_rel / mgx_spmm_rel_grad have a kernel for a [num_cols, D] operand and R relations over this CSR."""
+        D = int(x2d.shape[1]) if x2d.dim() == 2 else 0
+        return (x2d.dim() == 2 and x2d.is_cuda and x2d.dtype == torch.float32 and 1 <= R <= 16 and 1 <= D <= 128 and D & (D - 1) == 0
+                and x2d.stride(1) == 1 and x2d.stride(0) >= D and x2d.stride(0) % min(D, 4) == 0 and x2d.data_ptr() % (4 * min(D, 4)) == 0
+                and csr.indptr.is_cuda and csr.nnz > 0)
+
+    def spmm_rel(self, csr, reduce, w_pos, x2d, src_scale=None, dst_scale=None):
+        """out[v, r, :] = dst_scale[v] * sum|mean_{p in row v} w_pos[p, r] * src_scale[u_p] * x2d[u_p, :] (mgx_spmm_rel); w_pos: [nnz, R] in
+        the CSR's position order; x2d may be a row-strided view.  Returns [num_rows, R, D]."""
+        dev = self._check_dev(csr.indptr, w_pos, x2d, src_scale, dst_scale)
+        R, D = int(w_pos.shape[1]), int(x2d.shape[1])
+        if w_pos.shape[0] != csr.nnz or x2d.shape[0] != csr.num_cols or not w_pos.is_contiguous() or x2d.stride(1) != 1:
+            raise DGLError("spmm_rel: expected contiguous [nnz, R] weights and a row-strided [num_cols, D] operand")
+        out = torch.empty((csr.num_rows, R, D), dtype=torch.float32, device=dev)
+        plan = csr.plan()
+        partial = None
+        if plan is not None and plan.num_slots:
+            partial = torch.empty((plan.num_slots, R * D), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="spmm_rel", reduce=reduce, R=R, out_len=D, nnz=csr.nnz):
+            _lib.check(_lib.lib().mgx_spmm_rel(
+                ctypes.byref(csr.c_struct()), None if plan is None else ctypes.byref(plan.c_struct()), REDUCE[reduce], R, D, _ptr(w_pos),
+                _ptr(x2d), int(x2d.stride(0)), _ptr(src_scale), _ptr(dst_scale), _ptr(out), _ptr(partial), _stream(dev)))
+        return out
+
+    def spmm_rel_grad(self, csr_t, w_pos_t, dz3d, dst_scale=None, src_scale=None):
+        """dx[u, :] = src_scale[u] * sum_{p in row u} sum_r w_pos_t[p, r] * dst_scale[v_p] * dz3d[v_p, r, :] (mgx_spmm_rel_grad) over the
+        TRANSPOSED CSR (rows = source nodes) with the weights in its position order; dz3d: [num_cols, R, D] contiguous."""
+        dev = self._check_dev(csr_t.indptr, w_pos_t, dz3d, src_scale, dst_scale)
+        R, D = int(dz3d.shape[1]), int(dz3d.shape[2])
+        if (w_pos_t.shape[0] != csr_t.nnz or int(w_pos_t.shape[1]) != R or dz3d.shape[0] != csr_t.num_cols or not w_pos_t.is_contiguous()
+                or not dz3d.is_contiguous()):
+            raise DGLError("spmm_rel_grad: expected contiguous [nnz, R] weights and a contiguous [num_cols, R, D] gradient")
+        dx = torch.empty((csr_t.num_rows, D), dtype=torch.float32, device=dev)
+        plan = csr_t.plan()
+        partial = None
+        if plan is not None and plan.num_slots:
+            partial = torch.empty((plan.num_slots, D), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="spmm_rel_grad", R=R, out_len=D, nnz=csr_t.nnz):
+            _lib.check(_lib.lib().mgx_spmm_rel_grad(
+                ctypes.byref(csr_t.c_struct()), None if plan is None else ctypes.byref(plan.c_struct()), R, D, _ptr(w_pos_t), _ptr(dz3d),
+                _ptr(dst_scale), _ptr(src_scale), _ptr(dx), _ptr(partial), _stream(dev)))
+        return dx
+
     def sddmm(self, graph_index, op, L, R, lhs_target, rhs_target, l_len, r_len, out_len, reduce_size, l_off, r_off):
         """graph_index supplies either COO (edge-id order) or the in-CSR."""
         nnz = graph_index.num_edges()

@@ -281,6 +281,29 @@ int32_t mgx_spmm_tile_copy_u(const mgx_csr* csr, const mgx_spmm_plan* plan /* ma
                              int32_t reduce, const float* ufeat, int64_t D, int64_t u_stride, const float* dst_scale /* may be NULL */,
                              float* out, int64_t out_stride, float* partial_ws, int32_t flags, void* stream);
 
+/* Multi-relation g-SpMM (csrc/spmm_rel.hip): ALL R relations of an edge-weight matrix in one walk of the graph -- the edge-weighted
+ * relational layer of main_dgl_proteins_rgcn_for.py:46-60, which the reference runs as R update_all(fn.u_mul_e, fn.mean) calls with
+ * [E, 1] weight columns.
+ *
+ *   mgx_spmm_rel       out[v, r, d] = dst_scale[v] * SUM | MEAN_{p in row v} w[p, r] * src_scale[u_p] * x[u_p, d]      r < R, d < D
+ *   mgx_spmm_rel_grad  dx[u, d]     = src_scale[u] * SUM_{p in row u} SUM_r w[p, r] * dst_scale[v_p] * dz[v_p, r, d]
+ *
+ * w: [nnz, R] fp32 in the POSITION order of the CSR passed (NOT by edge id: permute once with mgx_gather_rows(idx = csr->eids, D = R));
+ * csr->eids is not read.  x: [num_cols, D] rows x_stride floats apart; out: [num_rows, R * D] dense.  MEAN divides by max(in_degree, 1),
+ * empty rows give 0.  mgx_spmm_rel_grad is the gradient with respect to x: `csr` is the TRANSPOSED CSR (rows = source nodes u, indices =
+ * destination nodes v_p) with w in THAT CSR's position order, dz: [num_cols, R * D] dense, dx: [num_rows, D] dense; the 1 / deg of a MEAN
+ * forward goes into dst_scale.  src_scale / dst_scale: optional per-node factors (NULL = 1), indexed by source / destination node in both
+ * entries.  plan / partial_ws as for mgx_spmm_csr (one schedule, no `rest` part; partial_ws: plan->num_slots * R * D floats forward,
+ * plan->num_slots * D reverse).  int32 and int64 graphs; offsets into w are 64-bit.  Deterministic: no atomics, fixed summation order
+ * for a given graph, plan, R and D.  1 <= R <= 16 and D in {1, 2, 4, ..., 128}, operands of D >= 4 16-byte aligned with x_stride % 4
+ * == 0 (D = 2: 8 bytes, even stride); otherwise MGX_ERR_UNSUPPORTED (call mgx_spmm_csr per relation, or with the (N, 1, D) x (E, R, 1)
+ * broadcast).  mgx_last_spmm_kernel(): "rel" / "rel_grad". */
+int32_t mgx_spmm_rel(const mgx_csr* csr, const mgx_spmm_plan* plan /* may be NULL */, int32_t reduce, int64_t R, int64_t D,
+                     const float* w, const float* x, int64_t x_stride, const float* src_scale, const float* dst_scale, float* out,
+                     float* partial_ws, void* stream);
+int32_t mgx_spmm_rel_grad(const mgx_csr* csr, const mgx_spmm_plan* plan /* may be NULL */, int64_t R, int64_t D, const float* w,
+                          const float* dz, const float* dst_scale, const float* src_scale, float* dx, float* partial_ws, void* stream);
+
 /* ------------------------------------------------------------------ g-SDDMM
  * Replaces _CAPI_DGLKernelSDDMM as reached by dgl.ops.gsddmm (kernel/dgl-new.py:39),
  * apply_edges(fn.u_add_v) inside GATConv (main_dgl_reddit_gat.py:10) and fn.u_dot_v
