@@ -754,6 +754,24 @@ __global__ __launch_bounds__(kBlock) void spmm_hub_fixup_kernel(const Idx* indpt
   }
 }
 
+// out[row, :] = out[row, :] / max(deg, 1) (mean) * dst_scale[row]: the epilogue of a sum that several launches formed unscaled in `out`
+// (u_add_e below), applied ONCE to the exact total.  One thread per element.
+template <typename Idx>
+__global__ __launch_bounds__(kBlock) void spmm_row_scale_kernel(const Idx* indptr, const float* dst_scale, float* out, int64_t n_rows,
+                                                                int D, int mean, int ldo) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n_rows * (int64_t)D) return;
+  const int64_t row = i / D;
+  const int k = (int)(i - row * D);
+  float v = out[row * ldo + k];
+  if (mean) {
+    const int64_t deg = (int64_t)indptr[row + 1] - (int64_t)indptr[row];
+    v = v / (float)(deg > 1 ? deg : 1);
+  }
+  if (dst_scale) v *= dst_scale[row];
+  out[row * ldo + k] = v;
+}
+
 // used by spmm_tile.hip: the same fix-up pass after the tile kernel
 int32_t spmm_hub_fixup_launch(const mgx_csr* csr, const mgx_spmm_plan* plan, const float* partial, const float* dst_scale, float* out,
                               int D, int mean, int accum, int ldo, hipStream_t s) {
@@ -1067,21 +1085,38 @@ static int32_t spmm_impl(const mgx_csr* csr, const mgx_spmm_plan* plan, float* p
     }
     // u_add_e with full-width operands: sum_e (U[u] + E[e]) = (copy_u sum) + (copy_e sum) -- two launches of the fast kernels,
     // the second accumulating into the first's output, instead of the generic one-wave-per-row kernel (128 -> ~25 us on a
-    // molhiv-sized batch).  mean and dst_scale distribute over the sum; src_scale belongs to the U term only.
+    // molhiv-sized batch).  src_scale belongs to the U term only.  mean / dst_scale: both launches leave the UNSCALED sums in `out`
+    // and spmm_row_scale_kernel divides the total once -- mean(U) + mean(E) rounds two quotients and is off by many ulp of the result
+    // where the two sums cancel.  Accumulating into the caller's values leaves no room for the unscaled total: there (only) the
+    // factors distribute over the two launches.
     if (op == MGX_OP_ADD && no_bcast && u_len == out_len && e_len == out_len && U && E) {
+      const bool scale_after = !accumulate && (a.mean || dst_scale);
+      if (scale_after) { a.mean = 0; a.dst_scale = nullptr; }
+      auto add_fixup = [&](int accum) -> int32_t {
+        if (plan && plan->num_hubs > 0) {
+          hipLaunchKernelGGL((spmm_hub_fixup_kernel<Idx>), dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)),
+                             dim3(kBlock), 0, s, a.indptr, plan->hub_row, plan->hub_slot_ptr, plan->num_hubs,
+                             (const float*)partial_ws, a.dst_scale, out, a.D, a.mean, accum, a.ldo);
+          MGX_CHECK_LAUNCH();
+        }
+        return MGX_OK;
+      };
       a.src = U; a.src_rows = csr->num_cols;
       launch_fast<Idx, MODE_COPY_LHS>(a, csr->nnz, s);
       MGX_CHECK_LAUNCH();
-      int32_t st = fixup();
+      int32_t st = add_fixup(a.accum);
       if (st != MGX_OK) return st;
       SpmmFastArgs<Idx> b = a;
       b.src = E; b.src_rows = csr->nnz; b.src_scale = nullptr; b.accum = 1;
       launch_fast<Idx, MODE_COPY_RHS>(b, csr->nnz, s);
       MGX_CHECK_LAUNCH();
-      if (plan && plan->num_hubs > 0) {
-        hipLaunchKernelGGL((spmm_hub_fixup_kernel<Idx>), dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)),
-                           dim3(kBlock), 0, s, a.indptr, plan->hub_row, plan->hub_slot_ptr, plan->num_hubs,
-                           (const float*)partial_ws, dst_scale, out, a.D, a.mean, 1, a.ldo);
+      st = add_fixup(1);
+      if (st != MGX_OK) return st;
+      if (scale_after) {
+        const int64_t total = n_rows * out_len;
+        MGX_CHECK_ARG((total + kBlock - 1) / kBlock < (int64_t(1) << 31), "mgx_spmm_csr: output too large");
+        hipLaunchKernelGGL((spmm_row_scale_kernel<Idx>), dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, a.indptr,
+                           dst_scale, out, n_rows, a.D, reduce == MGX_REDUCE_MEAN ? 1 : 0, a.ldo);
         MGX_CHECK_LAUNCH();
       }
       return MGX_OK;
