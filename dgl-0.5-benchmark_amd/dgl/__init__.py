@@ -8,7 +8,7 @@ from mi355x_graph.transform import (to_bidirected, add_self_loop, remove_self_lo
                                     reverse, from_networkx, from_scipy, batch, unbatch)
 from mi355x_graph import function, ops  # noqa: F401
 from . import nn, data, dataloading, utils, sampling, transform, backend  # noqa: F401
-from mi355x_graph.sampling import to_block, NID, EID  # noqa: F401
+from mi355x_graph.sampling import to_block, in_subgraph, NID, EID  # noqa: F401
 from mi355x_graph.ops import edge_softmax  # noqa: F401
 
 __version__ = "0.6.1+mi355x"

@@ -6,10 +6,17 @@ path -- bipartite "block" graphs on which the same g-SpMM / g-SDDMM kernels run 
       :67-75 (full-neighbour inference with fanout None)
   dgl.to_block, dgl.sampling.sample_neighbors, g.subgraph(mask)   reddit/load_graph.py:45-51
 
-Sampling is index work done with torch integer ops on whatever device holds the graph (the reference samples in CPU
-worker processes; sampling next to the features on the GPU removes the host round trip).  Semantics follow
-DGL: uniform WITHOUT replacement over the in-edges of each seed, rows with in-degree <= fanout keep all
-their edges, destination nodes of a block are a prefix of its source nodes (block.srcdata[NID][:num_dst] ==
+  dgl.sampling.sample_neighbors(g, seeds, fanout, replace=True), dgl.in_subgraph
+      end_to_end/sampling/node-classification/ogbn-product/ns-gat/ns-gat-dgl.py:22-42 (a hand-written NeighborSampler)
+
+Sampling is index work done where the graph lives (the reference samples in CPU worker processes; sampling next to
+the features on the GPU removes the host round trip): HIP kernels (csrc/sample.hip) for device graphs and fanout <= 64,
+torch integer ops of the same semantics otherwise.  Semantics follow DGL's sample_neighbors: over the in-edges of each
+seed (edge_dir="out": the out-edges), uniformly or proportionally to a non-negative edge weight (`prob`, an edge of
+weight 0 is never picked), without replacement (a row with no more than `fanout` eligible edges keeps them all) or with
+(`fanout` independent draws for every row that has an eligible edge; duplicates stay, as multi-edges); select_topk is
+the deterministic sibling.  Every mode returns its edges grouped by seed in seed order, CSR positions non-decreasing
+inside a seed.  Destination nodes of a block are a prefix of its source nodes (block.srcdata[NID][:num_dst] ==
 block.dstdata[NID]).
 """
 import math
@@ -23,11 +30,176 @@ NID = "_ID"
 EID = "_ID"
 
 
-def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, generator=None):
-    """Returns (src, dst, eid) of the sampled in-edges of `nodes` in GLOBAL ids."""
-    if edge_dir != "in" or prob is not None or replace:
-        raise DGLError("sample_neighbors: only uniform in-edge sampling without replacement is supported")
+DEVICE_MAX_FANOUT = 64  # fanout / k the HIP kernels take (include/mi355x_graph.h); above it the torch formulation runs
+
+
+def _rng_seed(generator):
+    if generator is None or generator.device.type == "cpu":
+        return int(torch.randint(0, 2 ** 62, (1,), generator=generator).item())
+    return int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item())
+
+
+def _rand(n, dev, generator):
+    """n fp64 numbers in [0, 1) on `dev`, drawn from `generator` on whichever device it lives."""
+    if generator is not None and generator.device != torch.device(dev):
+        return torch.rand(n, generator=generator, dtype=torch.float64, device=generator.device).to(dev)
+    return torch.rand(n, device=dev, generator=generator, dtype=torch.float64)
+
+
+def _edge_weights(g, idx, w, what):
+    """`w` (the name of an edge feature or a tensor) -> a contiguous fp32 vector with one weight per edge id, where the graph lives."""
+    if isinstance(w, str):
+        if not isinstance(g, DGLGraph) or w not in g.edata:
+            raise DGLError("%s: the graph has no edge feature %r" % (what, w))
+        w = g.edata[w]
+    w = torch.as_tensor(w)
+    if w.dim() != 1 or w.shape[0] != idx.num_edges() or not (w.is_floating_point()):
+        raise DGLError("%s: expected one floating-point weight per edge (%d), got a tensor of shape %s, %s"
+                       % (what, idx.num_edges(), tuple(w.shape), w.dtype))
+    return w.detach().to(device=idx.device, dtype=torch.float32).contiguous()
+
+
+def _candidates(view, nodes):
+    """Every stored edge of the rows `nodes` of `view`, row after row: (CSR positions, seed slot of each, first candidate of each
+    slot, row lengths)."""
+    dev = view.device
+    indptr = view.indptr.long()
+    beg = indptr[nodes]
+    deg = indptr[nodes + 1] - beg
+    total = int(deg.sum().item())
+    seg = torch.repeat_interleave(torch.arange(nodes.shape[0], device=dev), deg, output_size=total)
+    first = torch.cumsum(deg, 0) - deg
+    pos = torch.arange(total, device=dev) - first[seg] + beg[seg]
+    return pos, seg, first, deg
+
+
+def _smallest_per_segment(key, seg, first, k, eligible=None):
+    """Candidate numbers of the k smallest keys of every segment (equal keys: the earlier candidate), in candidate order."""
+    order = torch.argsort(key, stable=True)
+    order = order[torch.argsort(seg[order], stable=True)]  # by segment, by key inside a segment, by position among equal keys
+    rank = torch.arange(key.shape[0], device=key.device) - first[seg[order]]
+    keep = rank < k
+    if eligible is not None:  # ineligible candidates carry +inf keys: they sort after every eligible one of their segment
+        keep &= eligible[order]
+    return torch.sort(order[keep])[0]
+
+
+def _sample_torch(view, nodes, fanout, w, replace, generator):
+    """sample_neighbors in torch ops (CPU graphs, fanout above the device limit); `w`: per-edge-id weights or None.
+    Returns (CSR positions, seed slot of each pick)."""
+    dev = view.device
+    pos, seg, first, deg = _candidates(view, nodes)
+    total = pos.shape[0]
+    eligible = None
+    if w is not None:
+        wc = w[pos if view.eids is None else view.eids[pos].long()]
+        if bool((~(wc >= 0) | torch.isinf(wc)).any()):
+            raise DGLError("sample_neighbors: edge weights must be finite and non-negative")
+        eligible = wc > 0
+    if total == 0:
+        return pos, seg
+    if fanout is None or fanout < 0:  # every (eligible) edge
+        return (pos, seg) if eligible is None else (pos[eligible], seg[eligible])
+    if not replace:
+        u = 1.0 - _rand(total, dev, generator)  # (0, 1]
+        if w is None:
+            key = u
+        else:  # Efraimidis-Spirakis: the k smallest -log(u) / w are k successive draws proportional to w without replacement
+            key = torch.where(eligible, -torch.log(u) / wc.double(), torch.full_like(u, float("inf")))
+        keep = _smallest_per_segment(key, seg, first, fanout, eligible)
+        return pos[keep], seg[keep]
+    n_seeds = nodes.shape[0]
+    ar = torch.arange(total, device=dev)
+    if w is None:
+        active = torch.nonzero(deg > 0).flatten()
+    else:
+        # last eligible candidate of every slot: where a target that rounding pushed to the row total (or past it) lands
+        last = torch.full((n_seeds,), -1, dtype=torch.int64, device=dev)
+        last.scatter_reduce_(0, seg[eligible], ar[eligible], "amax", include_self=True)
+        active = torch.nonzero(last >= 0).flatten()
+    slot = torch.repeat_interleave(active, fanout)  # slot of every draw, `fanout` draws per slot that has an eligible edge
+    u = _rand(slot.shape[0], dev, generator)
+    if w is None:
+        pick = first[slot] + torch.minimum((u * deg[slot].double()).long(), deg[slot] - 1)
+    else:
+        # inverse CDF: one running sum over all candidates (fp64; a weight of 0 repeats its predecessor's sum bit for bit), each
+        # slot's stretch of it starts at `start`; the first candidate whose inclusive sum is strictly above start + u * W
+        csum = torch.cumsum(wc.double(), 0)
+        start = torch.where(first > 0, csum[torch.clamp(first - 1, min=0)], torch.zeros((), dtype=torch.float64, device=dev))
+        row_total = csum[torch.clamp(first + deg - 1, min=0)] - start
+        target = start[slot] + u * row_total[slot]
+        pick = torch.minimum(torch.searchsorted(csum, target, right=True), last[slot])
+    pick = torch.sort(pick)[0]  # candidate numbers grow with the slot, then with the CSR position: one sort gives the output order
+    return pos[pick], seg[pick]
+
+
+def _triple(view, nodes, pos, seg, edge_dir):
+    picked = view.indices[pos].long()
+    seeds = nodes[seg]
+    eid = pos if view.eids is None else view.eids[pos].long()
+    return (picked, seeds, eid) if edge_dir == "in" else (seeds, picked, eid)
+
+
+def _view(idx, edge_dir, what):
+    if edge_dir not in ("in", "out"):
+        raise DGLError("%s: edge_dir must be 'in' or 'out', got %r" % (what, edge_dir))
+    return idx.csc() if edge_dir == "in" else idx.csr()
+
+
+def _sample_modes(g, idx, nodes, fanout, edge_dir, prob, replace, generator):
+    """Every mode but the uniform in-edge one without replacement: prob=, replace=True, edge_dir='out'."""
+    view = _view(idx, edge_dir, "sample_neighbors")
+    dev = view.device
+    nodes = torch.as_tensor(nodes, device=dev).long()
+    w = None if prob is None else _edge_weights(g, idx, prob, "sample_neighbors")
+    if nodes.is_cuda and fanout is not None and 1 <= fanout <= DEVICE_MAX_FANOUT:
+        from . import sparse
+        backend = sparse.backend_for(view.indptr)
+        seeds = nodes.to(view.indptr.dtype)
+        if w is None and not replace:  # uniform without replacement over the out-CSR: the kernel of the in-edge path
+            picked, eid, counts = backend.sample_neighbors(view, seeds, fanout, _rng_seed(generator))
+        else:
+            picked, eid, counts = backend.sample_neighbors_modes(view, seeds, fanout, w, replace, _rng_seed(generator))
+        seeds = torch.repeat_interleave(nodes, counts, output_size=picked.shape[0])
+        return (picked.long(), seeds, eid.long()) if edge_dir == "in" else (seeds, picked.long(), eid.long())
+    pos, seg = _sample_torch(view, nodes, fanout, w, replace, generator)
+    return _triple(view, nodes, pos, seg, edge_dir)
+
+
+def select_topk(g, k, weight, nodes=None, edge_dir="in", ascending=False):
+    """(src, dst, eid) in GLOBAL ids of the `k` in-edges (edge_dir="out": out-edges) of largest `weight` -- smallest with
+    `ascending` -- of every node, or of every node of `nodes`; all of them where the degree is <= k (k None / -1: everywhere).
+    `weight`: the name of an edge feature or one value per edge id.  Equal weights go to the lower CSR position; the output
+    order is that of sample_neighbors."""
     idx = g._index if isinstance(g, DGLGraph) else g
+    view = _view(idx, edge_dir, "select_topk")
+    dev = view.device
+    nodes = torch.arange(view.num_rows, device=dev) if nodes is None else torch.as_tensor(nodes, device=dev).long()
+    w = _edge_weights(g, idx, weight, "select_topk")
+    if nodes.is_cuda and k is not None and 1 <= k <= DEVICE_MAX_FANOUT:
+        from . import sparse
+        picked, eid, counts = sparse.backend_for(view.indptr).select_topk(view, nodes.to(view.indptr.dtype), k, w, ascending)
+        seeds = torch.repeat_interleave(nodes, counts, output_size=picked.shape[0])
+        return (picked.long(), seeds, eid.long()) if edge_dir == "in" else (seeds, picked.long(), eid.long())
+    pos, seg, first, deg = _candidates(view, nodes)
+    if pos.shape[0] and k is not None and k >= 0:
+        wc = w[pos if view.eids is None else view.eids[pos].long()] + 0.0  # + 0: -0 and +0 are one key, as in the kernel
+        keep = _smallest_per_segment(wc if ascending else -wc, seg, first, k)
+        pos, seg = pos[keep], seg[keep]
+    return _triple(view, nodes, pos, seg, edge_dir)
+
+
+def in_subgraph(g, nodes):
+    """Every in-edge of `nodes` as (src, dst, eid) in GLOBAL ids (ns-gat-dgl.py:34 builds its last frontier with it)."""
+    return sample_neighbors(g, nodes, None)
+
+
+def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, generator=None):
+    """Returns (src, dst, eid) of the sampled in-edges (edge_dir="out": out-edges) of `nodes` in GLOBAL ids.
+    prob: the name of an edge feature or one non-negative weight per edge id; replace: draw with replacement."""
+    idx = g._index if isinstance(g, DGLGraph) else g
+    if edge_dir != "in" or prob is not None or replace:
+        return _sample_modes(g, idx, nodes, fanout, edge_dir, prob, replace, generator)
     csc = idx.csc()
     dev = csc.device
     nodes = torch.as_tensor(nodes, device=dev).long()
@@ -106,17 +278,16 @@ def to_block(g_or_edges, dst_nodes, num_nodes=None, idtype=torch.int64, dst_sort
 class MultiLayerNeighborSampler(object):
     """fanouts[i] = neighbours sampled for layer i (None / -1: all neighbours)."""
 
-    def __init__(self, fanouts, replace=False, return_eids=False):
-        if replace:
-            raise DGLError("sampling with replacement is not supported")
+    def __init__(self, fanouts, replace=False, return_eids=False, prob=None):
         self.fanouts = list(fanouts)
+        self.replace, self.prob = bool(replace), prob
 
     def sample_blocks(self, g, seed_nodes, generator=None):
         blocks = []
         seeds = torch.as_tensor(seed_nodes, device=g.device).long()
         n = g.number_of_nodes()
         for fanout in reversed(self.fanouts):
-            frontier = sample_neighbors(g, seeds, fanout, generator=generator)
+            frontier = sample_neighbors(g, seeds, fanout, prob=self.prob, replace=self.replace, generator=generator)
             # sample_neighbors returns edges grouped by seed in seed order (CSR positions sorted inside a seed)
             block = to_block(frontier, seeds, num_nodes=n, idtype=g.idtype, dst_sorted=True,
                              max_in_degree=fanout if (fanout is not None and fanout >= 0) else None)

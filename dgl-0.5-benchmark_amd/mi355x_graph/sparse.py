@@ -1146,6 +1146,62 @@ class HipBackend(object):
                                                        _ptr(eid), _stream(dev)))
         return src, eid, counts
 
+    @staticmethod
+    def _sample_offsets(counts):
+        """Per-seed counts -> their exclusive cumsum [n + 1]: where each seed's picks go; the last entry sizes the outputs."""
+        offsets = torch.zeros(counts.shape[0] + 1, dtype=torch.int64, device=counts.device)
+        torch.cumsum(counts, 0, out=offsets[1:])
+        return offsets
+
+    def sample_neighbors_modes(self, csr, seeds, fanout, prob, replace, rng_seed):
+        """The modes mgx_sample_neighbors does not have: `prob` (fp32, one weight per edge id, or None) and / or `replace`.
+        Returns (src, eid, counts) like sample_neighbors; DGLError when an in-edge of a seed has a negative, NaN or infinite weight."""
+        dev = self._check_dev(csr.indptr, seeds, prob)
+        n = seeds.shape[0]
+        c = ctypes.byref(csr.c_struct())
+        if prob is None:
+            if not replace:
+                raise DGLError("sample_neighbors_modes: uniform sampling without replacement is sample_neighbors")
+            deg = (csr.indptr[seeds.long() + 1] - csr.indptr[seeds.long()]).long()
+            counts = (deg > 0).long() * fanout
+            offsets = self._sample_offsets(counts)
+            total = int(offsets[-1].item())
+        else:
+            positive = torch.empty(n, dtype=torch.int64, device=dev)
+            invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.lib().mgx_sample_count_positive(c, n, _ptr(seeds), _ptr(prob), _ptr(positive), _ptr(invalid), _stream(dev)))
+            counts = (positive > 0).long() * fanout if replace else torch.clamp(positive, max=fanout)
+            offsets = self._sample_offsets(counts)
+            total, bad = torch.stack([offsets[-1], invalid[0].long()]).tolist()  # output size and the weight flag in one host read
+            if bad:
+                raise DGLError("sample_neighbors: edge weights must be finite and non-negative")
+        src = torch.empty(total, dtype=csr.indptr.dtype, device=dev)
+        eid = torch.empty(total, dtype=csr.indptr.dtype, device=dev)
+        if total == 0:
+            return src, eid, counts
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mgx_sample_neighbors_weighted(c, n, _ptr(seeds), int(fanout), _ptr(prob), 1 if replace else 0,
+                                                                ctypes.c_uint64(rng_seed & (2 ** 64 - 1)), _ptr(offsets), _ptr(src),
+                                                                _ptr(eid), _stream(dev)))
+        return src, eid, counts
+
+    def select_topk(self, csr, seeds, k, weight, ascending):
+        """(src, eid, counts): the k edges of largest (ascending: smallest) weight of every seed's row, ties to the lower CSR position."""
+        dev = self._check_dev(csr.indptr, seeds, weight)
+        deg = (csr.indptr[seeds.long() + 1] - csr.indptr[seeds.long()]).long()
+        counts = torch.clamp(deg, max=k)
+        offsets = self._sample_offsets(counts)
+        total = int(offsets[-1].item())
+        src = torch.empty(total, dtype=csr.indptr.dtype, device=dev)
+        eid = torch.empty(total, dtype=csr.indptr.dtype, device=dev)
+        if total == 0:
+            return src, eid, counts
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mgx_select_topk(ctypes.byref(csr.c_struct()), seeds.shape[0], _ptr(seeds), int(k), _ptr(weight),
+                                                  1 if ascending else 0, _ptr(offsets), _ptr(src), _ptr(eid), _stream(dev)))
+        return src, eid, counts
+
     # ---- halo rows as bitmaps + packed values (csrc/rowpack.hip; dist.SparseHalo)
     ROWPACK_MAX_D = 256
 

@@ -591,6 +591,43 @@ int32_t mgx_sample_neighbors(const mgx_csr* csr, int64_t num_seeds, const void* 
                              uint64_t rng_seed, const int64_t* out_offsets, void* out_src, void* out_eid,
                              void* stream);
 
+/* The other modes of dgl.sampling.sample_neighbors -- prob=, replace=True (ogbn-product/ns-gat/ns-gat-dgl.py:22-42) -- and
+ * dgl.sampling.select_topk: one wave per seed (csrc/sample.hip).  Purely additive entry points: no existing signature or behaviour
+ * changed with them, so mgx_abi_version() stays 35.
+ *
+ * Common to the three entry points below: `csr` is the in-CSR (or the out-CSR for edge_dir="out"; the seeds are its rows), `prob` /
+ * `weight` is fp32 with one value per EDGE ID -- the kernels read prob[eids[p]] for CSR position p, prob[p] only when csr->eids is
+ * NULL.  Output order is that of mgx_sample_neighbors: grouped by seed in seed order, CSR positions non-decreasing inside a seed.
+ * out_offsets is [num_seeds + 1] int64 (exclusive cumsum of the per-seed counts given below, computed by the caller, who allocates
+ * out_src / out_eid with out_offsets[num_seeds] entries of the graph's index width); a kernel never writes more than
+ * out_offsets[s + 1] - out_offsets[s] entries for seed s.  fanout / k in [1, 64]; rows shorter than 2^32 - 1 edges.
+ *
+ * mgx_sample_count_positive: out_counts[s] = number of in-edges of seed s with prob > 0.  *out_invalid (device int32, zeroed by the
+ *   caller) is set to 1 when an in-edge of any seed has a negative, NaN or infinite weight; the caller reads it together with the
+ *   output size and raises.  Weights of edges of other nodes are not looked at. */
+int32_t mgx_sample_count_positive(const mgx_csr* csr, int64_t num_seeds, const void* seeds, const float* prob,
+                                  int64_t* out_counts /* [num_seeds] */, int32_t* out_invalid /* [1] */, void* stream);
+/* mgx_sample_neighbors_weighted:
+ *   prob != NULL, replace == 0   successive weighted sampling without replacement (draw proportionally to weight, remove, repeat) as
+ *       Efraimidis-Spirakis keys: key = -log(u) / w, u strictly inside (0, 1) from (rng_seed, seed slot, CSR position); the `fanout`
+ *       smallest (key, position) pairs among the edges of weight > 0.  count(s) = min(fanout, positive-weight in-edges), all distinct.
+ *   replace != 0   `fanout` independent draws, lane j of the seed's wave owns draw j: position floor(r * deg) when prob == NULL
+ *       (count = fanout when deg > 0, else 0); else the inverse CDF over the row -- the first position whose inclusive running sum,
+ *       taken in row order (fp32 inside a chunk of 64, fp64 across chunks), is strictly greater than u * W, which is never an edge
+ *       of weight 0; a target that rounding pushed to >= W lands on the last positive-weight edge (count = fanout when the seed has
+ *       a positive-weight in-edge, else 0).  Duplicates are written as duplicates.
+ *   prob == NULL, replace == 0 is mgx_sample_neighbors and an error here.
+ *   The same rng_seed gives the same sample, for either index width.  A weight of 0 is never picked; negative / NaN / infinite
+ *   weights are treated as 0 here and reported by mgx_sample_count_positive. */
+int32_t mgx_sample_neighbors_weighted(const mgx_csr* csr, int64_t num_seeds, const void* seeds, int32_t fanout, const float* prob,
+                                      int32_t replace, uint64_t rng_seed, const int64_t* out_offsets, void* out_src, void* out_eid,
+                                      void* stream);
+/* mgx_select_topk: for every seed the k in-edges of largest weight (ascending != 0: smallest), all of them when in_degree <= k
+ *   (count = min(k, in_degree)); equal weights go to the lower CSR position.  Deterministic: the selection of
+ *   mgx_sample_neighbors_weighted with key = -weight (or +weight). */
+int32_t mgx_select_topk(const mgx_csr* csr, int64_t num_seeds, const void* seeds, int32_t k, const float* weight, int32_t ascending,
+                        const int64_t* out_offsets, void* out_src, void* out_eid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
