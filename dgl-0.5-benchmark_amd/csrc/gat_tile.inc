@@ -198,7 +198,7 @@ __global__ __launch_bounds__(512, 4) void gat_tile_kernel(const GatTileArgs a) {
       m4 = fmaxf(m4, quad_perm<0x4E>(m4));
       const float mx = fmaxf(rm[j], m4);
       const float resc = rm[j] > -INFINITY ? __expf(rm[j] - mx) : 0.f;
-      const float pe = live ? __expf(z - mx) : 0.f;
+      const float pe = live && mx > -INFINITY ? __expf(z - mx) : 0.f;  // mx = -inf: only masked logits (-inf) so far
       float ps = pe + quad_perm<0xB1>(pe);
       ps += quad_perm<0x4E>(ps);
       const float pw = pe * keep;
@@ -355,11 +355,13 @@ __global__ __launch_bounds__(512, 4) void gat_tile_kernel(const GatTileArgs a) {
         }
       };
       const char* xb = reinterpret_cast<const char*>(a.gat) + (size_t)(cvalid ? col : 0) * 4u;
+      const char* zb = reinterpret_cast<const char*>(a.zero_row) + (size_t)(cvalid ? col : 0) * 4u;
       const char* sb = reinterpret_cast<const char*>(a.small);
       auto step = [&](int j, const v4i& id4) {  // an id: bits 0-23 the source, bits 24-30 its rank among parallel edges, -1 = padding
         v4f v[4], sm = (v4f)(0.f);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const v4f*>(xb + (id4[u] >= 0 ? (uint32_t)id4[u] & 0xFFFFFFu : 0u) * rowbytes);
+        for (int u = 0; u < 4; ++u)  // padding gathers the zero row: its weight is 0, and 0 x a NaN or inf of source 0 would be NaN
+          v[u] = *reinterpret_cast<const v4f*>(id4[u] >= 0 ? xb + ((uint32_t)id4[u] & 0xFFFFFFu) * rowbytes : zb);
         int mine = id4[0];  // this lane's entry
         mine = l == 1 ? id4[1] : mine;
         mine = l == 2 ? id4[2] : mine;

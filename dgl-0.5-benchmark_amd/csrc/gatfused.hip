@@ -303,7 +303,8 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
             m4 = fmaxf(m4, gat_dpp<0x4E>(m4));
             const float mn = fmaxf(run_m, m4);
             const float rescale = run_m > -INFINITY ? __expf(run_m - mn) : 0.f;
-            const float pe = live ? __expf(z - mn) : 0.f;
+            // masked logits (el[u] = -inf) may open a stream: while the maximum is still -inf, z - mn is -inf - -inf, not a weight
+            const float pe = live && mn > -INFINITY ? __expf(z - mn) : 0.f;
             const float pw = pe * keep;
             v4f pa = val[0] * gat_dpp<0x00>(pw);
             pa = __builtin_elementwise_fma(val[1], (v4f)(gat_dpp<0x55>(pw)), pa);
@@ -360,7 +361,7 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
             const float z = t > 0.f ? t : t * a.slope;
             const float mn = live ? fmaxf(run_m, z) : run_m;
             const float rescale = run_m > -INFINITY ? __expf(run_m - mn) : 0.f;   // 1 while the maximum stands
-            const float pe = live ? __expf(z - mn) : 0.f;
+            const float pe = live && mn > -INFINITY ? __expf(z - mn) : 0.f;       // mn = -inf: only masked logits (-inf) so far
             run_s = run_s * rescale + pe;
             acc = acc * rescale + val[u] * (pe * keep);
             run_m = mn;

@@ -154,7 +154,11 @@ int32_t mgx_device_info(int32_t* num_cus, int32_t* lds_bytes_per_cu, char* arch_
  * op: ADD, MUL, COPY_LHS, COPY_RHS (callers rewrite SUB/DIV as ADD(-E)/MUL(1/E), as DGL does).
  * reduce: SUM, MEAN (sum / max(in_degree,1), the divide DGL performs after the kernel),
  *         MAX / MIN (empty rows give 0; arg_u/arg_e receive the winning source node / edge id,
- *         -1 for empty rows; first extremum in storage order wins).
+ *         -1 for empty rows).  MAX / MIN walk a row in CSR storage order with a strict compare (> / <) that starts
+ *         from the identity -inf / +inf: of several equal extrema the FIRST in storage order wins (for a CSR built
+ *         stably from COO, the smallest edge id; +0.0 and -0.0 are equal), and the backward routes the whole gradient
+ *         through that one arg.  A NaN term never wins.  A non-empty row whose terms never beat the identity -- all
+ *         NaN, all -inf under MAX, all +inf under MIN -- gives the identity with arg_u = arg_e = -1.
  * src_scale / dst_scale: optional per-node fp32 factors (NULL = 1); used for the fused backward
  * of `mean` and for symmetric-norm GCN layers.  Only with SUM/MEAN.
  * arg_u/arg_e: same index width as the graph, [num_rows*out_len], may be NULL.
