@@ -13,7 +13,8 @@
 // the row factor and the bounds are applied there.  WHICH 16 columns a tile holds is a labelling too: tile mt, index c stands for column
 // 64 (mt / 4) + 4 c + mt % 4, so a lane ends up with four CONSECUTIVE columns of a row in four accumulators and writes them as one float4
 // -- 256 contiguous bytes per row and store instruction (tile-major columns gave 64-byte pieces: 2.0 TB/s of writes).  K % 4 != 0 or an unaligned A (the 47-column output gradient) takes the DWORD
-// form: lane (c, q) loads A[row0 + c][4 s + q], B staged to match.  No atomics, fixed summation order.
+// form: lane (c, q) holds A[row0 + c][4 s + q] (loaded so, or -- contiguous aligned A -- through the staged span below), B staged to match.
+// No atomics, fixed summation order.
 #include "common.h"
 #include "slots.h"
 
@@ -39,15 +40,30 @@ struct RowsGemmAct {
   unsigned long long* overflow;  // optional: += rows with more than 24 non-zeros
 };
 
+// waves per SIMD the register allocator is held to: two workgroups per CU (128 VGPRs), except the 128-column activation forms that
+// would spill there (none of them is a layer of the products model); those keep one workgroup
+constexpr int rows_gemm_waves(int ks, int mt, bool v4, bool act) { return (act && mt == 8 && (!v4 || ks >= 32)) ? 2 : 4; }
+
 // KS = k-steps of 4 (K_pad / 4; a multiple of 4 in the float4 form), MT = column tiles of 16 (a multiple of 4: groups of 64 columns)
+//
+// The operand tile lives in ONE set of KS registers that rolls: the registers of k-chunk jj (float4 form; step s in the dword form) are
+// free once the MFMAs that consume them have issued and are refilled with the same chunk of the wave's NEXT tile, so a whole tile is
+// in flight without a second register tile.  (hipcc gathers the refill loads behind the tile's last MFMAs; holding each one behind
+// its own chunk with scheduling barriers measured slower.)  With that, the bias in LDS and the waves-per-SIMD hint every form of the
+// products epoch fits 128 VGPRs without spills: TWO workgroups per CU, one group's loads and stores travel under the other's MFMAs
+// (docs/LOG_rows_gemm_ring.md).
+// stage_a (dword form, A contiguous -- lda == K -- and 16-byte aligned): the 16 rows of a full tile are one aligned span of 64 K bytes;
+// it is fetched with lane-linear 16-byte loads (3 per lane at K = 47 instead of 12 dword loads of 16 bytes per row), passed through a
+// per-wave LDS area and read back as a[s] = A[row0 + c][4 s + q].  Same k <-> B pairing, same bits.
 template <int KS, int MT, bool V4, bool ACT>
-__global__ __launch_bounds__(kRgBlock) void rows_gemm_kernel(int64_t n, int K, int M, const float* __restrict__ A, int64_t lda,
-                                                           const float* __restrict__ B, int64_t ldb, int b_transposed,
-                                                           const float* __restrict__ bias, const float* __restrict__ row_scale,
-                                                           int scale_from, float* __restrict__ C, int64_t ldc, RowsGemmAct act,
-                                                           float* __restrict__ C2, int64_t ldc2, int split_col) {
+__global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void rows_gemm_kernel(
+    int64_t n, int K, int M, const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, int b_transposed,
+    const float* __restrict__ bias, const float* __restrict__ row_scale, int scale_from, float* __restrict__ C, int64_t ldc, RowsGemmAct act,
+    float* __restrict__ C2, int64_t ldc2, int split_col, int stage_a) {
   __shared__ float Bl[KS * MT * 64];
   __shared__ uint32_t slot_stage[ACT ? kRgWaves * 4 * 32 : 1];
+  __shared__ float bias_l[MT * 16];
+  __shared__ float a_stage[V4 ? 4 : kRgWaves * ((KS + 3) / 4) * 256];  // dword form: a tile's span, 64 lanes x (KS + 3) / 4 float4 per wave
   unsigned long long over_rows = 0;
   const int lane = threadIdx.x & (kWave - 1);
   const int c = lane % 16, q = lane / 16;
@@ -70,10 +86,9 @@ __global__ __launch_bounds__(kRgBlock) void rows_gemm_kernel(int64_t n, int K, i
     if (k < K && m < M) v = b_transposed ? B[(int64_t)m * ldb + k] : B[(int64_t)k * ldb + m];
     Bl[idx] = v;
   }
+  // the bias by column (zero beyond M): the epilogue reads a lane's four consecutive columns back -- MT registers less than holding them
+  for (int m = threadIdx.x; m < MT * 16; m += kRgBlock) bias_l[m] = (bias && m < M) ? bias[m] : 0.f;
   __syncthreads();
-  float bv[MT];
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) bv[mt] = (bias && rows_gemm_col(mt, c) < M) ? bias[rows_gemm_col(mt, c)] : 0.f;
   // float4 stores; columns from split_col on (a multiple of 4) go to a matrix of their own (C2): the two halves of d[h | neigh] are
   // then separate compact matrices -- the reversed aggregation gathers from one and accumulates into the other (rows that share
   // 512-byte blocks with the rows being gathered cost it 2.60 against 2.38 ms)
@@ -81,74 +96,42 @@ __global__ __launch_bounds__(kRgBlock) void rows_gemm_kernel(int64_t n, int K, i
 
   const int64_t gw = (int64_t)blockIdx.x * kRgWaves + threadIdx.x / kWave;
   const int64_t stride = (int64_t)gridDim.x * kRgWaves * 16;
-  // operand fragment of one 16-row tile: a[s] pairs with step s of the stage (float4 form: a[4 jj + t] = component t of chunk jj)
-  auto load_a = [&](int64_t r0, float (&a)[KS]) {
-    const int64_t arow = r0 + c;
-    const bool aok = arow < n;
+  // operand fragment of one 16-row tile: a[s] pairs with step s of the stage (float4 form: a[4 jj + t] = component t of chunk jj).
+  // A lane whose row is beyond n reads row n - 1 instead: row i of A only reaches row i of C, which is not stored.  The host picked
+  // KS = ceil(K / 16) * 4 (ceil(K / 4)), so only the LAST chunk (step) can reach beyond K.
+  float a[KS];
+  auto row_of = [&](int64_t r) { return A + (r + c < n ? r + c : n - 1) * lda; };
+  auto load_chunk = [&](const float* ap, int jj) {  // float4 form
+    const int k0 = 16 * jj + 4 * q;
+    const v4f v = (jj < KS / 4 - 1 || k0 < K) ? *reinterpret_cast<const v4f*>(ap + k0) : (v4f)(0.f);
+    a[4 * jj + 0] = v.x; a[4 * jj + 1] = v.y; a[4 * jj + 2] = v.z; a[4 * jj + 3] = v.w;
+  };
+  auto load_step = [&](const float* ap, int s) { a[s] = (s < KS - 1 || 4 * s + q < K) ? ap[4 * s + q] : 0.f; };  // dword form
+  auto load_a = [&](int64_t r) {
+    const float* ap = row_of(r);
     if (V4) {
 #pragma unroll
-      for (int jj = 0; jj < KS / 4; ++jj) {
-        const int k0 = 16 * jj + 4 * q;
-        const v4f v = (aok && k0 < K) ? *reinterpret_cast<const v4f*>(A + arow * lda + k0) : (v4f)(0.f);
-        a[4 * jj + 0] = v.x; a[4 * jj + 1] = v.y; a[4 * jj + 2] = v.z; a[4 * jj + 3] = v.w;
-      }
+      for (int jj = 0; jj < KS / 4; ++jj) load_chunk(ap, jj);
     } else {
 #pragma unroll
-      for (int s = 0; s < KS; ++s) a[s] = (aok && 4 * s + q < K) ? A[arow * lda + 4 * s + q] : 0.f;
+      for (int s = 0; s < KS; ++s) load_step(ap, s);
     }
   };
-  float a[KS], an[KS];
-  int64_t r0 = gw * 16;
-  if (r0 < n) load_a(r0, a);
-  for (; r0 < n; r0 += stride) {
-    if (r0 + stride < n) load_a(r0 + stride, an);  // the next tile's rows travel under this tile's MFMAs and stores
-    v4f acc[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt] = (v4f)(0.f);
-    // B stays in LDS: an address the compiler cannot prove loop-invariant keeps it from hoisting the KS x MT fragments into registers
-    // (199 - 276 VGPRs, two waves per SIMD or spills, against ~60 with one ds_read per MFMA group)
-    int lo = lane;
-    asm volatile("" : "+v"(lo));
-    if (V4) {
-#pragma unroll
-      for (int jj = 0; jj < KS / 4; ++jj) {
-        v4f b[MT];  // the MT column tiles of this k-chunk first, then MT INDEPENDENT accumulators between two uses of the same one
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) b[mt] = *reinterpret_cast<const v4f*>(&Bl[((jj * MT + mt) * 64 + lo) * 4]);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * jj + 0], b[mt].x, acc[mt], 0, 0, 0);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * jj + 1], b[mt].y, acc[mt], 0, 0, 0);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * jj + 2], b[mt].z, acc[mt], 0, 0, 0);
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * jj + 3], b[mt].w, acc[mt], 0, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], Bl[(s * MT + mt) * 64 + lo], acc[mt], 0, 0, 0);
-    }
-#pragma unroll
-    for (int s = 0; s < KS; ++s) a[s] = an[s];
-    // ---- epilogue: accumulator element r of tile mt = C[r0 + 4 q + r][rows_gemm_col(mt, c)]; the four tiles of a group = four consecutive columns
-    float rs[4] = {1.f, 1.f, 1.f, 1.f};
-    if (row_scale) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) rs[r] = (r0 + 4 * q + r < n) ? row_scale[r0 + 4 * q + r] : 1.f;
-    }
+
+  // ---- epilogue: accumulator element r of tile mt = C[r0 + 4 q + r][rows_gemm_col(mt, c)]; the four tiles of a group = four consecutive columns
+  auto epilogue = [&](int64_t r0, const v4f (&acc)[MT], const float (&rs)[4]) {
 #pragma unroll
     for (int g = 0; g < MT / 4; ++g) {
       const int m0 = 64 * g + 4 * c;
+      const v4f bv = *reinterpret_cast<const v4f*>(&bias_l[m0]);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int64_t row = r0 + 4 * q + r;
         float v[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          v[t] = acc[4 * g + t][r] + bv[4 * g + t];
-          if (row_scale && m0 + t >= scale_from) v[t] *= rs[r];
+          v[t] = acc[4 * g + t][r] + bv[t];
+          if (!ACT && row_scale && m0 + t >= scale_from) v[t] *= rs[r];
         }
         if (ACT) {  // (the host checked: float4 stores possible, M % 4 == 0)
           v4f kept = (v4f)(0.f);
@@ -184,31 +167,130 @@ __global__ __launch_bounds__(kRgBlock) void rows_gemm_kernel(int64_t n, int K, i
         }
       }
     }
+  };
+
+  // ---- one tile: the MFMAs of the rows in a[], in a fixed order; `more`: each chunk of a[] is refilled from the tile at r0 + stride
+  // right after its last use (a compile-time flag: a load under a run-time condition would cost a branch and a full wait per chunk)
+  auto tile = [&](int64_t r0, auto more, auto&& prefetch) {
+    const float* an = more ? row_of(r0 + stride) : nullptr;
+    // the row factors BEFORE the refill loads are issued: loads return in order, so a load issued after them in the epilogue would
+    // have to wait for the whole next tile (the activation forms have no row factor)
+    float rs[4] = {1.f, 1.f, 1.f, 1.f};
+    if (!ACT && row_scale) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rs[r] = (r0 + 4 * q + r < n) ? row_scale[r0 + 4 * q + r] : 1.f;
+    }
+    prefetch();
+    v4f acc[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) acc[mt] = (v4f)(0.f);
+    // B stays in LDS: an address the compiler cannot prove loop-invariant keeps it from hoisting the KS x MT fragments into registers
+    // (199 - 276 VGPRs, two waves per SIMD or spills, against ~60 with one ds_read per MFMA group)
+    int lo = lane;
+    asm volatile("" : "+v"(lo));
+    if (V4) {
+#pragma unroll
+      for (int jj = 0; jj < KS / 4; ++jj) {
+        v4f b[MT];  // the MT column tiles of this k-chunk first, then MT INDEPENDENT accumulators between two uses of the same one
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) b[mt] = *reinterpret_cast<const v4f*>(&Bl[((jj * MT + mt) * 64 + lo) * 4]);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * jj + 0], b[mt].x, acc[mt], 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * jj + 1], b[mt].y, acc[mt], 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * jj + 2], b[mt].z, acc[mt], 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[4 * jj + 3], b[mt].w, acc[mt], 0, 0, 0);
+        if (more) load_chunk(an, jj);
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s], Bl[(s * MT + mt) * 64 + lo], acc[mt], 0, 0, 0);
+        if (more) load_step(an, s);
+      }
+    }
+    epilogue(r0, acc, rs);
+  };
+  struct Yes { constexpr operator bool() const { return true; } };
+  struct No { constexpr operator bool() const { return false; } };
+
+  int64_t r0 = gw * 16;
+  if (!V4 && stage_a) {  // wave-uniform: the wave's FULL tiles; a ragged last tile of the matrix falls through to the row loads below
+    constexpr int NV = (KS + 3) / 4;  // 16-byte pieces per lane: 4 K of them per tile (a lane beyond them repeats the last one)
+    float* st = a_stage + (threadIdx.x / kWave) * (NV * 256);
+    v4f sv[NV];
+    auto load_span = [&](int64_t r) {
+      const v4f* sp = reinterpret_cast<const v4f*>(A + r * K);
+#pragma unroll
+      for (int i = 0; i < NV; ++i) sv[i] = sp[64 * i + lane < 4 * K ? 64 * i + lane : 4 * K - 1];
+    };
+    if (r0 + 16 <= n) load_span(r0);
+    for (; r0 + 16 <= n; r0 += stride) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) reinterpret_cast<v4f*>(st)[64 * i + lane] = sv[i];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int s = 0; s < KS; ++s) a[s] = (s < KS - 1 || 4 * s + q < K) ? st[c * K + 4 * s + q] : 0.f;
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      // the next full tile's span travels under this tile's MFMAs and stores (none left: this one again, no branch around the loads)
+      const int64_t rn = r0 + stride + 16 <= n ? r0 + stride : r0;
+      tile(r0, No{}, [&] { load_span(rn); });
+    }
+  }
+  if (r0 < n) {
+    load_a(r0);
+    for (; r0 + stride < n; r0 += stride) tile(r0, Yes{}, [] {});
+    tile(r0, No{}, [] {});
   }
   if (ACT && act.overflow && lane == 0 && over_rows) atomicAdd(act.overflow, over_rows);
+}
+
+// workgroups of this instantiation that are resident at once on the current device (asked once)
+template <int KS, int MT, bool V4, bool ACT>
+static int64_t rows_gemm_resident_groups() {
+  static const int64_t groups = [] {
+    int per_cu = 0, dev = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rows_gemm_kernel<KS, MT, V4, ACT>, kRgBlock, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+    (void)hipGetLastError();
+    return (int64_t)per_cu * cus;
+  }();
+  return groups;
+}
+
+// rows that one sweep of the grid covers for a long matrix: every resident workgroup, 16 rows per wave -- one round of groups, none
+// waiting for a CU and no partial last round (a wave strides over its tiles; B is staged once per group)
+template <int KS, int MT, bool V4>
+static int64_t rows_gemm_sweep(bool act) {
+  return (act ? rows_gemm_resident_groups<KS, MT, V4, true>() : rows_gemm_resident_groups<KS, MT, V4, false>()) * kRgWaves * 16;
 }
 
 template <int KS, int MT, bool V4>
 static void launch_rows_gemm(int64_t n, int K, int M, const float* A, int64_t lda, const float* B, int64_t ldb, int bt, const float* bias,
                              const float* rs, int scale_from, float* C, int64_t ldc, const RowsGemmAct* act, float* C2, int64_t ldc2,
                              int split_col, hipStream_t s) {
-  // waves: one per 16 rows up to 6 per SIMD of the chip (the stage of B is paid once per workgroup)
   int64_t blocks = (n + 16 * kRgWaves - 1) / (16 * kRgWaves);
-  const int64_t cap = 256 * 3;
+  const int64_t cap = rows_gemm_sweep<KS, MT, V4>(act != nullptr) / (16 * kRgWaves);
   if (blocks > cap) blocks = cap;
+  const int stage_a = !V4 && lda == K && (uintptr_t)A % 16 == 0;
   if (act) {
     hipLaunchKernelGGL((rows_gemm_kernel<KS, MT, V4, true>), dim3((unsigned)blocks), dim3(kRgBlock), 0, s, n, K, M, A, lda, B, ldb, bt, bias,
-                       rs, scale_from, C, ldc, *act, C2, ldc2, split_col);
+                       rs, scale_from, C, ldc, *act, C2, ldc2, split_col, stage_a);
   } else {
     hipLaunchKernelGGL((rows_gemm_kernel<KS, MT, V4, false>), dim3((unsigned)blocks), dim3(kRgBlock), 0, s, n, K, M, A, lda, B, ldb, bt, bias,
-                       rs, scale_from, C, ldc, RowsGemmAct{}, C2, ldc2, split_col);
+                       rs, scale_from, C, ldc, RowsGemmAct{}, C2, ldc2, split_col, stage_a);
   }
 }
 
 // shape -> kernel; false when none is built for it
 static bool rows_gemm_dispatch(bool dry, int64_t n, int64_t K, int64_t M, const float* a, int64_t lda, const float* b, int64_t ldb, int bt,
                                const float* bias, const float* rs, int64_t scale_from, float* c, int64_t ldc, const RowsGemmAct* act,
-                               hipStream_t s, float* c2 = nullptr, int64_t ldc2 = 0, int64_t split_col = 0) {
+                               hipStream_t s, float* c2 = nullptr, int64_t ldc2 = 0, int64_t split_col = 0, int64_t* sweep_rows = nullptr) {
   const bool v4 = K % 4 == 0 && lda % 4 == 0 && (dry || (uintptr_t)a % 16 == 0);
   const int mt = (int)((M + 63) / 64) * 4;  // column tiles in groups of four (64 columns)
   const int ks = v4 ? (int)((K + 15) / 16) * 4 : (int)((K + 3) / 4);
@@ -218,6 +300,7 @@ static bool rows_gemm_dispatch(bool dry, int64_t n, int64_t K, int64_t M, const 
   if (!ok && ks == KS_ && mt == MT_ && v4 == V4_) {                                                                                       \
     if (!dry) launch_rows_gemm<KS_, MT_, V4_>(n, (int)K, (int)M, a, lda, b, ldb, bt, bias, rs, (int)scale_from, c, ldc, act, c2, ldc2,     \
                                               (int)split_col, s);                                                                         \
+    if (sweep_rows) *sweep_rows = rows_gemm_sweep<KS_, MT_, V4_>(act != nullptr);                                                         \
     ok = true;                                                                                                                            \
   }
   // float4 form: K = 32 .. 208, M <= 64 / 128 -- the SAGE layers of the products model and of 64-wide models
@@ -252,6 +335,15 @@ extern "C" int32_t mgx_rows_gemm(int64_t n, int64_t K, int64_t M, const float* a
 
 extern "C" int32_t mgx_rows_gemm_supported(int64_t K, int64_t M, int64_t lda) {
   return mgx::rows_gemm_dispatch(true, 0, K, M, nullptr, lda, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr) ? 1 : 0;
+}
+
+extern "C" int64_t mgx_rows_gemm_sweep_rows(int64_t K, int64_t M, int64_t lda, int32_t relu_dropout) {
+  mgx::RowsGemmAct act{};
+  int64_t rows = 0;
+  MGX_ENTER();
+  mgx::rows_gemm_dispatch(true, 0, K, M, nullptr, lda, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0, relu_dropout ? &act : nullptr, nullptr,
+                          nullptr, 0, 0, &rows);
+  return rows;
 }
 
 extern "C" int32_t mgx_rows_gemm_relu_dropout(int64_t n, int64_t K, int64_t M, const float* a, int64_t lda, const float* b, int64_t ldb,

@@ -1093,6 +1093,10 @@ class HipBackend(object):
     def rows_gemm_supported(self, K, M, lda):
         return bool(_lib.lib().mgx_rows_gemm_supported(int(K), int(M), int(lda)))
 
+    def rows_gemm_sweep_rows(self, K, M, lda, relu_dropout=False):
+        """Rows one sweep of the rows_gemm grid covers on this device (0: no kernel for the shape)."""
+        return int(_lib.lib().mgx_rows_gemm_sweep_rows(int(K), int(M), int(lda), 1 if relu_dropout else 0))
+
     def rows_gemm_relu_dropout(self, a2d, b2d, b_transposed, bias, p, seed, offset, out=None, slots=None, overflow=None):
         """dropout(relu(a2d x B + bias), p) written into `out` (a row-strided [n, M] view, or a new matrix) + the mask of
         relu_dropout_fwd -- bit for bit what rows_gemm followed by relu_dropout_fwd(seed, offset) gives, without storing the product.

@@ -483,6 +483,10 @@ int32_t mgx_rows_gemm(int64_t n, int64_t K, int64_t M, const float* a, int64_t l
                       int64_t ldc2, int64_t split_col /* a multiple of 4 */, void* stream);
 /* 1 when mgx_rows_gemm has a kernel for these sizes (lda: A's row stride in floats), else 0. */
 int32_t mgx_rows_gemm_supported(int64_t K, int64_t M, int64_t lda);
+/* Rows that one sweep of mgx_rows_gemm's grid covers on the current device for these sizes (relu_dropout != 0: of
+ * mgx_rows_gemm_relu_dropout's): every workgroup that is resident at once, 16 rows per wave.  A wave of a longer matrix walks its
+ * tiles this far apart.  0 when there is no kernel. */
+int64_t mgx_rows_gemm_sweep_rows(int64_t K, int64_t M, int64_t lda, int32_t relu_dropout);
 /* The same product followed by relu and inverted dropout (main_dgl_product_sage.py:93-95) in the epilogue: y[r, :] (row stride ldy) and the
  * 4 mask bits per float4 exactly as mgx_relu_dropout_fwd_strided(p, seed, offset) would produce them from the stored product -- which is
  * never written.  M % 4 == 0, y 16-byte aligned, ldy % 4 == 0; mask: [n * M / 4] bytes.
