@@ -32,7 +32,7 @@ import torch.nn.functional as F  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dgl  # noqa: E402
 import dgl.function as fn  # noqa: E402
-from dgl.nn.pytorch import GATConv, Linear, BatchNorm1d, RelGraphConv  # noqa: E402
+from dgl.nn.pytorch import GATConv, DotGatConv, Linear, BatchNorm1d, RelGraphConv  # noqa: E402
 from mi355x_graph import config, ops  # noqa: E402
 from dgl.utils import expand_as_pair  # noqa: E402
 
@@ -190,6 +190,28 @@ class GAT(nn.Module):
         return self.gat_layers[-1](self.g, h).mean(1)
 
 
+class DotGAT(nn.Module):
+    """The GAT stack above over dgl.nn DotGatConv layers (scaled dot-product attention): same heads, hidden size and feat_drop; the layer
+    has no activation, feat_drop or attn_drop of its own, so the activation and the input dropout are applied here."""
+
+    def __init__(self, g, num_layers, in_feats, num_hidden, num_classes, heads, activation=F.elu, feat_drop=0.0):
+        super(DotGAT, self).__init__()
+        self.num_layers, self.g, self.activation = num_layers, g, activation
+        self.feat_drop = nn.Dropout(feat_drop)
+        widths = [in_feats] + [num_hidden * heads[l] for l in range(num_layers - 1)]
+        self.gat_layers = nn.ModuleList()
+        for l in range(num_layers - 1):
+            self.gat_layers.append(DotGatConv(widths[l], num_hidden, heads[l]))
+        self.gat_layers.append(DotGatConv(widths[-1], num_classes, heads[-1]))
+
+    def forward(self, h):
+        for l in range(self.num_layers - 1):
+            if l > 0:
+                h = self.feat_drop(h)
+            h = self.activation(self.gat_layers[l](self.g, h)).flatten(1)
+        return self.gat_layers[-1](self.g, self.feat_drop(h)).mean(1)
+
+
 def sage_train_step(model, g, feats, labels, train_idx, optimizer):
     """main_dgl_product_sage.py:101-110."""
     model.train()
@@ -313,8 +335,8 @@ def spmm_edges_per_epoch(num_layers, num_edges):
 
 def main():
     p = argparse.ArgumentParser("full-graph training on the MI355X message-passing backend")
-    p.add_argument("--model", default="sage", choices=["sage", "gat", "rgcn"],
-                   help="rgcn: the edge-weighted relational model on the proteins stand-in (--dataset is not read)")
+    p.add_argument("--model", default="sage", choices=["sage", "gat", "dotgat", "rgcn"],
+                   help="dotgat: the GAT stack with DotGatConv layers (dropout = feat_drop only); rgcn: the edge-weighted relational model on the proteins stand-in (--dataset is not read)")
     p.add_argument("--dataset", default="products")
     p.add_argument("--epochs", type=int, default=10)
     p.add_argument("--scale", type=float, default=1.0)
@@ -370,9 +392,14 @@ def main():
             if val is not None:
                 gcfg[key] = val
         heads = [gcfg["heads"]] * (gcfg["num_layers"] - 1) + [gcfg["out_heads"]]
-        print("GAT: %d layers, heads %s, hidden %d, feat_drop = attn_drop = %g" % (gcfg["num_layers"], heads, gcfg["hidden"], gcfg["dropout"]))
-        model = GAT(g, gcfg["num_layers"], data.features.shape[1], gcfg["hidden"], data.num_classes, heads,
-                    feat_drop=gcfg["dropout"], attn_drop=gcfg["dropout"]).to(device)
+        if args.model == "dotgat":
+            print("DotGAT: %d layers, heads %s, hidden %d, feat_drop = %g" % (gcfg["num_layers"], heads, gcfg["hidden"], gcfg["dropout"]))
+            model = DotGAT(g, gcfg["num_layers"], data.features.shape[1], gcfg["hidden"], data.num_classes, heads,
+                           feat_drop=gcfg["dropout"]).to(device)
+        else:
+            print("GAT: %d layers, heads %s, hidden %d, feat_drop = attn_drop = %g" % (gcfg["num_layers"], heads, gcfg["hidden"], gcfg["dropout"]))
+            model = GAT(g, gcfg["num_layers"], data.features.shape[1], gcfg["hidden"], data.num_classes, heads,
+                        feat_drop=gcfg["dropout"], attn_drop=gcfg["dropout"]).to(device)
         opt = torch.optim.Adam(model.parameters(), lr=0.003, weight_decay=2.4e-5)
         loss_fcn = nn.CrossEntropyLoss()
         if args.hipgraph:

@@ -81,6 +81,11 @@ SIGNATURES = {
                                 _vp, _vp, _vp]),
     "mgx_gat_tile_bwd": (_i32, [_csr_p, _vp, _vp, _csr_p, _vp, _vp, _i64, _i64, _fp, _fp, ctypes.c_float, ctypes.c_float, ctypes.c_uint64,
                                 _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp, _vp]),
+    "mgx_dot_attention_supported": (_i32, [_csr_p, _i64, _i64]),
+    "mgx_dot_attention_workspace": (_i64, [_vp, _i64, _i64]),
+    "mgx_dot_attention_fwd": (_i32, [_csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, ctypes.c_float, _fp, _fp, _vp, _vp]),
+    "mgx_dot_attention_bwd": (_i32, [_csr_p, _vp, _csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, ctypes.c_float, _fp, _fp, _fp,
+                                     _fp, _fp, _fp, _vp, _vp]),
     "mgx_head_dot_fwd": (_i32, [_i64, _i64, _i64, _fp, _fp, _fp, _fp, _fp, _vp]),
     "mgx_head_dot_bwd_workspace": (_i64, [_i64, _i64]),
     "mgx_head_dot_bwd": (_i32, [_i64, _i64, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),

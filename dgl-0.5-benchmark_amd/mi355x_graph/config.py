@@ -27,6 +27,9 @@ XTY_COLSUM = True          # ... with the bias gradient from the same pass (mgx_
 GAT_AGG_FIRST = True       # aggregate before projecting when in_feats < heads * out_feats
 GAT_PACK = True            # one packed gather operand per node for the fused walks (mgx_gat_fused_pack_workspace); False: separate arrays
 
+# ---- dot-product attention (ops.dot_attention, nn.DotGatConv)
+DOT_ATTENTION_FUSED = True  # the fused walks of csrc/dotattn.hip; False: u_dot_v -> edge_softmax -> u_mul_e/sum through the existing operators
+
 # ---- schedules (schedule.py, tileplan.py)
 PLAN_BUILDER = "device"    # "device" (mgx_spmm_plan_count / _fill) | "torch" | "host": the same tables three ways (tests compare them)
 HUB_SPLIT = 256            # rows longer than this become several work items (256 measured best on MI355X; 1024: +5..10 %)

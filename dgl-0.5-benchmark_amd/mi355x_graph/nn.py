@@ -1,5 +1,6 @@
 """dgl.nn.pytorch modules used by the benchmark scripts, written against this backend's ops:
   GATConv    main_dgl_reddit_gat.py:10,31-55 (u_add_v SDDMM + fused edge_softmax + u_mul_e/sum SpMM)
+  DotGatConv dgl.nn.pytorch.DotGatConv (u_dot_v SDDMM + edge_softmax + u_mul_e/sum SpMM, fused: ops.dot_attention)
   SAGEConv   main_dgl_arxiv_sage_nn.py:9,27-34
   GraphConv  main_dgl_enzymes_gcn_nn.py:12,29-36
   AvgPooling / SumPooling / MaxPooling   main_dgl_molhiv_gcn.py:75,93
@@ -230,6 +231,47 @@ class GATConv(nn.Module):
                     a = a_user
                 return rst, a
             return rst
+
+
+class DotGatConv(nn.Module):
+    """dgl.nn.pytorch.DotGatConv: scaled dot-product attention over the in-edges, h'_v = sum_{u->v} softmax_u(<W h_v, W h_u> / sqrt(F)) W h_u
+    per head, with ONE bias-free projection `fc` for both roles.  The block between the projection and the result is
+    ops.dot_attention (csrc/dotattn.hip when it takes the shape); get_attention=True runs the operators one by one and also returns
+    the attention [E, H, 1] in edge-id order."""
+
+    def __init__(self, in_feats, out_feats, num_heads, allow_zero_in_degree=False):
+        super(DotGatConv, self).__init__()
+        self._in_src_feats, self._in_dst_feats = expand_as_pair(in_feats)
+        self._out_feats = out_feats
+        self._num_heads = num_heads
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.fc = Linear(self._in_src_feats, out_feats * num_heads, bias=False)  # a pair of inputs shares it, as in DGL
+
+    def set_allow_zero_in_degree(self, set_value):
+        self._allow_zero_in_degree = set_value
+
+    def forward(self, graph, feat, get_attention=False):
+        with graph.local_scope():
+            if not self._allow_zero_in_degree:
+                if _has_zero_in_degree(graph):
+                    raise DGLError(
+                        "There are 0-in-degree nodes in the graph, output for those nodes will be invalid. "
+                        "This is harmful for some applications, causing silent performance regression. "
+                        "Adding self-loop on the input graph by calling `g = dgl.add_self_loop(g)` will resolve "
+                        "the issue. Setting ``allow_zero_in_degree`` to be `True` when constructing this module "
+                        "will suppress the check and let the code run.")
+            if isinstance(feat, tuple):
+                feat_src = self.fc(feat[0]).view(-1, self._num_heads, self._out_feats)
+                feat_dst = self.fc(feat[1]).view(-1, self._num_heads, self._out_feats)
+            else:
+                feat_src = feat_dst = self.fc(feat).view(-1, self._num_heads, self._out_feats)
+                if graph.is_block:
+                    feat_dst = feat_src[:graph.number_of_dst_nodes()]
+            scale = float(self._out_feats) ** -0.5
+            if not get_attention:  # q, k and v are one tensor here: k and v are gathered once, autograd sums the three gradients
+                return ops.dot_attention(graph, feat_dst, feat_src, feat_src, scale)
+            a = ops.edge_softmax(graph, ops.gsddmm(graph, "dot", feat_src, feat_dst, "u", "v") * scale)
+            return ops.gspmm(graph, "mul", "sum", feat_src, a), a
 
 
 class SAGEConv(nn.Module):

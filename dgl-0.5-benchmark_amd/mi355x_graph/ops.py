@@ -19,7 +19,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "segment_reduce", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "segment_reduce", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -408,6 +408,72 @@ def gat_fused(graph, feat, el, er, negative_slope=0.2, attn_drop=0.0, training=T
         raise DGLError("gat_fused: attn_drop > 0 under HIP-graph capture would replay ONE dropout mask (the seed is a launch "
                        "argument); use the unfused operators there, as GATConv does")
     return GATFused.apply(_gidx(graph), feat, el, er, negative_slope, p, attn_l)
+
+
+class DotAttention(torch.autograd.Function):
+    """out[v,h,:] = sum_e softmax_{e->v}(scale <q[v,h,:], k[u,h,:]>)[e,h] v[u,h,:] -- dgl.nn.DotGatConv's whole message-passing block
+    in one walk forward and two backward, with no E-sized tensor: the attention of an edge is rebuilt from the per-row statistics
+    where it is needed (csrc/dotattn.hip)."""
+
+    @staticmethod
+    def forward(ctx, gidx, q, k, v, scale):
+        # k and v that are one tensor -- or two views of the same memory -- are gathered once
+        same = k is v or (k.data_ptr() == v.data_ptr() and k.stride() == v.stride())
+        out, stat = sparse.backend_for(q).dot_attention_fwd(gidx.csc(), q, k, k if same else v, float(scale))
+        ctx.backward_cache = gidx, float(scale), same
+        ctx.save_for_backward(q, k, v, out, stat)
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        gidx, scale, same = ctx.backward_cache
+        q, k, v, out, stat = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dq, dk, dv = sparse.backend_for(q).dot_attention_bwd(gidx.csc(), gidx.csr(), q, k, k if same else v, scale, out,
+                                                             d_out.contiguous(), stat, need[1], need[2], need[3])
+        return None, dq, dk, dv, None
+
+
+def _dot_attention_args(graph, q, k, v):
+    gidx = _gidx(graph)
+    if not all(torch.is_tensor(t) and t.dim() == 3 for t in (q, k, v)):
+        raise DGLError("dot_attention: expected q [N_dst, H, F] and k, v [N_src, H, F], got %s"
+                       % (", ".join(str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__ for t in (q, k, v)),))
+    if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
+        raise DGLError("dot_attention expects float32 inputs, got %s / %s / %s" % (q.dtype, k.dtype, v.dtype))
+    if (q.shape[0] != gidx.num_dst or k.shape[0] != gidx.num_src or v.shape[0] != gidx.num_src or q.shape[1:] != k.shape[1:]
+            or k.shape[1:] != v.shape[1:]):
+        raise DGLError("dot_attention: expected q [%d, H, F] and k, v [%d, H, F], got q %s, k %s, v %s"
+                       % (gidx.num_dst, gidx.num_src, tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    return gidx
+
+
+def dot_attention_fused(graph, q, k, v):
+    """True when dot_attention(graph, q, k, v) runs the fused kernels (else it is u_dot_v -> edge_softmax -> u_mul_e/sum)."""
+    gidx = _gidx(graph)
+    if (not all(torch.is_tensor(t) and t.dim() == 3 and t.is_cuda and t.dtype == torch.float32 and t.device == q.device for t in (q, k, v))
+            or not config.DOT_ATTENTION_FUSED or _torch_ops() is not None or q.device.type not in sparse._BACKENDS):
+        return False
+    be = sparse.backend_for(q)
+    if (not hasattr(be, "dot_attention_fwd") or q.shape[0] != gidx.num_dst or k.shape[0] != gidx.num_src or k.shape != v.shape
+            or q.shape[1:] != k.shape[1:] or gidx.num_edges() == 0):
+        return False
+    return be.dot_attention_supported(gidx.csc(), int(q.shape[1]), int(q.shape[2]))
+
+
+def dot_attention(graph, q, k, v, scale=None):
+    """Scaled dot-product attention over a graph: out[v,h,:] = sum_{e: u->v} a[e,h] v[u,h,:] with a = edge_softmax(scale * u_dot_v(k, q)).
+
+    q: [N_dst, H, F], k, v: [N_src, H, F] (fp32; row-strided views such as column blocks of one projection are taken without a copy),
+    scale: default F ** -0.5; result [N_dst, H, F], exactly 0 for destinations without in-edges.  Device operands with F in {4, 8, 16, 32,
+    64} and H*F <= 256 on an int32 graph run csrc/dotattn.hip (dot_attention_fused); everything else takes
+    gspmm(g, "mul", "sum", v, edge_softmax(g, gsddmm(g, "dot", k, q, "u", "v") * scale)) -- the same values through the existing operators."""
+    gidx = _dot_attention_args(graph, q, k, v)
+    scale = float(q.shape[2]) ** -0.5 if scale is None else float(scale)
+    if not dot_attention_fused(graph, q, k, v):
+        return gspmm(gidx, "mul", "sum", v, edge_softmax(gidx, gsddmm(gidx, "dot", k, q, "u", "v") * scale))
+    return DotAttention.apply(gidx, q, k, v, scale)
 
 
 class HeadDot(torch.autograd.Function):

@@ -869,6 +869,68 @@ class HipBackend(object):
                                                     _ptr(d_feat), _ptr(d_el), _ptr(d_er), _ptr(ws), _ptr(pack), _stream(dev)))
         return d_feat, d_el, d_er
 
+    # ---- scaled dot-product attention (csrc/dotattn.hip)
+    @staticmethod
+    def dot_attention_supported(csr, H, F):
+        """Shapes mgx_dot_attention_* takes: F in {4, 8, 16, 32, 64}, H*F <= 256, 32-bit indices, at least one edge, dense operands below
+        4 GiB (32-bit byte offsets)."""
+        return bool(_lib.lib().mgx_dot_attention_supported(ctypes.byref(csr.c_struct()), H, F))
+
+    @staticmethod
+    def _dot_operand(x3d):
+        """(tensor, row stride in floats) of a [N, H, F] operand as the kernels take it: the H*F floats of a node contiguous, the row
+        stride a multiple of 4 floats, the base 16-byte aligned, rows * stride below 4 GiB (a column block of a wider projection qualifies);
+        else a dense copy."""
+        H, F = int(x3d.shape[1]), int(x3d.shape[2])
+        if (x3d.shape[0] > 0 and x3d.stride(2) == 1 and x3d.stride(1) == F and x3d.stride(0) >= H * F and x3d.stride(0) % 4 == 0
+                and x3d.data_ptr() % 16 == 0 and x3d.shape[0] * x3d.stride(0) * 4 < 2 ** 32):  # 32-bit byte offsets: a dense copy fits
+            return x3d, int(x3d.stride(0))
+        x3d = x3d.contiguous()
+        return x3d, H * F
+
+    def _dot_ws(self, plans, H, F, dev):
+        L = _lib.lib()
+        need = max([L.mgx_dot_attention_workspace(self._plan_ptr(p), H, F) for p in plans] + [0])
+        return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+
+    def dot_attention_fwd(self, csc, q3d, k3d, v3d, scale):
+        """q3d [n_dst, H, F], k3d / v3d [n_src, H, F] (row-strided views are taken as they are) -> (out [n_dst, H, F],
+        stat [n_dst, H, 4] = (m, 1/s, -, -))."""
+        dev = self._check_dev(csc.indptr, q3d, k3d, v3d)
+        H, F = int(q3d.shape[1]), int(q3d.shape[2])
+        same = k3d is v3d
+        (q, q_ld), (k, k_ld) = self._dot_operand(q3d), self._dot_operand(k3d)
+        v, v_ld = (k, k_ld) if same else self._dot_operand(v3d)
+        out = torch.empty((csc.num_rows, H, F), dtype=torch.float32, device=dev)
+        stat = torch.empty((csc.num_rows, H, 4), dtype=torch.float32, device=dev)
+        plan = csc.plan()
+        ws = self._dot_ws([plan], H, F, dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="dot_attn_fwd", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
+            _lib.check(_lib.lib().mgx_dot_attention_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), H, F, _ptr(q), q_ld, _ptr(k), k_ld,
+                                                        _ptr(v), v_ld, ctypes.c_float(scale), _ptr(out), _ptr(stat), _ptr(ws), _stream(dev)))
+        return out, stat
+
+    def dot_attention_bwd(self, csc, csr, q3d, k3d, v3d, scale, out3d, d_out3d, stat, need_q, need_k, need_v):
+        """-> (dq | None, dk | None, dv | None), each dense; stat[..., 2] is overwritten with <out, d_out> per head."""
+        dev = self._check_dev(csc.indptr, csr.indptr, q3d, k3d, v3d, out3d, d_out3d, stat)
+        H, F = int(q3d.shape[1]), int(q3d.shape[2])
+        if not (need_q or need_k or need_v):
+            return None, None, None
+        same = k3d is v3d
+        (q, q_ld), (k, k_ld) = self._dot_operand(q3d), self._dot_operand(k3d)
+        v, v_ld = (k, k_ld) if same else self._dot_operand(v3d)
+        dq = torch.empty((csc.num_rows, H, F), dtype=torch.float32, device=dev) if need_q else None
+        dk = torch.empty((csc.num_cols, H, F), dtype=torch.float32, device=dev) if need_k else None
+        dv = torch.empty((csc.num_cols, H, F), dtype=torch.float32, device=dev) if need_v else None
+        p_dst, p_src = csc.plan(), csr.plan()
+        ws = self._dot_ws([p_dst, p_src], H, F, dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="dot_attn_bwd", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
+            _lib.check(_lib.lib().mgx_dot_attention_bwd(ctypes.byref(csc.c_struct()), self._plan_ptr(p_dst), ctypes.byref(csr.c_struct()),
+                                                        self._plan_ptr(p_src), H, F, _ptr(q), q_ld, _ptr(k), k_ld, _ptr(v), v_ld,
+                                                        ctypes.c_float(scale), _ptr(out3d), _ptr(d_out3d), _ptr(stat), _ptr(dq), _ptr(dk),
+                                                        _ptr(dv), _ptr(ws), _stream(dev)))
+        return dq, dk, dv
+
     @staticmethod
     def head_dot_supported(H, F):
         return H * F <= 256 and (F <= 64 or F in (128, 256))

@@ -419,6 +419,36 @@ int32_t mgx_gat_tile_bwd(const mgx_csr* csc, const mgx_spmm_plan* csc_plan, cons
                          float* nstat, float* d_feat /* may be NULL with d_el */, float* d_el, float* d_er, void* workspace,
                          void* pack_ws, void* stream);
 
+/* Scaled dot-product attention over a graph with NO E-sized tensor (dgl.nn.DotGatConv between its projection and its result:
+ * apply_edges(fn.u_dot_v) -> edge_softmax -> update_all(fn.u_mul_e, fn.sum); csrc/dotattn.hip):
+ *   z[e,h]     = scale * sum_f q[dst(e),h,f] * k[src(e),h,f]          (scale applied once, after the sum)
+ *   a[e,h]     = exp(z[e,h] - m[v,h]) / s[v,h],   m, s = max and sum over the in-edges of v = dst(e)
+ *   out[v,h,:] = sum_{e: u->v} a[e,h] * v[u,h,:]                      (exactly 0 for a destination without in-edges)
+ *   fwd: writes out and stat[v,h,0..3] = (m, 1/s, -, -), from which the backward rebuilds a[e,h]; `a` is never written.
+ *   bwd: with t[v,h] = <out[v,h,:], d_out[v,h,:]> (written to stat[v,h,2]), dp[e,h] = <v[u,h,:], d_out[v,h,:]> and
+ *        ds = a * (dp - t) * scale:   dq[v] = sum_e ds * k[u],   dk[u] = sum_e ds * q[v],   dv[u] = sum_e a * d_out[v].
+ *        `csc` is the in-CSR the forward ran on, `csr` its transpose (rows = source nodes).  dq, dk, dv may each be NULL.
+ * q [num_rows, q_ld], k [num_cols, k_ld], v [num_cols, v_ld]: the first H*F floats of a row are the operand; every row stride is
+ * a multiple of 4 floats, at least H*F, with a 16-byte aligned base -- so q, k and v may be column blocks of one [N, 3*H*F]
+ * projection.  k == v with k_ld == v_ld: the row is gathered once.  out, d_out, dq [num_rows, H*F], dk, dv [num_cols, H*F],
+ * stat [num_rows, H, 4]: dense, 16-byte aligned, allocated by the caller.
+ * Supported (mgx_dot_attention_supported; everything else is MGX_ERR_UNSUPPORTED and the caller composes mgx_sddmm_*,
+ * mgx_edge_softmax_* and mgx_spmm_csr): F in {4, 8, 16, 32, 64}, H >= 1, H*F <= 256, 32-bit indices, nnz > 0, and
+ * max(num_rows, num_cols) * H * max(4 F, 16) below 4 GiB (32-bit byte offsets: the dense operands and stat).  A strided q, k or v
+ * whose rows * row stride * 4 reaches 4 GiB is MGX_ERR_UNSUPPORTED too: pass a dense copy.
+ * workspace: max over the plans passed of mgx_dot_attention_workspace(plan, H, F) bytes (NULL when no plan splits rows).
+ * mgx_last_spmm_kernel(): "dot_attn_fwd" / "dot_attn_bwd_dst" / "dot_attn_bwd_src" after the respective launch.
+ * Deterministic: no atomics, hub partial sums combined in slot order.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_dot_attention_supported(const mgx_csr* csr, int64_t H, int64_t F);
+int64_t mgx_dot_attention_workspace(const mgx_spmm_plan* plan /* may be NULL */, int64_t H, int64_t F);
+int32_t mgx_dot_attention_fwd(const mgx_csr* csr, const mgx_spmm_plan* plan /* may be NULL */, int64_t H, int64_t F,
+                              const float* q, int64_t q_ld, const float* k, int64_t k_ld, const float* v, int64_t v_ld,
+                              float scale, float* out, float* stat, void* workspace, void* stream);
+int32_t mgx_dot_attention_bwd(const mgx_csr* csc, const mgx_spmm_plan* csc_plan /* may be NULL */, const mgx_csr* csr,
+                              const mgx_spmm_plan* csr_plan /* may be NULL */, int64_t H, int64_t F, const float* q, int64_t q_ld,
+                              const float* k, int64_t k_ld, const float* v, int64_t v_ld, float scale, const float* out,
+                              const float* d_out, float* stat, float* dq, float* dk, float* dv, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ GAT attention terms
  * el[n,h] = sum_f feat[n,h,f] * attn[h,f] -- GATConv's `(feat * attn_l).sum(-1)` (main_dgl_reddit_gat.py:10, UPSTREAM
  * dgl.nn.pytorch.GATConv.forward), one pass; attn_b/out_b (may be NULL) apply a second attention vector to the same
