@@ -18,27 +18,21 @@
 //
 // Laid out like gat_fused_kernel (gatfused.hip): one wave per work item of the mgx_spmm_plan, lanes ALONG the H*F row with 16-byte
 // loads, 64/G neighbour rows per wave-instruction, ids handed out by ds_bpermute as 32-bit byte offsets; hub rows are split by the
-// plan and merged in slot order by the fix-up kernels below (no atomics: deterministic).  Every matrix operand of the caller has a
-// row stride, so q, k and v may be column blocks of one projection.  KV_SAME: k and v are one array -- the row is gathered once.
+// plan and merged in slot order (no atomics: deterministic).  The walk skeleton -- the plan's items as kernel arguments, a block's
+// stretch and an item's (row, edge range), the hub-slot convention, the two hub merge kernels -- is plan_walk.h, shared with
+// gatfused.hip; the edge loop, the NaN rule (nan_max: a NaN logit reaches the row's result) and the (m, 1/s, t) statistics are this
+// family's own.  Every matrix operand of the caller has a row stride, so q, k and v may be column blocks of one projection.
+// KV_SAME: k and v are one array -- the row is gathered once.
 #include <math.h>
 
-#include "common.h"
+#include "plan_walk.h"
 
 namespace mgx {
 
 enum { DOT_FWD = 0, DOT_BWD_DST = 1, DOT_BWD_SRC = 2 };
 
 struct DotArgs {
-  const int32_t* indptr;
-  const int32_t* indices;
-  const int32_t* item_row;  // plan (all NULL: one item per row)
-  const int32_t* item_beg;
-  const int32_t* item_end;
-  const int32_t* item_node;
-  int64_t n_items;
-  XcdRanges xcd;
-  int64_t nblocks;
-  int rpb;
+  PlanItems plan;
   int H, D;
   float scale;
   const float* q;      // [num_dst, q_ld]
@@ -55,63 +49,7 @@ struct DotArgs {
   float* partial2;     // BWD_SRC: [slots, D] of d v; FWD: [slots, 2H] chunk statistics (m_c, s_c)
 };
 
-// max that keeps a NaN (fmaxf drops it): a NaN logit must reach the row's result
-__device__ __forceinline__ float dot_nmax(float a, float b) { return (a > b || a != a) ? a : b; }
-
 __device__ __forceinline__ float dot4(const v4f& a, const v4f& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-
-// ---------------------------------------------------------------------------------------------- hub rows
-// Forward: a hub row's chunks each leave (m_c, s_c) per head in pstat [slot, 2H] and an accumulator relative to m_c in partial
-// [slot, D]; merged in slot order: m = max m_c, s = sum s_c e^(m_c - m), out = sum acc_c e^(m_c - m) / s.
-__global__ __launch_bounds__(kBlock) void dot_attn_online_fixup_kernel(const int32_t* hub_row, const int32_t* hub_slot_ptr, int64_t n_hubs,
-                                                                       int H, int F, const float* partial, const float* pstat, float* out,
-                                                                       float* stat) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t hb = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-  if (hb >= n_hubs) return;
-  const int64_t row = hub_row[hb];
-  const int s0 = hub_slot_ptr[hb], s1 = hub_slot_ptr[hb + 1];
-  const int D = H * F;
-  for (int c = lane; c < D; c += kWave) {
-    const int h = c / F;
-    float m = -INFINITY;
-    for (int s = s0; s < s1; ++s) m = dot_nmax(m, pstat[(int64_t)s * 2 * H + h]);
-    float sum = 0.f, acc = 0.f;
-    for (int s = s0; s < s1; ++s) {
-      const float mc = pstat[(int64_t)s * 2 * H + h];
-      if (!(mc == -INFINITY)) {
-        const float fct = __expf(mc - m);
-        sum += pstat[(int64_t)s * 2 * H + H + h] * fct;
-        acc += partial[(int64_t)s * D + c] * fct;
-      }
-    }
-    const float is = sum == 0.f ? 0.f : 1.f / sum;
-    out[row * D + c] = acc * is;
-    if (c % F == 0) {
-      v4f st;
-      st.x = m == -INFINITY ? 0.f : m;
-      st.y = is;
-      st.z = 0.f;
-      st.w = 0.f;
-      *reinterpret_cast<v4f*>(stat + (row * H + h) * 4) = st;
-    }
-  }
-}
-
-// out[hub_row[h], c] = sum over the hub's slots, in slot order, of partial[slot, c]
-__global__ __launch_bounds__(kBlock) void dot_attn_rows_fixup_kernel(const int32_t* hub_row, const int32_t* hub_slot_ptr, int64_t n_hubs,
-                                                                     int L, const float* partial, float* out) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t h = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-  if (h >= n_hubs) return;
-  const int64_t row = hub_row[h];
-  const int s0 = hub_slot_ptr[h], s1 = hub_slot_ptr[h + 1];
-  for (int c = lane; c < L; c += kWave) {
-    float acc = 0.f;
-    for (int s = s0; s < s1; ++s) acc += partial[(int64_t)s * L + c];
-    out[row * L + c] = acc;
-  }
-}
 
 // t[v,h] = <out[v,h,:], d out[v,h,:]> into stat[v,h,2] -- only when d q is not wanted but d k is (BWD_DST writes it otherwise)
 __global__ __launch_bounds__(kBlock) void dot_attn_t_kernel(int64_t rows, int H, int F, const float* out, const float* dout, float* stat) {
@@ -125,18 +63,12 @@ __global__ __launch_bounds__(kBlock) void dot_attn_t_kernel(int64_t rows, int H,
 }
 
 // ---------------------------------------------------------------------------------------------- the gather kernels
-template <int G>
-struct DotUnroll {
-  static constexpr int NB = kWave / G;
-  static constexpr int value = NB >= 16 ? 1 : (NB >= 8 ? 2 : 4);
-};
-
 // G lanes cover one H*F row (16 bytes each; the lanes past D / 4 of a row whose lane count is no power of two idle);
 // LPH = F / 4 lanes share a head.
 template <int G, int LPH, int MODE, bool KV_SAME>
 __global__ __launch_bounds__(kBlock) void dot_attn_kernel(const DotArgs a) {
   constexpr int NB = kWave / G;
-  constexpr int U = DotUnroll<G>::value;
+  constexpr int U = LaneUnroll<G>::value;
   constexpr int STEP = NB * U;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -157,24 +89,14 @@ __global__ __launch_bounds__(kBlock) void dot_attn_kernel(const DotArgs a) {
   const uint32_t h16 = (uint32_t)head * 16u;
   const float scale = a.scale;
   int64_t item_base, item_stop;
-  xcd_stretch(a.xcd, item_base, item_stop);
-  item_base += (int64_t)(blockIdx.x / kXcds) * a.rpb;
+  plan_block_items(a.plan, item_base, item_stop);
 
-  for (int r = wave; r < a.rpb; r += kWavesPerBlock) {
+  for (int r = wave; r < a.plan.rpb; r += kWavesPerBlock) {
     const int64_t item = item_base + r;
     if (item >= item_stop) break;
-    int64_t row, irow;
-    int32_t beg, end;
-    if (a.item_row) {
-      irow = a.item_row[item];
-      row = a.item_node[item];
-      beg = a.item_beg[item];
-      end = a.item_end[item];
-    } else {
-      irow = row = item;
-      beg = a.indptr[item];
-      end = a.indptr[item + 1];
-    }
+    const PlanItem it = plan_item(a.plan, item);
+    const int64_t row = it.row, irow = it.irow;
+    const int32_t beg = it.beg, end = it.end;
     // ---- row constants (idle lanes hold zeros and take part in the lane swaps)
     v4f ra = (v4f)(0.f), rb = (v4f)(0.f);  // FWD: q[v], -; BWD_DST: q[v], d out[v]; BWD_SRC: k[u], v[u]
     float c_m = 0.f, c_is = 0.f, c_t = 0.f;
@@ -204,7 +126,7 @@ __global__ __launch_bounds__(kBlock) void dot_attn_kernel(const DotArgs a) {
       const int32_t p = cbase + lane;
       uint32_t aoff = 0, boff = 0, soff = 0;
       if (p < end) {
-        const uint32_t gid = (uint32_t)__builtin_nontemporal_load(&a.indices[p]);
+        const uint32_t gid = (uint32_t)__builtin_nontemporal_load(&a.plan.indices[p]);
         aoff = gid * abytes;
         boff = gid * bbytes;
         soff = gid * sbytes;
@@ -226,7 +148,7 @@ __global__ __launch_bounds__(kBlock) void dot_attn_kernel(const DotArgs a) {
           const bool live = j + u * NB + sub < cnt;
           const float z = lanes_sum<LPH>(dot4(ra, va[u])) * scale;
           if (MODE == DOT_FWD) {
-            const float mn = live ? dot_nmax(run_m, z) : run_m;
+            const float mn = live ? nan_max(run_m, z) : run_m;
             const float rescale = run_m == -INFINITY ? 0.f : __expf(run_m - mn);  // 1 while the maximum stands
             const float pe = (!live || mn == -INFINITY) ? 0.f : __expf(z - mn);   // mn = -inf: only masked logits (-inf) so far
             run_s = run_s * rescale + pe;
@@ -251,7 +173,7 @@ __global__ __launch_bounds__(kBlock) void dot_attn_kernel(const DotArgs a) {
       for (int off = G; off < kWave; off <<= 1) {
         const float mo = __shfl_xor(run_m, off, kWave), so = __shfl_xor(run_s, off, kWave);
         const v4f ao = vec_shfl_xor<4>(acc, off);
-        const float mn = dot_nmax(run_m, mo);
+        const float mn = nan_max(run_m, mo);
         const float f1 = run_m == -INFINITY ? 0.f : __expf(run_m - mn), f2 = mo == -INFINITY ? 0.f : __expf(mo - mn);
         run_s = run_s * f1 + so * f2;
         acc = acc * f1 + ao * f2;
@@ -269,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void dot_attn_kernel(const DotArgs a) {
           *reinterpret_cast<v4f*>(a.stat_w + (row * H + head) * 4) = st;
         }
       } else if (lead) {  // hub chunk: statistics travel with the unnormalised partial row
-        const int64_t slot = -(irow + 1);
+        const int64_t slot = plan_slot(irow);
         a.partial2[slot * 2 * H + head] = run_m;
         a.partial2[slot * 2 * H + H + head] = run_s;
       }
@@ -281,7 +203,7 @@ __global__ __launch_bounds__(kBlock) void dot_attn_kernel(const DotArgs a) {
       }
     }
     if (fact && sub == 0) {
-      const int64_t slot = -(irow + 1);
+      const int64_t slot = plan_slot(irow);
       if (a.o1) *reinterpret_cast<v4f*>(irow >= 0 ? a.o1 + row * (int64_t)D + f : a.partial + slot * (int64_t)D + f) = acc;
       if (MODE == DOT_BWD_SRC && a.o2) *reinterpret_cast<v4f*>(irow >= 0 ? a.o2 + row * (int64_t)D + f : a.partial2 + slot * (int64_t)D + f) = acc2;
     }
@@ -290,7 +212,7 @@ __global__ __launch_bounds__(kBlock) void dot_attn_kernel(const DotArgs a) {
 
 template <int G, int LPH, int MODE>
 static void dot_launch_kv(const DotArgs& a, bool kv_same, hipStream_t s) {
-  const dim3 grid((unsigned)a.nblocks), block(kBlock);
+  const dim3 grid((unsigned)a.plan.nblocks), block(kBlock);
   if (MODE != DOT_BWD_SRC && kv_same) hipLaunchKernelGGL((dot_attn_kernel<G, LPH, MODE, true>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((dot_attn_kernel<G, LPH, MODE, false>), grid, block, 0, s, a);
 }
@@ -350,31 +272,14 @@ static int32_t dot_check(const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t 
   if (csr->nnz <= 0) MGX_UNSUPPORTED("%s: graph without edges", who);
   if (!dot_size_ok(csr, H, F)) MGX_UNSUPPORTED("%s: operands beyond 32-bit byte offsets", who);
   MGX_CHECK_ARG(csr->indptr && csr->indices, "%s: indptr / indices is NULL", who);
-  if (plan) {
-    MGX_CHECK_ARG(plan->item_row && plan->item_beg && plan->item_end && plan->item_node && plan->num_items >= csr->num_rows,
-                  "%s: malformed plan", who);
-    MGX_CHECK_ARG(plan->num_slots == 0 || (plan->hub_row && plan->hub_slot_ptr), "%s: plan has split rows but no hub tables", who);
-  }
-  return MGX_OK;
+  return plan_check(csr, plan, who);
 }
 
 static void dot_fill(DotArgs& a, const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t H, int64_t F, float scale) {
   memset(&a, 0, sizeof(a));
-  a.indptr = (const int32_t*)csr->indptr; a.indices = (const int32_t*)csr->indices;
-  a.n_items = csr->num_rows;
-  if (plan) {
-    a.item_row = plan->item_row; a.item_beg = (const int32_t*)plan->item_beg; a.item_end = (const int32_t*)plan->item_end;
-    a.item_node = plan->item_node; a.n_items = plan->num_items;
-  }
-  a.rpb = 16;  // work items per workgroup: the g-SpMM's measured choice (spmm.hip), as gatfused.hip
-  a.nblocks = xcd_ranges(plan, a.n_items, a.rpb, a.xcd);
+  plan_items_fill(a.plan, csr, plan, kPlanRowsPerBlock);
   a.H = (int)H; a.D = (int)(H * F);
   a.scale = scale;
-}
-
-static void dot_rows_fixup(const mgx_spmm_plan* plan, int L, const float* partial, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(dot_attn_rows_fixup_kernel, dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s,
-                     plan->hub_row, plan->hub_slot_ptr, plan->num_hubs, L, partial, out);
 }
 
 }  // namespace mgx
@@ -419,9 +324,7 @@ extern "C" int32_t mgx_dot_attention_fwd(const mgx_csr* csr, const mgx_spmm_plan
   if (!dot_launch<DOT_FWD>(a, (int)F, k == v && k_ld == v_ld, s)) MGX_UNSUPPORTED("mgx_dot_attention_fwd: unsupported head layout");
   MGX_CHECK_LAUNCH();
   if (hubs) {
-    hipLaunchKernelGGL(dot_attn_online_fixup_kernel, dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s,
-                       plan->hub_row, plan->hub_slot_ptr, plan->num_hubs, (int)H, (int)F, (const float*)a.partial, (const float*)a.partial2,
-                       out, stat);
+    hub_online_merge<true>(plan, (int)H, (int)F, nullptr, a.partial, a.partial2, out, stat, s);
     MGX_CHECK_LAUNCH();
   }
   note_spmm_kernel("dot_attn_fwd");
@@ -463,7 +366,7 @@ extern "C" int32_t mgx_dot_attention_bwd(const mgx_csr* csc, const mgx_spmm_plan
     if (!dot_launch<DOT_BWD_DST>(a, (int)F, k == v && k_ld == v_ld, s)) MGX_UNSUPPORTED("mgx_dot_attention_bwd: unsupported head layout");
     MGX_CHECK_LAUNCH();
     if (hubs_dst) {
-      dot_rows_fixup(csc_plan, (int)D, a.partial, dq, s);
+      hub_rows_sum(csc_plan, (int)D, a.partial, dq, s);
       MGX_CHECK_LAUNCH();
     }
     note_spmm_kernel("dot_attn_bwd_dst");
@@ -484,8 +387,8 @@ extern "C" int32_t mgx_dot_attention_bwd(const mgx_csr* csc, const mgx_spmm_plan
     if (!dot_launch<DOT_BWD_SRC>(a, (int)F, false, s)) MGX_UNSUPPORTED("mgx_dot_attention_bwd: unsupported head layout");
     MGX_CHECK_LAUNCH();
     if (hubs_src) {
-      if (dk) dot_rows_fixup(csr_plan, (int)D, a.partial, dk, s);
-      if (dv) dot_rows_fixup(csr_plan, (int)D, a.partial2, dv, s);
+      if (dk) hub_rows_sum(csr_plan, (int)D, a.partial, dk, s);
+      if (dv) hub_rows_sum(csr_plan, (int)D, a.partial2, dv, s);
       MGX_CHECK_LAUNCH();
     }
     note_spmm_kernel("dot_attn_bwd_src");

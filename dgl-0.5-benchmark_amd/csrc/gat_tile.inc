@@ -69,12 +69,8 @@ __device__ __forceinline__ float gat_pair_keep(uint64_t seed, int dst, int src, 
   return gat_hash(seed, (uint32_t)src, (uint32_t)dst + rank * 0x9E3779B1u) >= drop_below ? keep_scale : 0.f;
 }
 
-// x of the lane quad_perm names inside this lane's quad (four consecutive lanes = the lane group of one row); CTRL = a | b << 2 |
-// c << 4 | d << 6: 0xB1 swaps neighbours, 0x4E swaps pairs, 0x00 / 0x55 / 0xAA / 0xFF broadcast lane 0 / 1 / 2 / 3.
-template <int CTRL>
-__device__ __forceinline__ float quad_perm(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
+// dpp_mov<CTRL> below: x of the lane quad_perm names inside this lane's quad (four consecutive lanes = the lane group of one row);
+// CTRL = a | b << 2 | c << 4 | d << 6: 0xB1 swaps neighbours, 0x4E swaps pairs, 0x00 / 0x55 / 0xAA / 0xFF broadcast lane 0 / 1 / 2 / 3.
 
 template <int MODE, int NACC, bool DROP>
 __global__ __launch_bounds__(512, 4) void gat_tile_kernel(const GatTileArgs a) {
@@ -194,18 +190,18 @@ __global__ __launch_bounds__(512, 4) void gat_tile_kernel(const GatTileArgs a) {
     const float z = t > 0.f ? t : t * a.slope;
     if (MODE == GAT_FWD) {
       float m4 = live ? z : -INFINITY;
-      m4 = fmaxf(m4, quad_perm<0xB1>(m4));
-      m4 = fmaxf(m4, quad_perm<0x4E>(m4));
+      m4 = fmaxf(m4, dpp_mov<0xB1>(m4));
+      m4 = fmaxf(m4, dpp_mov<0x4E>(m4));
       const float mx = fmaxf(rm[j], m4);
       const float resc = rm[j] > -INFINITY ? __expf(rm[j] - mx) : 0.f;
       const float pe = live && mx > -INFINITY ? __expf(z - mx) : 0.f;  // mx = -inf: only masked logits (-inf) so far
-      float ps = pe + quad_perm<0xB1>(pe);
-      ps += quad_perm<0x4E>(ps);
+      float ps = pe + dpp_mov<0xB1>(pe);
+      ps += dpp_mov<0x4E>(ps);
       const float pw = pe * keep;
-      v4f pa = v[0] * quad_perm<0x00>(pw);  // explicit fused multiply-adds (the library is built with -ffp-contract=off)
-      pa = __builtin_elementwise_fma(v[1], (v4f)(quad_perm<0x55>(pw)), pa);
-      pa = __builtin_elementwise_fma(v[2], (v4f)(quad_perm<0xAA>(pw)), pa);
-      pa = __builtin_elementwise_fma(v[3], (v4f)(quad_perm<0xFF>(pw)), pa);
+      v4f pa = v[0] * dpp_mov<0x00>(pw);  // explicit fused multiply-adds (the library is built with -ffp-contract=off)
+      pa = __builtin_elementwise_fma(v[1], (v4f)(dpp_mov<0x55>(pw)), pa);
+      pa = __builtin_elementwise_fma(v[2], (v4f)(dpp_mov<0xAA>(pw)), pa);
+      pa = __builtin_elementwise_fma(v[3], (v4f)(dpp_mov<0xFF>(pw)), pa);
       rs[j] = __builtin_fmaf(rs[j], resc, ps);
       acc[j] = __builtin_elementwise_fma(acc[j], (v4f)(resc), pa);
       rm[j] = mx;
@@ -218,8 +214,8 @@ __global__ __launch_bounds__(512, 4) void gat_tile_kernel(const GatTileArgs a) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         d[u] = __builtin_fmaf(v[u].w, ra[j].w, __builtin_fmaf(v[u].z, ra[j].z, __builtin_fmaf(v[u].y, ra[j].y, v[u].x * ra[j].x)));
-        d[u] += quad_perm<0xB1>(d[u]);
-        d[u] += quad_perm<0x4E>(d[u]);
+        d[u] += dpp_mov<0xB1>(d[u]);
+        d[u] += dpp_mov<0x4E>(d[u]);
       }
       float dot = d[0];  // this lane's entry
       dot = l == 1 ? d[1] : dot;
@@ -228,10 +224,10 @@ __global__ __launch_bounds__(512, 4) void gat_tile_kernel(const GatTileArgs a) {
       hacc[j] += av * (dot * keep - tt) * (t > 0.f ? 1.f : a.slope);  // summed over the quad in the epilogue
       if (MODE == GAT_BWD_SRC) {
         const float w = av * keep;
-        acc[j] = __builtin_elementwise_fma(v[0], (v4f)(quad_perm<0x00>(w)), acc[j]);
-        acc[j] = __builtin_elementwise_fma(v[1], (v4f)(quad_perm<0x55>(w)), acc[j]);
-        acc[j] = __builtin_elementwise_fma(v[2], (v4f)(quad_perm<0xAA>(w)), acc[j]);
-        acc[j] = __builtin_elementwise_fma(v[3], (v4f)(quad_perm<0xFF>(w)), acc[j]);
+        acc[j] = __builtin_elementwise_fma(v[0], (v4f)(dpp_mov<0x00>(w)), acc[j]);
+        acc[j] = __builtin_elementwise_fma(v[1], (v4f)(dpp_mov<0x55>(w)), acc[j]);
+        acc[j] = __builtin_elementwise_fma(v[2], (v4f)(dpp_mov<0xAA>(w)), acc[j]);
+        acc[j] = __builtin_elementwise_fma(v[3], (v4f)(dpp_mov<0xFF>(w)), acc[j]);
       }
     }
   };
@@ -406,7 +402,7 @@ __global__ __launch_bounds__(512, 4) void gat_tile_kernel(const GatTileArgs a) {
   for (int j = 0; j < NACC; ++j) {
     if (item[j] == kNoItem) continue;
     const bool whole = item[j] >= 0;
-    const int64_t row = node[j], slot = -((int64_t)item[j] + 1);
+    const int64_t row = node[j], slot = plan_slot(item[j]);
     if (MODE == GAT_FWD) {
       if (whole) {
         const float is = rs[j] > 0.f ? 1.f / rs[j] : 0.f;  // rows without in-edges aggregate to 0
@@ -428,8 +424,8 @@ __global__ __launch_bounds__(512, 4) void gat_tile_kernel(const GatTileArgs a) {
       }
     } else {
       if (MODE == GAT_BWD_SRC && cvalid) *reinterpret_cast<v4f*>((whole ? a.out + row * a.D : a.partial + slot * a.D) + col) = acc[j];
-      float hs = hacc[j] + quad_perm<0xB1>(hacc[j]);  // every lane accumulated the terms of its own entries
-      hs += quad_perm<0x4E>(hs);
+      float hs = hacc[j] + dpp_mov<0xB1>(hacc[j]);  // every lane accumulated the terms of its own entries
+      hs += dpp_mov<0x4E>(hs);
       if (l == 0) *(whole ? a.out_h + row : a.partial_h + slot) = hs;
     }
   }

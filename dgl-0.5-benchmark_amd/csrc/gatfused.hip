@@ -21,12 +21,16 @@
 // All three gather kernels are laid out like the summing g-SpMM (spmm.hip): one wave per work item of the
 // mgx_spmm_plan, lanes ALONG the H*F feature row with 16-byte loads, 64/G neighbour rows per wave-instruction, ids
 // handed out by ds_bpermute as 32-bit byte offsets; hub rows are split by the plan, their partial sums are combined in
-// slot order by gat_rows_fixup_kernel (no atomics: deterministic).  HBM/gather-bound fp32 work, no MFMA.
+// slot order (no atomics: deterministic).  The walk skeleton -- the plan's items as kernel arguments, a block's stretch and an
+// item's (row, edge range), the hub-slot convention, the two hub merge kernels -- is plan_walk.h, shared with dotattn.hip; the edge
+// loop, the NaN rule (fmaxf: a NaN logit does not become the maximum) and the (er, m, 1/s, t) statistics are this family's own.
+// HBM/gather-bound fp32 work, no MFMA.
 #include <math.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
+#include "plan_walk.h"
 #include "tile_common.h"
 
 namespace mgx {
@@ -46,37 +50,9 @@ __device__ __forceinline__ uint32_t gat_hash(uint64_t seed, uint32_t klo, uint32
   return x;
 }
 
-// Sum over the LPH lanes of a head (LPH a power of two, the lanes aligned to LPH): the xor butterfly of __shfl_xor, with its first
-// four steps as DPP moves instead of ds_bpermute -- swap neighbours, swap pairs (quad_perm), then mirror a half row and a row
-// (every lane of a quad / half row already holds the same partial sum, so the mirrored partner's value IS the xor partner's).
-// Bitwise the same sums; no LDS-pipe instruction for heads of up to 16 lanes.
-template <int CTRL>
-__device__ __forceinline__ float gat_dpp(float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-template <int LPH>
-__device__ __forceinline__ float head_sum(float x) {
-  if (LPH >= 2) x += gat_dpp<0xB1>(x);    // quad_perm [1, 0, 3, 2]
-  if (LPH >= 4) x += gat_dpp<0x4E>(x);    // quad_perm [2, 3, 0, 1]
-  if (LPH >= 8) x += gat_dpp<0x141>(x);   // row_half_mirror
-  if (LPH >= 16) x += gat_dpp<0x140>(x);  // row_mirror
-#pragma unroll
-  for (int off = 16; off < LPH; off <<= 1) x += __shfl_xor(x, off, kWave);
-  return x;
-}
-
 struct GatArgs {
-  const int32_t* indptr;
-  const int32_t* indices;
+  PlanItems plan;
   const int32_t* eids;      // CSR position -> edge id (NULL: identity); keys the dropout mask
-  const int32_t* item_row;  // plan (all NULL: one item per row)
-  const int32_t* item_beg;
-  const int32_t* item_end;
-  const int32_t* item_node;
-  int64_t n_items;
-  XcdRanges xcd;    // item stretch of every XCD (edge balanced when the plan says so)
-  int64_t nblocks;
-  int rpb;
   int H, F, D;
   float slope;
   uint32_t drop_below;  // keep when (uint32)hash >= drop_below
@@ -98,67 +74,8 @@ struct GatArgs {
   int small_ld;         // floats between consecutive nodes of the small gathered array (el: H, nstat: 4H unless packed)
 };
 
-// ---------------------------------------------------------------------------------------------- hub rows of the forward
-// A hub row's chunks each leave (running max m_c, sum s_c) per head in partial_h [slot, 2H] and an accumulator relative to
-// m_c in partial [slot, D]; merged here in slot order: m = max m_c, s = sum s_c e^(m_c - m), out = sum acc_c e^(m_c - m) / s.
-__global__ __launch_bounds__(kBlock) void gat_online_fixup_kernel(const int32_t* hub_row, const int32_t* hub_slot_ptr, int64_t n_hubs,
-                                                                  int H, int F, const float* er, const float* partial,
-                                                                  const float* partial_h, float* out, float* nstat) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t hb = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-  if (hb >= n_hubs) return;
-  const int64_t row = hub_row[hb];
-  const int s0 = hub_slot_ptr[hb], s1 = hub_slot_ptr[hb + 1];
-  const int D = H * F;
-  for (int k = lane; k < D; k += kWave) {
-    const int h = k / F;
-    float m = -INFINITY;
-    for (int s = s0; s < s1; ++s) m = fmaxf(m, partial_h[(int64_t)s * 2 * H + h]);
-    float sum = 0.f, acc = 0.f;
-    for (int s = s0; s < s1; ++s) {
-      const float mc = partial_h[(int64_t)s * 2 * H + h];
-      if (mc > -INFINITY) {
-        const float fct = __expf(mc - m);
-        sum += partial_h[(int64_t)s * 2 * H + H + h] * fct;
-        acc += partial[(int64_t)s * D + k] * fct;
-      }
-    }
-    const float is = sum > 0.f ? 1.f / sum : 0.f;
-    out[row * D + k] = acc * is;
-    if (k % F == 0) {
-      v4f st;
-      st.x = er[row * H + h];
-      st.y = m > -INFINITY ? m : 0.f;
-      st.z = is;
-      st.w = 0.f;
-      *reinterpret_cast<v4f*>(nstat + (row * H + h) * 4) = st;
-    }
-  }
-}
-
-// out[hub_row[h], k] = sum over the hub's slots, in slot order, of partial[slot, k]
-__global__ __launch_bounds__(kBlock) void gat_rows_fixup_kernel(const int32_t* hub_row, const int32_t* hub_slot_ptr, int64_t n_hubs,
-                                                                int L, const float* partial, float* out) {
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t h = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-  if (h >= n_hubs) return;
-  const int64_t row = hub_row[h];
-  const int s0 = hub_slot_ptr[h], s1 = hub_slot_ptr[h + 1];
-  for (int k = lane; k < L; k += kWave) {
-    float acc = 0.f;
-    for (int s = s0; s < s1; ++s) acc += partial[(int64_t)s * L + k];
-    out[row * L + k] = acc;
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- the gather kernels
 enum { GAT_FWD = 0, GAT_BWD_DST = 1, GAT_BWD_SRC = 2 };
-
-template <int G>
-struct GatUnroll {
-  static constexpr int NB = kWave / G;
-  static constexpr int value = NB >= 16 ? 1 : (NB >= 8 ? 2 : 4);
-};
 
 // G lanes cover one H*F row (16 bytes each); LPH = F / 4 lanes share a head.
 // RAGGED (one head, F % 4 != 0, e.g. the 41-class output layer of main_dgl_reddit_gat.py): rows are still moved 16 bytes per
@@ -174,7 +91,7 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
   typedef v4f v4u __attribute__((aligned(4)));
   typedef typename std::conditional<RAGGED, v4u, v4f>::type V4;
   constexpr int NB = kWave / G;
-  constexpr int U = GatUnroll<G>::value;
+  constexpr int U = LaneUnroll<G>::value;
   constexpr int STEP = NB * U;
   // heads of >= 4 lanes, four edges per batch: 8 x 16, 4 x 16, 4 x 64, the 41-column layer (whose destination walk measured slower this way)
   constexpr bool QUAD = LPH >= 4 && U == 4 && (LPH == 4 || MODE != GAT_BWD_DST);
@@ -201,31 +118,21 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
   v4f al = (v4f)(0.f);
   if (ELK && fact) al = *reinterpret_cast<const v4f*>(a.attn + f);  // attn_l[head, (l % LPH) * 4 ..]: flat index = this lane's column
   auto head_dot = [&](const v4f& v) -> float {  // <row[h,:], attn_l[h,:]> over the LPH lanes of this lane's head
-    return head_sum<LPH>(v.x * al.x + v.y * al.y + v.z * al.z + v.w * al.w);
+    return lanes_sum<LPH>(v.x * al.x + v.y * al.y + v.z * al.z + v.w * al.w);
   };
   const uint32_t hbytes = (uint32_t)a.small_ld * 4u;  // per-node stride of the small per-head array (el: H floats, nstat: 4H; packed: the row stride)
   const uint32_t h4 = (uint32_t)head * (MODE == GAT_BWD_SRC ? 16u : 4u);
   const char* __restrict__ gatb = reinterpret_cast<const char*>(a.gat);
   const char* __restrict__ smallb = reinterpret_cast<const char*>(MODE == GAT_BWD_SRC ? a.nstat : a.el);
   int64_t item_base, item_stop;
-  xcd_stretch(a.xcd, item_base, item_stop);
-  item_base += (int64_t)(blockIdx.x / kXcds) * a.rpb;
+  plan_block_items(a.plan, item_base, item_stop);
 
-  for (int r = wave; r < a.rpb; r += kWavesPerBlock) {
+  for (int r = wave; r < a.plan.rpb; r += kWavesPerBlock) {
     const int64_t item = item_base + r;
     if (item >= item_stop) break;
-    int64_t row, irow;
-    int32_t beg, end;
-    if (a.item_row) {
-      irow = a.item_row[item];
-      row = a.item_node[item];
-      beg = a.item_beg[item];
-      end = a.item_end[item];
-    } else {
-      irow = row = item;
-      beg = a.indptr[item];
-      end = a.indptr[item + 1];
-    }
+    const PlanItem it = plan_item(a.plan, item);
+    const int64_t row = it.row, irow = it.irow;
+    const int32_t beg = it.beg, end = it.end;
     // ---- row constants
     v4f ra = (v4f)(0.f);
     float c_er = 0.f, c_m = 0.f, c_is = 0.f, c_t = 0.f, c_el = 0.f;
@@ -245,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
         ra = clip((v4f)*reinterpret_cast<const V4*>(a.rowa + row * D + fw));  // d out[v]
         ov = (v4f)*reinterpret_cast<const V4*>(a.rowb + row * D + fw);        // out[v]
       }
-      const float t = head_sum<LPH>(ra.x * ov.x + ra.y * ov.y + ra.z * ov.z + ra.w * ov.w);  // idle lanes take part with zeros
+      const float t = lanes_sum<LPH>(ra.x * ov.x + ra.y * ov.y + ra.z * ov.z + ra.w * ov.w);  // idle lanes take part with zeros
       c_t = t;
       // every chunk of a hub row writes the same value
       if (fact && (l % LPH) == 0 && sub == 0) a.nstat_w[(row * H + head) * 4 + 3] = t;
@@ -261,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
       uint32_t goff = 0, soff = 0;
       int32_t eid = 0;
       if (q < end) {
-        const int32_t gid = __builtin_nontemporal_load(&a.indices[q]);
+        const int32_t gid = __builtin_nontemporal_load(&a.plan.indices[q]);
         goff = (uint32_t)gid * rowbytes;
         soff = (uint32_t)gid * hbytes;
         if (DROP) eid = a.eids ? __builtin_nontemporal_load(&a.eids[q]) : q;
@@ -299,18 +206,18 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
           const float z = t > 0.f ? t : t * a.slope;
           if (MODE == GAT_FWD) {
             float m4 = live ? z : -INFINITY;
-            m4 = fmaxf(m4, gat_dpp<0xB1>(m4));
-            m4 = fmaxf(m4, gat_dpp<0x4E>(m4));
+            m4 = fmaxf(m4, dpp_mov<0xB1>(m4));
+            m4 = fmaxf(m4, dpp_mov<0x4E>(m4));
             const float mn = fmaxf(run_m, m4);
             const float rescale = run_m > -INFINITY ? __expf(run_m - mn) : 0.f;
             // masked logits (el[u] = -inf) may open a stream: while the maximum is still -inf, z - mn is -inf - -inf, not a weight
             const float pe = live && mn > -INFINITY ? __expf(z - mn) : 0.f;
             const float pw = pe * keep;
-            v4f pa = val[0] * gat_dpp<0x00>(pw);
-            pa = __builtin_elementwise_fma(val[1], (v4f)(gat_dpp<0x55>(pw)), pa);
-            pa = __builtin_elementwise_fma(val[2], (v4f)(gat_dpp<0xAA>(pw)), pa);
-            pa = __builtin_elementwise_fma(val[3], (v4f)(gat_dpp<0xFF>(pw)), pa);
-            run_s = __builtin_fmaf(run_s, rescale, head_sum<4>(pe));
+            v4f pa = val[0] * dpp_mov<0x00>(pw);
+            pa = __builtin_elementwise_fma(val[1], (v4f)(dpp_mov<0x55>(pw)), pa);
+            pa = __builtin_elementwise_fma(val[2], (v4f)(dpp_mov<0xAA>(pw)), pa);
+            pa = __builtin_elementwise_fma(val[3], (v4f)(dpp_mov<0xFF>(pw)), pa);
+            run_s = __builtin_fmaf(run_s, rescale, lanes_sum<4>(pe));
             acc = __builtin_elementwise_fma(acc, (v4f)(rescale), pa);
             run_m = mn;
           } else {
@@ -321,15 +228,15 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
             float d[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-              d[u] = head_sum<LPH>(__builtin_fmaf(val[u].w, ra.w, __builtin_fmaf(val[u].z, ra.z, __builtin_fmaf(val[u].y, ra.y, val[u].x * ra.x))));
+              d[u] = lanes_sum<LPH>(__builtin_fmaf(val[u].w, ra.w, __builtin_fmaf(val[u].z, ra.z, __builtin_fmaf(val[u].y, ra.y, val[u].x * ra.x))));
             const float dot = qv == 0 ? d[0] : (qv == 1 ? d[1] : (qv == 2 ? d[2] : d[3]));
             hacc += av * (dot * keep - tt) * (t > 0.f ? 1.f : a.slope);  // this lane's edge only: summed over the quad below
             if (MODE == GAT_BWD_SRC) {
               const float w = av * keep;
-              acc = __builtin_elementwise_fma(val[0], (v4f)(gat_dpp<0x00>(w)), acc);
-              acc = __builtin_elementwise_fma(val[1], (v4f)(gat_dpp<0x55>(w)), acc);
-              acc = __builtin_elementwise_fma(val[2], (v4f)(gat_dpp<0xAA>(w)), acc);
-              acc = __builtin_elementwise_fma(val[3], (v4f)(gat_dpp<0xFF>(w)), acc);
+              acc = __builtin_elementwise_fma(val[0], (v4f)(dpp_mov<0x00>(w)), acc);
+              acc = __builtin_elementwise_fma(val[1], (v4f)(dpp_mov<0x55>(w)), acc);
+              acc = __builtin_elementwise_fma(val[2], (v4f)(dpp_mov<0xAA>(w)), acc);
+              acc = __builtin_elementwise_fma(val[3], (v4f)(dpp_mov<0xFF>(w)), acc);
             }
           }
           continue;
@@ -372,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
             const float tt = MODE == GAT_BWD_DST ? c_t : sm[u].w;
             const float z = t > 0.f ? t : t * a.slope;
             const float av = __expf(z - mm) * is;
-            const float dot = head_sum<LPH>(val[u].x * ra.x + val[u].y * ra.y + val[u].z * ra.z + val[u].w * ra.w);
+            const float dot = lanes_sum<LPH>(val[u].x * ra.x + val[u].y * ra.y + val[u].z * ra.z + val[u].w * ra.w);
             float de = av * (dot * keep - tt) * (t > 0.f ? 1.f : a.slope);
             de = live ? de : 0.f;
             hacc += de;
@@ -408,7 +315,7 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
           *reinterpret_cast<v4f*>(a.nstat_w + (row * H + head) * 4) = st;
         }
       } else if (fact && sub == 0 && (l % LPH) == 0) {  // hub chunk: statistics travel with the unnormalised partial row
-        const int64_t slot = -(irow + 1);
+        const int64_t slot = plan_slot(irow);
         a.partial_h[slot * 2 * H + head] = run_m;
         a.partial_h[slot * 2 * H + H + head] = run_s;
       }
@@ -417,13 +324,13 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
       for (int off = G; off < kWave; off <<= 1) acc += vec_shfl_xor<4>(acc, off);
     }
     if (MODE != GAT_FWD) {
-      if (QUAD) hacc = head_sum<4>(hacc);  // every lane of the head accumulated its own edges' terms
+      if (QUAD) hacc = lanes_sum<4>(hacc);  // every lane of the head accumulated its own edges' terms
 #pragma unroll
       for (int off = G; off < kWave; off <<= 1) hacc += __shfl_xor(hacc, off, kWave);
     }
     if (fact && sub == 0) {
       if (MODE != GAT_BWD_DST) {
-        float* op = irow >= 0 ? a.out + row * (int64_t)D + f : a.partial + (-(irow + 1)) * (int64_t)D + f;
+        float* op = irow >= 0 ? a.out + row * (int64_t)D + f : a.partial + plan_slot(irow) * (int64_t)D + f;
         if (!tail) {
           *reinterpret_cast<V4*>(op) = acc;
         } else {  // own columns f .. f+nvalid-1 are components 4-nvalid .. 3 of the window
@@ -432,7 +339,7 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
         }
       }
       if (MODE != GAT_FWD && (l % LPH) == 0) {
-        float* op = irow >= 0 ? a.out_h + row * (int64_t)H + head : a.partial_h + (-(irow + 1)) * (int64_t)H + head;
+        float* op = irow >= 0 ? a.out_h + row * (int64_t)H + head : a.partial_h + plan_slot(irow) * (int64_t)H + head;
         *op = hacc;
       }
     }
@@ -441,7 +348,7 @@ __global__ __launch_bounds__(kBlock) void gat_fused_kernel(const GatArgs a) {
 
 template <int G, int LPH, int MODE>
 static void gat_launch_drop(const GatArgs& a, bool drop, hipStream_t s) {
-  const dim3 grid((unsigned)a.nblocks), block(kBlock);
+  const dim3 grid((unsigned)a.plan.nblocks), block(kBlock);
   if (G >= 16 && LPH >= 2 && LPH < G && a.attn) {  // el formed in the kernel (set by the entry points for unpacked multi-head rows)
     constexpr int GE = G >= 16 ? G : 16, LE = (LPH >= 2 && LPH < G) ? LPH : 2;
     if (drop) hipLaunchKernelGGL((gat_fused_kernel<GE, LE, MODE, true, false, true>), grid, block, 0, s, a);
@@ -454,7 +361,7 @@ static void gat_launch_drop(const GatArgs& a, bool drop, hipStream_t s) {
 
 template <int G, int MODE>
 static void gat_launch_ragged(const GatArgs& a, bool drop, hipStream_t s) {  // one head: the whole lane group is the head
-  const dim3 grid((unsigned)a.nblocks), block(kBlock);
+  const dim3 grid((unsigned)a.plan.nblocks), block(kBlock);
   if (drop) hipLaunchKernelGGL((gat_fused_kernel<G, G, MODE, true, true>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((gat_fused_kernel<G, G, MODE, false, true>), grid, block, 0, s, a);
 }
@@ -497,8 +404,6 @@ static bool gat_launch(const GatArgs& a, bool drop, hipStream_t s) {
   }
 }
 
-static int gat_rows_per_block() { return 16; }  // work items per workgroup: the g-SpMM's measured choice (spmm.hip)
-
 static int32_t gat_check(const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t H, int64_t F, int64_t gathered_rows, float p,
                          const char* who) {
   MGX_CHECK_ARG(csr != nullptr, "%s: csr is NULL", who);
@@ -513,25 +418,14 @@ static int32_t gat_check(const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t 
   MGX_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout probability %g outside [0, 1)", who, (double)p);
   MGX_CHECK_ARG(csr->num_rows == 0 || csr->indptr, "%s: indptr is NULL", who);
   MGX_CHECK_ARG(csr->nnz == 0 || csr->indices, "%s: indices is NULL", who);
-  if (plan) {
-    MGX_CHECK_ARG(plan->item_row && plan->item_beg && plan->item_end && plan->item_node && plan->num_items >= csr->num_rows,
-                  "%s: malformed plan", who);
-    MGX_CHECK_ARG(plan->num_slots == 0 || (plan->hub_row && plan->hub_slot_ptr), "%s: plan has split rows but no hub tables", who);
-  }
-  return MGX_OK;
+  return plan_check(csr, plan, who);
 }
 
 static void gat_fill(GatArgs& a, const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t H, int64_t F, float slope, float p,
                      uint64_t seed) {
   memset(&a, 0, sizeof(a));
-  a.indptr = (const int32_t*)csr->indptr; a.indices = (const int32_t*)csr->indices; a.eids = (const int32_t*)csr->eids;
-  a.n_items = csr->num_rows;
-  if (plan) {
-    a.item_row = plan->item_row; a.item_beg = (const int32_t*)plan->item_beg; a.item_end = (const int32_t*)plan->item_end;
-    a.item_node = plan->item_node; a.n_items = plan->num_items;
-  }
-  a.rpb = gat_rows_per_block();
-  a.nblocks = xcd_ranges(plan, a.n_items, a.rpb, a.xcd);
+  plan_items_fill(a.plan, csr, plan, kPlanRowsPerBlock);
+  a.eids = (const int32_t*)csr->eids;
   a.H = (int)H; a.F = (int)F; a.D = (int)(H * F);
   a.gat_ld = a.D; a.small_ld = 0;  // small_ld: set by the caller (H for el, 4H for nstat, the packed stride otherwise)
   a.slope = slope; a.seed = seed;
@@ -568,11 +462,6 @@ static void gat_pack(int64_t n, int D, int S, int ld, const float* rows, const f
   int64_t b = (n * (int64_t)ld + kBlock - 1) / kBlock;
   if (b > 256 * 64) b = 256 * 64;
   hipLaunchKernelGGL(gat_pack_kernel, dim3((unsigned)(b < 1 ? 1 : b)), dim3(kBlock), 0, s, n, D, S, ld, (int)round_up(D, 4), rows, small, out);
-}
-
-static void gat_fixup(const mgx_spmm_plan* plan, int L, const float* partial, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(gat_rows_fixup_kernel, dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s,
-                     plan->hub_row, plan->hub_slot_ptr, plan->num_hubs, L, partial, out);
 }
 
 }  // namespace mgx
@@ -633,9 +522,7 @@ extern "C" int32_t mgx_gat_fused_fwd(const mgx_csr* csr, const mgx_spmm_plan* pl
   if (!gat_launch<GAT_FWD>(a, drop_p > 0.f, s)) MGX_UNSUPPORTED("mgx_gat_fused_fwd: unsupported head layout H = %lld, F = %lld", (long long)H, (long long)F);
   MGX_CHECK_LAUNCH();
   if (hubs) {
-    hipLaunchKernelGGL(gat_online_fixup_kernel, dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s,
-                       plan->hub_row, plan->hub_slot_ptr, plan->num_hubs, (int)H, (int)F, er, (const float*)a.partial,
-                       (const float*)a.partial_h, out, nstat);
+    hub_online_merge<false>(plan, (int)H, (int)F, er, a.partial, a.partial_h, out, nstat, s);
     MGX_CHECK_LAUNCH();
   }
   return MGX_OK;
@@ -679,7 +566,7 @@ extern "C" int32_t mgx_gat_fused_bwd(const mgx_csr* csc, const mgx_spmm_plan* cs
     if (!gat_launch<GAT_BWD_DST>(a, drop_p > 0.f, s)) MGX_UNSUPPORTED("mgx_gat_fused_bwd: unsupported head layout");
     MGX_CHECK_LAUNCH();
     if (hubs_dst) {
-      gat_fixup(csc_plan, (int)H, (const float*)workspace, d_er, s);
+      hub_rows_sum(csc_plan, (int)H, (const float*)workspace, d_er, s);
       MGX_CHECK_LAUNCH();
     }
   }
@@ -707,8 +594,8 @@ extern "C" int32_t mgx_gat_fused_bwd(const mgx_csr* csc, const mgx_spmm_plan* cs
     if (!gat_launch<GAT_BWD_SRC>(a, drop_p > 0.f, s)) MGX_UNSUPPORTED("mgx_gat_fused_bwd: unsupported head layout");
     MGX_CHECK_LAUNCH();
     if (hubs_src) {
-      gat_fixup(csr_plan, D, a.partial, d_feat, s);
-      gat_fixup(csr_plan, (int)H, a.partial_h, d_el, s);
+      hub_rows_sum(csr_plan, D, a.partial, d_feat, s);
+      hub_rows_sum(csr_plan, (int)H, a.partial_h, d_el, s);
       MGX_CHECK_LAUNCH();
     }
   }
@@ -749,9 +636,7 @@ extern "C" int32_t mgx_gat_tile_fwd(const mgx_csr* csr, const mgx_spmm_plan* pla
   if (!gat_tile_launch<GAT_FWD>(a, tp->nacc, drop_p > 0.f, s)) MGX_UNSUPPORTED("mgx_gat_tile_fwd: no kernel for %d rows per lane group", tp->nacc);
   MGX_CHECK_LAUNCH();
   if (hubs) {
-    hipLaunchKernelGGL(gat_online_fixup_kernel, dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)), dim3(kBlock), 0, s,
-                       plan->hub_row, plan->hub_slot_ptr, plan->num_hubs, 1, (int)F, er, (const float*)a.partial,
-                       (const float*)a.partial_h, out, nstat);
+    hub_online_merge<false>(plan, 1, (int)F, er, a.partial, a.partial_h, out, nstat, s);
     MGX_CHECK_LAUNCH();
   }
   return MGX_OK;
@@ -797,7 +682,7 @@ extern "C" int32_t mgx_gat_tile_bwd(const mgx_csr* csc, const mgx_spmm_plan* csc
     if (!gat_tile_launch<GAT_BWD_DST>(a, csc_tp->nacc, drop_p > 0.f, s)) MGX_UNSUPPORTED("mgx_gat_tile_bwd: no kernel for this tile plan");
     MGX_CHECK_LAUNCH();
     if (hubs_dst) {
-      gat_fixup(csc_plan, 1, (const float*)workspace, d_er, s);
+      hub_rows_sum(csc_plan, 1, (const float*)workspace, d_er, s);
       MGX_CHECK_LAUNCH();
     }
   }
@@ -819,8 +704,8 @@ extern "C" int32_t mgx_gat_tile_bwd(const mgx_csr* csc, const mgx_spmm_plan* csc
     if (!gat_tile_launch<GAT_BWD_SRC>(a, csr_tp->nacc, drop_p > 0.f, s)) MGX_UNSUPPORTED("mgx_gat_tile_bwd: no kernel for this tile plan");
     MGX_CHECK_LAUNCH();
     if (hubs_src) {
-      gat_fixup(csr_plan, (int)F, a.partial, d_feat, s);
-      gat_fixup(csr_plan, 1, a.partial_h, d_el, s);
+      hub_rows_sum(csr_plan, (int)F, a.partial, d_feat, s);
+      hub_rows_sum(csr_plan, 1, a.partial_h, d_el, s);
       MGX_CHECK_LAUNCH();
     }
   }

@@ -774,9 +774,9 @@ class HipBackend(object):
     def _plan_ptr(plan):
         return None if plan is None else ctypes.byref(plan.c_struct())
 
-    def _gat_ws(self, plans, H, F, dev):
-        L = _lib.lib()
-        need = max([L.mgx_gat_fused_workspace(self._plan_ptr(p), H, F) for p in plans] + [0])
+    def _plan_ws(self, workspace_fn, plans, H, F, dev):
+        """Hub-row workspace of an attention call (workspace_fn: mgx_gat_fused_workspace | mgx_dot_attention_workspace): the largest need."""
+        need = max([workspace_fn(self._plan_ptr(p), H, F) for p in plans] + [0])
         return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
 
     @staticmethod
@@ -805,7 +805,7 @@ class HipBackend(object):
         tiles = self._gat_tile_plans(csc, csr, H, F, p)
         if tiles is not None:  # dense neighbourhoods, one narrow head: the LDS-staged tile walk
             tp = tiles[0]
-            ws = self._gat_ws([tp.base], H, F, dev)
+            ws = self._plan_ws(_lib.lib().mgx_gat_fused_workspace, [tp.base], H, F, dev)
             pack = self._gat_pack_ws(csc, H, F, dev)
             with torch.cuda.device(dev), timed_call(dev, kernel="gat_fwd", form="tile", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
                 _lib.check(_lib.lib().mgx_gat_tile_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(tp.base), ctypes.byref(tp.c_struct()),
@@ -813,7 +813,7 @@ class HipBackend(object):
                                                        ctypes.c_uint64(seed), _ptr(out), _ptr(nstat), _ptr(ws), _ptr(pack), _stream(dev)))
             return out, nstat, "tile"
         plan = csc.plan()
-        ws = self._gat_ws([plan], H, F, dev)
+        ws = self._plan_ws(_lib.lib().mgx_gat_fused_workspace, [plan], H, F, dev)
         pack = self._gat_pack_ws(csc, H, F, dev)
         with torch.cuda.device(dev), timed_call(dev, kernel="gat_fwd", form="row", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
             _lib.check(_lib.lib().mgx_gat_fused_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), H, F, _ptr(feat3d), _ptr(el2d),
@@ -848,7 +848,7 @@ class HipBackend(object):
             t_dst, t_src = tiles
             if not need_src:  # the kernel's source walk is skipped when both are NULL
                 d_feat = d_el = None
-            ws = self._gat_ws([t_dst.base, t_src.base], H, F, dev)
+            ws = self._plan_ws(_lib.lib().mgx_gat_fused_workspace, [t_dst.base, t_src.base], H, F, dev)
             pack = self._gat_pack_ws(csc, H, F, dev)
             with torch.cuda.device(dev), timed_call(dev, kernel="gat_bwd", form="tile", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows,
                                                     source_walk=bool(need_src)):
@@ -859,7 +859,7 @@ class HipBackend(object):
                                                        _ptr(d_el), _ptr(d_er), _ptr(ws), _ptr(pack), _stream(dev)))
             return d_feat, d_el, d_er
         p_dst, p_src = csc.plan(), csr.plan()
-        ws = self._gat_ws([p_dst, p_src], H, F, dev)
+        ws = self._plan_ws(_lib.lib().mgx_gat_fused_workspace, [p_dst, p_src], H, F, dev)
         pack = self._gat_pack_ws(csc, H, F, dev)
         with torch.cuda.device(dev), timed_call(dev, kernel="gat_bwd", form="row", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows,
                                                 source_walk=bool(need_src)):
@@ -888,11 +888,6 @@ class HipBackend(object):
         x3d = x3d.contiguous()
         return x3d, H * F
 
-    def _dot_ws(self, plans, H, F, dev):
-        L = _lib.lib()
-        need = max([L.mgx_dot_attention_workspace(self._plan_ptr(p), H, F) for p in plans] + [0])
-        return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
-
     def dot_attention_fwd(self, csc, q3d, k3d, v3d, scale):
         """q3d [n_dst, H, F], k3d / v3d [n_src, H, F] (row-strided views are taken as they are) -> (out [n_dst, H, F],
         stat [n_dst, H, 4] = (m, 1/s, -, -))."""
@@ -904,7 +899,7 @@ class HipBackend(object):
         out = torch.empty((csc.num_rows, H, F), dtype=torch.float32, device=dev)
         stat = torch.empty((csc.num_rows, H, 4), dtype=torch.float32, device=dev)
         plan = csc.plan()
-        ws = self._dot_ws([plan], H, F, dev)
+        ws = self._plan_ws(_lib.lib().mgx_dot_attention_workspace, [plan], H, F, dev)
         with torch.cuda.device(dev), timed_call(dev, kernel="dot_attn_fwd", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
             _lib.check(_lib.lib().mgx_dot_attention_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), H, F, _ptr(q), q_ld, _ptr(k), k_ld,
                                                         _ptr(v), v_ld, ctypes.c_float(scale), _ptr(out), _ptr(stat), _ptr(ws), _stream(dev)))
@@ -923,7 +918,7 @@ class HipBackend(object):
         dk = torch.empty((csc.num_cols, H, F), dtype=torch.float32, device=dev) if need_k else None
         dv = torch.empty((csc.num_cols, H, F), dtype=torch.float32, device=dev) if need_v else None
         p_dst, p_src = csc.plan(), csr.plan()
-        ws = self._dot_ws([p_dst, p_src], H, F, dev)
+        ws = self._plan_ws(_lib.lib().mgx_dot_attention_workspace, [p_dst, p_src], H, F, dev)
         with torch.cuda.device(dev), timed_call(dev, kernel="dot_attn_bwd", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
             _lib.check(_lib.lib().mgx_dot_attention_bwd(ctypes.byref(csc.c_struct()), self._plan_ptr(p_dst), ctypes.byref(csr.c_struct()),
                                                         self._plan_ptr(p_src), H, F, _ptr(q), q_ld, _ptr(k), k_ld, _ptr(v), v_ld,

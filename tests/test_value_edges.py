@@ -530,6 +530,52 @@ def test_fused_gat_layer_masked_sources(H, F, monkeypatch):
         assert np.isfinite(out[~dead]).all() and close_rows(out[~dead], ref0["out"][~dead], ref0["out_mag"][~dead]), ("fully masked rows",) + leg
 
 
+@pytest.mark.gpu
+def test_fused_gat_nan_logit_in_a_hub_row_is_the_same_split_or_not(monkeypatch):
+    """One NaN attention term el[u, 1] on an edge of the 1000-edge row.  The row kernel's rule (fmaxf: a NaN is never the maximum;
+    1 / s = 0 unless s > 0) leaves (m finite, 1 / s = 0) in nstat for that row and head whether the row is walked whole or in hub
+    chunks merged by hub_online_merge_kernel<false>, so the backward sees the same statistics in every leg: d feat is NaN at the
+    NaN edge's source alone.  Merged under the dot-product family's rule (1 / s = NaN) the split legs would poison d feat of every
+    source of the row.  The edge sits at storage rank 300: position 44 of its 64-edge step and of its chunk at both thresholds,
+    never the first edge a lane group sees (a NaN that OPENS a stream meets m = -inf and counts for nothing, like a masked edge)."""
+    src, dst, n_src, n_dst = PRIVATE
+    H, F = 2, 8
+    deg = private_lens()
+    hub = int(np.argmax(deg))
+    assert int(deg[hub]) == 1000
+    u = int(src[np.nonzero(dst == hub)[0][300]])                            # edge-id order is storage order inside a row
+    fed = ve.fed_rows(src, dst, n_dst, [u])
+    assert np.array_equal(np.nonzero(fed)[0], [hub])
+    rng = np.random.default_rng(77)
+    feat, up = fused_operands(H, F, 78)
+    el, er = rng.standard_normal((n_src, H)).astype(np.float32), rng.standard_normal((n_dst, H)).astype(np.float32)
+    ref = ve.gat_reference(PRIVATE, el, er, SLOPE, feat, up)                # of the clean logits: the magnitudes of the bound
+    el[u, 1] = np.nan
+    want_nan = np.zeros((n_dst, H, F), bool)
+    want_nan[fed, 1] = True
+    legs = {}
+    for mode, split in (("none", 256), ("natural", 64), ("natural", 256)):
+        set_leg(monkeypatch, mode, split, "0")
+        g = graph_of(PRIVATE, torch.int32, DEV)
+        plan = g._index.csc().plan()
+        assert (plan is None) == (mode == "none") and (plan is None or plan.num_hubs == int((deg > split).sum()) >= 1)
+        assert g._index.csc().gat_tile_plan(F) is None
+        ins = [T(v, DEV).requires_grad_(True) for v in (feat, el.reshape(n_src, H, 1), er.reshape(n_dst, H, 1))]
+        out = ops.gat_fused(g, ins[0], ins[1], ins[2], SLOPE, 0.0, True)
+        out.backward(T(up, DEV))
+        got = dict(out=N(out), dfeat=N(ins[0].grad), **{"del": N(ins[1].grad).reshape(n_src, H), "der": N(ins[2].grad).reshape(n_dst, H)})
+        assert np.array_equal(np.isnan(got["out"]), want_nan) and np.isfinite(got["out"][~want_nan]).all(), ("out", mode, split)
+        legs[mode, split] = got
+    first = legs["none", 256]
+    for key, got in legs.items():
+        for name in ("out", "dfeat", "del", "der"):
+            nan = np.isnan(first[name])
+            assert np.array_equal(np.isnan(got[name]), nan), ("the NaN mask of %s depends on the hub split" % name, key, int(np.isnan(got[name]).sum()), int(nan.sum()))
+            assert np.isfinite(got[name][~nan]).all(), (name, key)
+            assert close_rows(np.where(nan, 0, got[name]), np.where(nan, 0, first[name]), ref[name + "_mag"]), (name, key)
+    assert int(np.isnan(first["dfeat"]).any(axis=(1, 2)).sum()) == 1 and np.isnan(first["dfeat"][u, 1]).all()
+
+
 # ============================================================================= 4. a non-finite source stays where the graph sends it
 _wired = {}
 
