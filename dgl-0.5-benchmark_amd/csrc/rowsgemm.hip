@@ -55,11 +55,22 @@ constexpr int rows_gemm_waves(int ks, int mt, bool v4, bool act) { return (act &
 // stage_a (dword form, A contiguous -- lda == K -- and 16-byte aligned): the 16 rows of a full tile are one aligned span of 64 K bytes;
 // it is fetched with lane-linear 16-byte loads (3 per lane at K = 47 instead of 12 dword loads of 16 bytes per row), passed through a
 // per-wave LDS area and read back as a[s] = A[row0 + c][4 s + q].  Same k <-> B pairing, same bits.
-template <int KS, int MT, bool V4, bool ACT>
+//
+// ROWS (mgx_rows_gemm_rows): a row list as an operand, `rows` = int64[n], in range (not checked).  The MFMAs of a row and their
+// order are those of ROWS == 0 on a gathered copy, so the bits are the same.
+//   kRgGather  -- row r of the product reads A[rows[r]] (the loss rows of an [N, 2K] layer buffer); the outputs stay compact.  The
+//                 ring refills a tile ahead, and an address that hangs on a load would stall it: the list entry of the tile AFTER
+//                 next is fetched before this tile's refill loads are issued, a whole tile before it becomes an address
+//   kRgScatter -- row r of the second output is stored at C2[rows[r]] (distinct rows); the first output stays compact and nothing
+//                 else of C2 is written.  A is compact, so the staged span applies as before
+// A lane whose row is beyond n reads list entry n - 1 (kRgGather) or none (kRgScatter) and stores nothing.
+constexpr int kRgGather = 1, kRgScatter = 2;
+
+template <int KS, int MT, bool V4, bool ACT, int ROWS = 0>
 __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void rows_gemm_kernel(
     int64_t n, int K, int M, const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, int b_transposed,
     const float* __restrict__ bias, const float* __restrict__ row_scale, int scale_from, float* __restrict__ C, int64_t ldc, RowsGemmAct act,
-    float* __restrict__ C2, int64_t ldc2, int split_col, int stage_a) {
+    float* __restrict__ C2, int64_t ldc2, int split_col, int stage_a, const int64_t* __restrict__ rows) {
   __shared__ float Bl[KS * MT * 64];
   __shared__ uint32_t slot_stage[ACT ? kRgWaves * 4 * 32 : 1];
   __shared__ float bias_l[MT * 16];
@@ -100,7 +111,9 @@ __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void ro
   // A lane whose row is beyond n reads row n - 1 instead: row i of A only reaches row i of C, which is not stored.  The host picked
   // KS = ceil(K / 16) * 4 (ceil(K / 4)), so only the LAST chunk (step) can reach beyond K.
   float a[KS];
-  auto row_of = [&](int64_t r) { return A + (r + c < n ? r + c : n - 1) * lda; };
+  auto list_at = [&](int64_t r) { return rows[r + c < n ? r + c : n - 1]; };  // kRgGather: this lane's source row of the tile at r
+  auto row_of = [&](int64_t r) { return A + (ROWS == kRgGather ? list_at(r) : (r + c < n ? r + c : n - 1)) * lda; };
+  int64_t next_src = 0;  // kRgGather: list_at(the wave's next tile)
   auto load_chunk = [&](const float* ap, int jj) {  // float4 form
     const int k0 = 16 * jj + 4 * q;
     const v4f v = (jj < KS / 4 - 1 || k0 < K) ? *reinterpret_cast<const v4f*>(ap + k0) : (v4f)(0.f);
@@ -119,7 +132,7 @@ __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void ro
   };
 
   // ---- epilogue: accumulator element r of tile mt = C[r0 + 4 q + r][rows_gemm_col(mt, c)]; the four tiles of a group = four consecutive columns
-  auto epilogue = [&](int64_t r0, const v4f (&acc)[MT], const float (&rs)[4]) {
+  auto epilogue = [&](int64_t r0, const v4f (&acc)[MT], const float (&rs)[4], const int64_t (&to)[4]) {
 #pragma unroll
     for (int g = 0; g < MT / 4; ++g) {
       const int m0 = 64 * g + 4 * c;
@@ -155,7 +168,7 @@ __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void ro
             over_rows += (unsigned long long)__popcll(__ballot(over && c == 0 && row < n));
           }
         } else if (row < n) {
-          float* dst = (C2 && m0 >= split_col) ? C2 + row * ldc2 + (m0 - split_col) : C + row * ldc + m0;
+          float* dst = (C2 && m0 >= split_col) ? C2 + (ROWS == kRgScatter ? to[r] : row) * ldc2 + (m0 - split_col) : C + row * ldc + m0;
           if (cvec && m0 + 3 < M) {
             v4f o; o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
             *reinterpret_cast<v4f*>(dst) = o;
@@ -172,13 +185,19 @@ __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void ro
   // ---- one tile: the MFMAs of the rows in a[], in a fixed order; `more`: each chunk of a[] is refilled from the tile at r0 + stride
   // right after its last use (a compile-time flag: a load under a run-time condition would cost a branch and a full wait per chunk)
   auto tile = [&](int64_t r0, auto more, auto&& prefetch) {
-    const float* an = more ? row_of(r0 + stride) : nullptr;
+    const float* an = !more ? nullptr : ROWS == kRgGather ? A + next_src * lda : row_of(r0 + stride);
+    if (ROWS == kRgGather && more) next_src = list_at(r0 + 2 * stride);  // ahead of the refill loads: the oldest load when it is needed
     // the row factors BEFORE the refill loads are issued: loads return in order, so a load issued after them in the epilogue would
     // have to wait for the whole next tile (the activation forms have no row factor)
     float rs[4] = {1.f, 1.f, 1.f, 1.f};
     if (!ACT && row_scale) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) rs[r] = (r0 + 4 * q + r < n) ? row_scale[r0 + 4 * q + r] : 1.f;
+    }
+    int64_t to[4] = {0, 0, 0, 0};  // kRgScatter: where the four rows of this lane's accumulators go in C2, fetched with the row factors
+    if (ROWS == kRgScatter) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) to[r] = (r0 + 4 * q + r < n) ? rows[r0 + 4 * q + r] : 0;
     }
     prefetch();
     v4f acc[MT];
@@ -212,7 +231,7 @@ __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void ro
         if (more) load_step(an, s);
       }
     }
-    epilogue(r0, acc, rs);
+    epilogue(r0, acc, rs, to);
   };
   struct Yes { constexpr operator bool() const { return true; } };
   struct No { constexpr operator bool() const { return false; } };
@@ -244,6 +263,7 @@ __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void ro
   }
   if (r0 < n) {
     load_a(r0);
+    if (ROWS == kRgGather) next_src = list_at(r0 + stride);
     for (; r0 + stride < n; r0 += stride) tile(r0, Yes{}, [] {});
     tile(r0, No{}, [] {});
   }
@@ -251,11 +271,11 @@ __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void ro
 }
 
 // workgroups of this instantiation that are resident at once on the current device (asked once)
-template <int KS, int MT, bool V4, bool ACT>
+template <int KS, int MT, bool V4, bool ACT, int ROWS = 0>
 static int64_t rows_gemm_resident_groups() {
   static const int64_t groups = [] {
     int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rows_gemm_kernel<KS, MT, V4, ACT>, kRgBlock, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, rows_gemm_kernel<KS, MT, V4, ACT, ROWS>, kRgBlock, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
     (void)hipGetLastError();
     return (int64_t)per_cu * cus;
@@ -270,20 +290,27 @@ static int64_t rows_gemm_sweep(bool act) {
   return (act ? rows_gemm_resident_groups<KS, MT, V4, true>() : rows_gemm_resident_groups<KS, MT, V4, false>()) * kRgWaves * 16;
 }
 
-template <int KS, int MT, bool V4>
+template <int KS, int MT, bool V4, int ROWS = 0>
 static void launch_rows_gemm(int64_t n, int K, int M, const float* A, int64_t lda, const float* B, int64_t ldb, int bt, const float* bias,
                              const float* rs, int scale_from, float* C, int64_t ldc, const RowsGemmAct* act, float* C2, int64_t ldc2,
-                             int split_col, hipStream_t s) {
+                             int split_col, hipStream_t s, const int64_t* rows = nullptr) {
   int64_t blocks = (n + 16 * kRgWaves - 1) / (16 * kRgWaves);
+  const int stage_a = !V4 && lda == K && (uintptr_t)A % 16 == 0;
+  if constexpr (ROWS != 0) {  // the row-list forms have no activation epilogue
+    const int64_t cap = rows_gemm_resident_groups<KS, MT, V4, false, ROWS>();
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL((rows_gemm_kernel<KS, MT, V4, false, ROWS>), dim3((unsigned)blocks), dim3(kRgBlock), 0, s, n, K, M, A, lda, B, ldb,
+                       bt, bias, rs, scale_from, C, ldc, RowsGemmAct{}, C2, ldc2, split_col, stage_a, rows);
+    return;
+  }
   const int64_t cap = rows_gemm_sweep<KS, MT, V4>(act != nullptr) / (16 * kRgWaves);
   if (blocks > cap) blocks = cap;
-  const int stage_a = !V4 && lda == K && (uintptr_t)A % 16 == 0;
   if (act) {
     hipLaunchKernelGGL((rows_gemm_kernel<KS, MT, V4, true>), dim3((unsigned)blocks), dim3(kRgBlock), 0, s, n, K, M, A, lda, B, ldb, bt, bias,
-                       rs, scale_from, C, ldc, *act, C2, ldc2, split_col, stage_a);
+                       rs, scale_from, C, ldc, *act, C2, ldc2, split_col, stage_a, rows);
   } else {
     hipLaunchKernelGGL((rows_gemm_kernel<KS, MT, V4, false>), dim3((unsigned)blocks), dim3(kRgBlock), 0, s, n, K, M, A, lda, B, ldb, bt, bias,
-                       rs, scale_from, C, ldc, RowsGemmAct{}, C2, ldc2, split_col, stage_a);
+                       rs, scale_from, C, ldc, RowsGemmAct{}, C2, ldc2, split_col, stage_a, rows);
   }
 }
 
@@ -312,6 +339,29 @@ static bool rows_gemm_dispatch(bool dry, int64_t n, int64_t K, int64_t M, const 
   return ok;
 }
 
+// the row-list forms that are built: what the last layer of a model whose loss reads a row list runs -- the gather of [N, 128] rows
+// into <= 64 columns (float4 form) and the scatter of the second 64 columns of a K = 37 .. 48 gradient (dword form); false otherwise
+static bool rows_gemm_rows_dispatch(int64_t n, int64_t K, int64_t M, const float* a, int64_t lda, const float* b, int64_t ldb, int bt,
+                                    const float* bias, const float* rs, int64_t scale_from, float* c, int64_t ldc, float* c2, int64_t ldc2,
+                                    int64_t split_col, const int64_t* a_rows, const int64_t* c2_rows, hipStream_t s) {
+  const bool v4 = K % 4 == 0 && lda % 4 == 0 && (uintptr_t)a % 16 == 0;
+  const int mt = (int)((M + 63) / 64) * 4;
+  const int ks = v4 ? (int)((K + 15) / 16) * 4 : (int)((K + 3) / 4);
+#define MGX_RGR(KS_, MT_, V4_, ROWS_, LIST_)                                                                                             \
+  if (ks == KS_ && mt == MT_ && v4 == V4_) {                                                                                             \
+    launch_rows_gemm<KS_, MT_, V4_, ROWS_>(n, (int)K, (int)M, a, lda, b, ldb, bt, bias, rs, (int)scale_from, c, ldc, nullptr, c2, ldc2,   \
+                                           (int)split_col, s, LIST_);                                                                    \
+    return true;                                                                                                                         \
+  }
+  if (a_rows && !c2_rows) {
+    MGX_RGR(32, 4, true, kRgGather, a_rows)
+  } else if (c2_rows && !a_rows && c2) {
+    MGX_RGR(12, 8, false, kRgScatter, c2_rows) MGX_RGR(11, 8, false, kRgScatter, c2_rows) MGX_RGR(10, 8, false, kRgScatter, c2_rows)
+  }
+#undef MGX_RGR
+  return false;
+}
+
 }  // namespace mgx
 
 extern "C" int32_t mgx_rows_gemm(int64_t n, int64_t K, int64_t M, const float* a, int64_t lda, const float* b, int64_t ldb,
@@ -329,6 +379,29 @@ extern "C" int32_t mgx_rows_gemm(int64_t n, int64_t K, int64_t M, const float* a
   if (!rows_gemm_dispatch(false, n, K, M, a, lda, b, ldb, b_transposed, bias, row_scale, scale_from, c, ldc, nullptr, (hipStream_t)stream, c2, ldc2,
                           split_col))
     MGX_UNSUPPORTED("mgx_rows_gemm: no kernel for K = %lld, M = %lld", (long long)K, (long long)M);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int32_t mgx_rows_gemm_rows(int64_t n, int64_t K, int64_t M, const float* a, int64_t lda, const int64_t* a_rows, const float* b,
+                                      int64_t ldb, int32_t b_transposed, const float* bias, const float* row_scale, int64_t scale_from,
+                                      float* c, int64_t ldc, float* c2, int64_t ldc2, int64_t split_col, const int64_t* c2_rows,
+                                      void* stream) {
+  using namespace mgx;
+  if (!a_rows && !c2_rows)
+    return mgx_rows_gemm(n, K, M, a, lda, b, ldb, b_transposed, bias, row_scale, scale_from, c, ldc, c2, ldc2, split_col, stream);
+  MGX_ENTER();
+  MGX_CHECK_ARG(n >= 0 && K >= 1 && M >= 1, "mgx_rows_gemm_rows: bad sizes");
+  MGX_CHECK_ARG(!c2_rows || c2, "mgx_rows_gemm_rows: c2_rows without a second output");
+  if (n == 0) return MGX_OK;
+  MGX_CHECK_ARG(a && b && c, "mgx_rows_gemm_rows: NULL pointer");
+  MGX_CHECK_ARG(lda >= K && ldc >= (c2 ? split_col : M) && ldb >= (b_transposed ? K : M), "mgx_rows_gemm_rows: leading dimensions smaller than the operands");
+  MGX_CHECK_ARG(!c2 || (split_col > 0 && split_col < M && split_col % 4 == 0 && ldc2 >= M - split_col),
+                "mgx_rows_gemm_rows: a second output needs 0 < split_col < M, split_col % 4 == 0, ldc2 >= M - split_col");
+  MGX_CHECK_ARG(scale_from >= 0 && scale_from <= M, "mgx_rows_gemm_rows: scale_from outside [0, M]");
+  if (!rows_gemm_rows_dispatch(n, K, M, a, lda, b, ldb, b_transposed, bias, row_scale, scale_from, c, ldc, c2, ldc2, split_col, a_rows,
+                               c2_rows, (hipStream_t)stream))
+    MGX_UNSUPPORTED("mgx_rows_gemm_rows: no row-list kernel for K = %lld, M = %lld", (long long)K, (long long)M);
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }

@@ -76,10 +76,20 @@ __global__ __launch_bounds__(kBlock) void xty_partial_kernel(int64_t n, int M, i
 // column 4c + t.  Per operand: VG groups of 64 columns by float4 loads (VG * 4 tiles) + ST tiles of 16 columns by dword loads for the
 // remainder (K = 72 = one group + one tile) or for an operand whose row stride is not a multiple of 4 floats (the 47-column output
 // gradient).  Same accumulators, same partial layout, same finish kernel; fp32 MFMA, sums in another (fixed) order.
-template <int AVG, int AST, int BVG, int BST>
+// ROWS (mgx_xty_rows): row r of B is B[b_rows[r]] -- the loss rows of an [N, 2K] layer buffer against their compact output gradient;
+// int64[n], in range (not checked).  Same rows per wave, same MFMAs in the same order as ROWS = false on a gathered copy: same bits.
+// A row beyond n reads no list entry.
+// ROWS = kXtyAPos (mgx_xty_colsum_pos): the reduction runs over all n rows of B, but A exists on some of them only: row r pairs
+// A[b_rows[r]] with B[r], and b_rows[r] < 0 stands for a ZERO row of A, which is neither read nor multiplied (B[r] is not read either).
+// Adding the products of a zero row leaves an accumulator as it is, so the bits are those of ROWS = 0 on A scattered into a zero
+// [n, M] matrix -- same rows per wave, same place of every row in its MFMA; a step of four rows without any row of A is skipped.
+// (For FINITE B: an Inf or NaN in a row of B that meets a zero row of A gives NaN in that product and is not even read here.)
+constexpr int kXtyBRows = 1, kXtyAPos = 2;
+template <int AVG, int AST, int BVG, int BST, int ROWS = 0>
 __global__ __launch_bounds__(kBlock) void xty_partial_v4_kernel(int64_t n, int M, int K, int mt16, int kt16, const float* __restrict__ A,
                                                                 int64_t lda, const float* __restrict__ B, int64_t ldb,
-                                                                float* __restrict__ part, float* __restrict__ part_sum) {
+                                                                float* __restrict__ part, float* __restrict__ part_sum,
+                                                                const int64_t* __restrict__ b_rows) {
   // part_sum (may be NULL): the COLUMN SUMS of A as well -- the bias gradient that goes with this weight gradient -- as the product with
   // one more B column of ones: four MFMAs per 16 rows instead of another pass over A (mgx_column_sum: 0.08 - 0.11 ms at N = 2.45 M)
   constexpr int AT = AVG * 4 + AST, BT = BVG * 4 + BST;
@@ -96,38 +106,61 @@ __global__ __launch_bounds__(kBlock) void xty_partial_v4_kernel(int64_t n, int M
   }
   const float one = c == 0 ? 1.f : 0.f;  // B column 0 of the extra tile is all ones, the other fifteen zero
   const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * 16;
+  // kXtyAPos: the operand addresses hang on the map, so a tile's four entries are fetched a tile ahead (one round trip per tile, not two)
+  int64_t ahead[4] = {-1, -1, -1, -1};
+  auto pos_of = [&](int64_t r, int s) { return r + s * 4 + q < n ? b_rows[r + s * 4 + q] : (int64_t)-1; };
+  if (ROWS == kXtyAPos) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) ahead[s] = pos_of(gw * 16, s);
+  }
   for (int64_t r0 = gw * 16; r0 < n; r0 += stride) {
     float a[4][AT > 0 ? AT : 1], b[4][BT > 0 ? BT : 1];
+    bool live[4] = {true, true, true, true};  // kXtyAPos, wave-uniform: some row of this step has a row of A
+    int64_t here[4] = {0, 0, 0, 0};
+    if (ROWS == kXtyAPos) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        here[s] = ahead[s];
+        ahead[s] = pos_of(r0 + stride, s);
+      }
+    }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       const int64_t row = r0 + s * 4 + q;
-      const bool ok = row < n;
+      const int64_t listed = ROWS == kXtyAPos ? here[s] : ROWS ? (row < n ? b_rows[row] : 0) : row;
+      const bool ok = row < n && (ROWS != kXtyAPos || listed >= 0);
+      const int64_t brow = ROWS == kXtyBRows ? listed : row, arow = ROWS == kXtyAPos ? listed : row;
+      if (ROWS == kXtyAPos) live[s] = __ballot(ok) != 0;
 #pragma unroll
       for (int g = 0; g < AVG; ++g) {
-        const v4f v = (ok && g * 64 + 4 * c + 3 < M) ? *reinterpret_cast<const v4f*>(A + row * lda + g * 64 + 4 * c) : (v4f)(0.f);
+        const v4f v = (ok && g * 64 + 4 * c + 3 < M) ? *reinterpret_cast<const v4f*>(A + arow * lda + g * 64 + 4 * c) : (v4f)(0.f);
         a[s][g * 4 + 0] = v.x; a[s][g * 4 + 1] = v.y; a[s][g * 4 + 2] = v.z; a[s][g * 4 + 3] = v.w;
       }
 #pragma unroll
-      for (int i = 0; i < AST; ++i) a[s][AVG * 4 + i] = (ok && AVG * 64 + i * 16 + c < M) ? A[row * lda + AVG * 64 + i * 16 + c] : 0.f;
+      for (int i = 0; i < AST; ++i) a[s][AVG * 4 + i] = (ok && AVG * 64 + i * 16 + c < M) ? A[arow * lda + AVG * 64 + i * 16 + c] : 0.f;
 #pragma unroll
       for (int g = 0; g < BVG; ++g) {
-        const v4f v = (ok && g * 64 + 4 * c + 3 < K) ? *reinterpret_cast<const v4f*>(B + row * ldb + g * 64 + 4 * c) : (v4f)(0.f);
+        const v4f v = (ok && g * 64 + 4 * c + 3 < K) ? *reinterpret_cast<const v4f*>(B + brow * ldb + g * 64 + 4 * c) : (v4f)(0.f);
         b[s][g * 4 + 0] = v.x; b[s][g * 4 + 1] = v.y; b[s][g * 4 + 2] = v.z; b[s][g * 4 + 3] = v.w;
       }
 #pragma unroll
-      for (int j = 0; j < BST; ++j) b[s][BVG * 4 + j] = (ok && BVG * 64 + j * 16 + c < K) ? B[row * ldb + BVG * 64 + j * 16 + c] : 0.f;
+      for (int j = 0; j < BST; ++j) b[s][BVG * 4 + j] = (ok && BVG * 64 + j * 16 + c < K) ? B[brow * ldb + BVG * 64 + j * 16 + c] : 0.f;
     }
 #pragma unroll
     for (int s = 0; s < 4; ++s)
+      if (ROWS != kXtyAPos || live[s]) {
 #pragma unroll
-      for (int i = 0; i < AT; ++i)
+        for (int i = 0; i < AT; ++i)
 #pragma unroll
-        for (int j = 0; j < BT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s][i], b[s][j], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < BT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s][i], b[s][j], acc[i][j], 0, 0, 0);
+      }
     if (part_sum) {
 #pragma unroll
       for (int s = 0; s < 4; ++s)
+        if (ROWS != kXtyAPos || live[s]) {
 #pragma unroll
-        for (int i = 0; i < AT; ++i) accs[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s][i], (r0 + s * 4 + q < n) ? one : 0.f, accs[i], 0, 0, 0);
+          for (int i = 0; i < AT; ++i) accs[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s][i], (r0 + s * 4 + q < n) ? one : 0.f, accs[i], 0, 0, 0);
+        }
     }
   }
   if (part_sum && c == 0) {  // lane (0, q) holds the sums of the real columns behind (tile i, index 4 q + r): one [mt16] vector per wave
@@ -158,8 +191,20 @@ __global__ __launch_bounds__(kBlock) void xty_partial_v4_kernel(int64_t n, int M
 
 template <int AVG, int AST>
 static bool launch_xty_v4_b(int bvg, int bst, int waves, int64_t n, int M, int K, int mt16, int kt16, const float* A, int64_t lda,
-                            const float* B, int64_t ldb, float* part, float* part_sum, hipStream_t s) {
-#define MGX_XTY4(G, T) if (bvg == G && bst == T) { hipLaunchKernelGGL((xty_partial_v4_kernel<AVG, AST, G, T>), dim3(waves / kWavesPerBlock), dim3(kBlock), 0, s, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum); return true; }
+                            const float* B, int64_t ldb, float* part, float* part_sum, hipStream_t s, const int64_t* b_rows, int mode) {
+  if (b_rows && mode == kXtyAPos) {
+#define MGX_XTY4P(G) if (AVG == 0 && AST == 3 && bvg == G && bst == 0) { hipLaunchKernelGGL((xty_partial_v4_kernel<0, 3, G, 0, kXtyAPos>), dim3(waves / kWavesPerBlock), dim3(kBlock), 0, s, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, b_rows); return true; }
+    MGX_XTY4P(2) MGX_XTY4P(1)
+#undef MGX_XTY4P
+    return false;
+  }
+  if (b_rows) {  // the row-list forms that are built: a dword-loaded A (the 47-column output gradient) against 128 or 64 float4 columns
+#define MGX_XTY4R(G) if (AVG == 0 && AST == 3 && bvg == G && bst == 0) { hipLaunchKernelGGL((xty_partial_v4_kernel<0, 3, G, 0, kXtyBRows>), dim3(waves / kWavesPerBlock), dim3(kBlock), 0, s, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, b_rows); return true; }
+    MGX_XTY4R(2) MGX_XTY4R(1)
+#undef MGX_XTY4R
+    return false;
+  }
+#define MGX_XTY4(G, T) if (bvg == G && bst == T) { hipLaunchKernelGGL((xty_partial_v4_kernel<AVG, AST, G, T>), dim3(waves / kWavesPerBlock), dim3(kBlock), 0, s, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, b_rows); return true; }
   MGX_XTY4(2, 0) MGX_XTY4(1, 0) MGX_XTY4(1, 1) MGX_XTY4(1, 2) MGX_XTY4(1, 3) MGX_XTY4(1, 4)
 #undef MGX_XTY4
   return false;
@@ -167,18 +212,18 @@ static bool launch_xty_v4_b(int bvg, int bst, int waves, int64_t n, int M, int K
 
 // 16-byte loads for the operand(s) that allow it; false = use the dword kernels above
 static bool launch_xty_v4(int mt, int kt, int waves, int64_t n, int M, int K, const float* A, int64_t lda, const float* B, int64_t ldb,
-                          float* part, float* part_sum, hipStream_t s) {
+                          float* part, float* part_sum, hipStream_t s, const int64_t* b_rows = nullptr, int mode = 0) {
   const bool bvec = ldb % 4 == 0 && (uintptr_t)B % 16 == 0 && K % 4 == 0 && K >= 64;
   if (!bvec) return false;
   const int bvg = K >= 128 ? 2 : 1, bst = (K - bvg * 64 + 15) / 16;
-  const bool avec = lda % 4 == 0 && (uintptr_t)A % 16 == 0 && M == 64;
+  const bool avec = lda % 4 == 0 && (uintptr_t)A % 16 == 0 && M == 64 && !b_rows;
   const int mt16 = mt * 16, kt16 = kt * 16;
-  if (avec) return launch_xty_v4_b<1, 0>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s);
+  if (avec) return launch_xty_v4_b<1, 0>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s, b_rows, mode);
   switch (mt) {
-    case 1: return launch_xty_v4_b<0, 1>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s);
-    case 2: return launch_xty_v4_b<0, 2>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s);
-    case 3: return launch_xty_v4_b<0, 3>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s);
-    default: return launch_xty_v4_b<0, 4>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s);
+    case 1: return launch_xty_v4_b<0, 1>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s, b_rows, mode);
+    case 2: return launch_xty_v4_b<0, 2>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s, b_rows, mode);
+    case 3: return launch_xty_v4_b<0, 3>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s, b_rows, mode);
+    default: return launch_xty_v4_b<0, 4>(bvg, bst, waves, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, s, b_rows, mode);
   }
 }
 
@@ -338,7 +383,7 @@ extern "C" int64_t mgx_xty_workspace(int64_t M, int64_t K) {
 }
 
 static int32_t xty_impl(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int64_t ldc,
-                        float* colsum, void* workspace, void* stream);
+                        float* colsum, void* workspace, void* stream, const int64_t* b_rows = nullptr, int mode = 0);
 
 extern "C" int32_t mgx_xty(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out,
                            int64_t ldc, void* workspace, void* stream) {
@@ -351,8 +396,24 @@ extern "C" int32_t mgx_xty_colsum(int64_t n, int64_t M, int64_t K, const float* 
   return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream);
 }
 
+extern "C" int32_t mgx_xty_rows(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb,
+                                const int64_t* b_rows, float* out, int64_t ldc, void* workspace, void* stream) {
+  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, nullptr, workspace, stream, b_rows, b_rows ? mgx::kXtyBRows : 0);
+}
+
+extern "C" int32_t mgx_xty_colsum_rows(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb,
+                                       const int64_t* b_rows, float* out, int64_t ldc, float* colsum, void* workspace, void* stream) {
+  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream, b_rows, b_rows ? mgx::kXtyBRows : 0);
+}
+
+extern "C" int32_t mgx_xty_colsum_pos(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const int64_t* a_pos, const float* b,
+                                      int64_t ldb, float* out, int64_t ldc, float* colsum, void* workspace, void* stream) {
+  if (!a_pos) return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream);
+  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream, a_pos, mgx::kXtyAPos);
+}
+
 static int32_t xty_impl(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int64_t ldc,
-                        float* colsum, void* workspace, void* stream) {
+                        float* colsum, void* workspace, void* stream, const int64_t* b_rows, int mode) {
   using namespace mgx;
   MGX_ENTER();
   MGX_CHECK_ARG(n >= 0 && M >= 1 && K >= 1, "mgx_xty: bad sizes");
@@ -369,6 +430,7 @@ static int32_t xty_impl(int64_t n, int64_t M, int64_t K, const float* a, int64_t
   }
   MGX_CHECK_ARG(a && b && workspace, "mgx_xty: NULL pointer");
   float* part = (float*)workspace;
+  if (b_rows && (mt > 4 || kt > 8)) MGX_UNSUPPORTED("mgx_xty_rows: one 64 x 128 tile only");
   if (mt > 4 || kt > 8) {
     if (colsum) MGX_UNSUPPORTED("mgx_xty_colsum: one 64 x 128 tile only");
     const int tiles_m = (int)((M + kXtyTileM - 1) / kXtyTileM), tiles_k = (int)((K + kXtyTileK - 1) / kXtyTileK);
@@ -388,7 +450,8 @@ static int32_t xty_impl(int64_t n, int64_t M, int64_t K, const float* a, int64_t
   }
   const int waves = xty_waves(n);
   float* part_sum = colsum ? part + (int64_t)kXtyWaves * mt * 16 * kt * 16 : nullptr;
-  bool ok = launch_xty_v4(mt, kt, waves, n, (int)M, (int)K, a, lda, b, ldb, part, part_sum, s);
+  bool ok = launch_xty_v4(mt, kt, waves, n, (int)M, (int)K, a, lda, b, ldb, part, part_sum, s, b_rows, mode);
+  if (!ok && b_rows) MGX_UNSUPPORTED("mgx_xty_rows: no row-list kernel for %lld x %lld", (long long)M, (long long)K);
   if (!ok && colsum) MGX_UNSUPPORTED("mgx_xty_colsum: needs the 16-byte-load form (B: K %% 4 == 0, K >= 64, aligned)");
   if (!ok) switch (mt) {
     case 1: ok = launch_xty_kt<1>(kt, waves, n, (int)M, (int)K, a, lda, b, ldb, part, s); break;

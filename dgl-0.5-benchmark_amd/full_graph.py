@@ -153,8 +153,9 @@ class GraphSAGE(nn.Module):
                     cat = None
         last = self.layers[-1]
         if rows is not None and self.rows_are_distinct and not self.plain and last.fc_self.bias is None:
-            # opt-in (MGX_SAGE_SPARSE_LAST=1): the last layer and the row selection as one node whose backward knows that the
-            # output gradient is zero outside the loss rows
+            # the last layer and the row selection as one node that projects, differentiates and reduces over the loss rows only
+            # (ops.SageMeanCatHeadFn; MGX_SAGE_HEAD_ROWS=0: the layer over all rows, then the selection).  Opt-in
+            # MGX_SAGE_SPARSE_LAST=1: its backward aggregation also skips the gathers of rows whose gradient is zero
             y = ops.sage_mean_layer_rows(g, x, last.fc_self.weight, last.fc_neigh.weight, last.fc_neigh.bias, cat, rows)
             if y is not None:
                 return y.log_softmax(dim=-1)

@@ -102,6 +102,10 @@ SIGNATURES = {
     "mgx_xty": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _vp, _vp]),
     "mgx_xty_colsum": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _vp, _vp]),
     "mgx_rows_gemm": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _i32, _fp, _fp, _i64, _fp, _i64, _fp, _i64, _i64, _vp]),
+    "mgx_xty_rows": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _vp, _fp, _i64, _vp, _vp]),
+    "mgx_xty_colsum_rows": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _vp, _fp, _i64, _fp, _vp, _vp]),
+    "mgx_xty_colsum_pos": (_i32, [_i64, _i64, _i64, _fp, _i64, _vp, _fp, _i64, _fp, _i64, _fp, _vp, _vp]),
+    "mgx_rows_gemm_rows": (_i32, [_i64, _i64, _i64, _fp, _i64, _vp, _fp, _i64, _i32, _fp, _fp, _i64, _fp, _i64, _fp, _i64, _i64, _vp, _vp]),
     "mgx_rows_gemm_supported": (_i32, [_i64, _i64, _i64]),
     "mgx_rows_gemm_sweep_rows": (_i64, [_i64, _i64, _i64, _i32]),
     "mgx_rows_gemm_relu_dropout": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _i32, _fp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,

@@ -2,7 +2,7 @@
 
 USER switches are environment variables, read where they are used; the complete list is the table in README.md ("Switches"):
     MGX_LIB_PATH  MGX_DATA_ROOT  MGX_CACHE_DIR  MGX_SCHEDULE  MGX_TILE  MGX_GAT_TILE  MGX_GAT_FUSED  MGX_TORCH_OPS  MGX_SDDMM_WALK
-    MGX_SPARSE_HALO  MGX_ACCELERATE_LINEAR  MGX_SAGE_SPARSE_LAST  MGX_SAGE_L1_PROJECT_FIRST  MGX_PLAIN_MODEL  MGX_HOST_THREADS
+    MGX_SPARSE_HALO  MGX_ACCELERATE_LINEAR  MGX_SAGE_SPARSE_LAST  MGX_SAGE_HEAD_ROWS  MGX_SAGE_L1_PROJECT_FIRST  MGX_PLAIN_MODEL  MGX_HOST_THREADS
 (+ the bench / test hooks MGX_DIST_BACKEND, MGX_BENCH_SHARE_GPU, MGX_BENCH_TUNABLEOP, MGX_BENCH_STEP_TIMES, MGX_DATASET_SCALE).
 
 Everything below is NOT a user switch: module attributes with fixed defaults that choose between a fused form and the composition it
@@ -19,6 +19,7 @@ SAGE_STATIC_CAT = True     # an unmodified input tensor stays resident in that b
 SAGE_FUSED_ADD = True      # fc_self(h) + fc_neigh(neigh) as two GEMMs, the second accumulating (ops.linear_sum)
 SAGE_FUSED_ACT = True      # relu + dropout in the layer GEMM's epilogue (mgx_rows_gemm_relu_dropout)
 SAGE_PROJECT_FIRST = True  # project before aggregating when that moves fewer columns (reddit: 602 -> 16)
+SAGE_HEAD_ROWS = True      # the last layer's dense work on the loss rows only (ops.SageMeanCatHeadFn; MGX_SAGE_HEAD_ROWS=0 turns it off)
 ROWS_GEMM = True           # mgx_rows_gemm for the projections of a layer over >= 65 536 rows (else the library GEMM)
 LINEAR_XTY = True          # tall-skinny weight gradients by mgx_xty (else the library GEMM)
 XTY_COLSUM = True          # ... with the bias gradient from the same pass (mgx_xty_colsum)

@@ -977,6 +977,29 @@ def _rows_linear(be, x2d, weight, bias):
     return torch.nn.functional.linear(x2d, weight, bias)
 
 
+def _cat_aggregate(be, gidx, cat, h):
+    """The forward aggregation of a layer over a CatBuffer: h into the left half (unless it lives there or is the resident input), its
+    mean over the in-edges into the right half, every row."""
+    csc = gidx.csc()
+    if not cat.holds(h):
+        # a layer input that lives elsewhere -- the model's input features -- is copied into the left half; when it is the
+        # SAME tensor object, unmodified (version counter), as in the previous pass the copy is skipped.  The buffer keeps
+        # a reference to that tensor: a per-step temporary at a recycled address is a different object and is copied.
+        same = cat.static_key is not None and cat.static_key[0] is h and cat.static_key[1] == h._version
+        if not same or h.requires_grad or not config.SAGE_STATIC_CAT:
+            cat.left.copy_(h)
+            cat.static_key = None if h.requires_grad else (h, h._version)
+    cat.generation += 1
+    tail_ops = _edge_tail_operands(be, csc, cat, h)
+    if tail_ops is not None:
+        # the constant 100-column input: columns 0 .. 95 as a compact block (three cache lines per row instead of four and an eighth),
+        # the last four laid out along the edge list -- once, for as long as the tensor is not written to
+        be.spmm_copy_u_edge_tail(csc, "mean", tail_ops[0], tail_ops[1], cat.right)
+    else:
+        # a relu + dropout output (a hidden layer's input) is gathered as 128-byte slots, one cache line per edge instead of two
+        be.spmm_copy_u_strided(csc, "mean", cat.left, cat.right, slots=_packed_rows(be, gidx, csc, h, cat.left))
+
+
 class SageMeanCatFn(torch.autograd.Function):
     """SageMeanLayerFn over a CatBuffer: the aggregation reads the left half and writes the right half in place
     (mgx_spmm_copy_u_strided), forward and weight gradients are ONE GEMM / ONE mgx_xty against the stacked weights, and the
@@ -984,25 +1007,8 @@ class SageMeanCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gidx, cat, h, w_self, w_neigh, bias, act=None):
-        csc = gidx.csc()
         be = sparse.backend_for(h)
-        if not cat.holds(h):
-            # a layer input that lives elsewhere -- the model's input features -- is copied into the left half; when it is the
-            # SAME tensor object, unmodified (version counter), as in the previous pass the copy is skipped.  The buffer keeps
-            # a reference to that tensor: a per-step temporary at a recycled address is a different object and is copied.
-            same = cat.static_key is not None and cat.static_key[0] is h and cat.static_key[1] == h._version
-            if not same or h.requires_grad or not config.SAGE_STATIC_CAT:
-                cat.left.copy_(h)
-                cat.static_key = None if h.requires_grad else (h, h._version)
-        cat.generation += 1
-        tail_ops = _edge_tail_operands(be, csc, cat, h)
-        if tail_ops is not None:
-            # the constant 100-column input: columns 0 .. 95 as a compact block (three cache lines per row instead of four and an eighth),
-            # the last four laid out along the edge list -- once, for as long as the tensor is not written to
-            be.spmm_copy_u_edge_tail(csc, "mean", tail_ops[0], tail_ops[1], cat.right)
-        else:
-            # a relu + dropout output (a hidden layer's input) is gathered as 128-byte slots, one cache line per edge instead of two
-            be.spmm_copy_u_strided(csc, "mean", cat.left, cat.right, slots=_packed_rows(be, gidx, csc, h, cat.left))
+        _cat_aggregate(be, gidx, cat, h)
         ctx.gidx, ctx.cat, ctx.generation = gidx, cat, cat.generation
         if act is not None:
             # relu + dropout in the GEMM's epilogue (mgx_rows_gemm_relu_dropout): the activation lands in the next layer's buffer and
@@ -1090,41 +1096,114 @@ class SageMeanCatFn(torch.autograd.Function):
         return None, None, dh, dws, dwn, db, None
 
 
-_ROW_BITS = {}  # (rows.data_ptr(), len, N) -> (rows, bitmap): the loss rows of a training run are one tensor, reused every step
+_ROW_BITS = {}  # (rows.data_ptr(), len, N) -> (rows, version, bitmap): the loss rows of a training run are one tensor, reused every step
+# (this and the two caches below hold what was derived from a row list: same tensor object AND same version counter, so a list written
+# in place is derived again; a write behind autograd's back -- `.data`, a raw kernel -- is not seen: do not change a row list that way)
 
 
 def _row_bits(rows, n, be):
     key = (rows.data_ptr(), int(rows.shape[0]), int(n))
     held = _ROW_BITS.get(key)
-    if held is None or held[0] is not rows:
+    if held is None or held[0] is not rows or held[1] != rows._version:
         flag = torch.zeros((n, 4), dtype=torch.float32, device=rows.device)
         flag[rows] = 1.0
         if len(_ROW_BITS) > 8:
             _ROW_BITS.clear()
-        held = _ROW_BITS[key] = (rows, be.row_nonzero_bits(flag))
+        held = _ROW_BITS[key] = (rows, rows._version, be.row_nonzero_bits(flag))
+    return held[2]
+
+
+_ROW_INV_DEG = {}  # (rows.data_ptr(), len, inv_deg.data_ptr()) -> (rows, inv_deg, inv_deg[rows]): one gather per row list, not per step
+
+
+def _row_inv_deg(rows, inv_deg):
+    key = (rows.data_ptr(), int(rows.shape[0]), inv_deg.data_ptr())
+    held = _ROW_INV_DEG.get(key)
+    if held is None or held[0] is not rows or held[1] is not inv_deg or held[3] != rows._version:
+        if len(_ROW_INV_DEG) > 8:
+            _ROW_INV_DEG.clear()
+        held = _ROW_INV_DEG[key] = (rows, inv_deg, inv_deg.index_select(0, rows), rows._version)
+    return held[2]
+
+
+_ROW_POS = {}  # (rows.data_ptr(), len, N) -> (rows, int64 [N]: the place of a node in `rows`, -1 outside)
+
+
+def _row_pos(rows, n):
+    key = (rows.data_ptr(), int(rows.shape[0]), int(n))
+    held = _ROW_POS.get(key)
+    if held is None or held[0] is not rows or held[2] != rows._version:
+        pos = torch.full((n,), -1, dtype=torch.int64, device=rows.device)
+        pos[rows] = torch.arange(rows.shape[0], dtype=torch.int64, device=rows.device)
+        if len(_ROW_POS) > 8:
+            _ROW_POS.clear()
+        held = _ROW_POS[key] = (rows, pos, rows._version)
     return held[1]
 
 
-class SageMeanCatRowsFn(torch.autograd.Function):
+def _head_rows_forward(be, gidx, cat, h, w_self, w_neigh, bias, rows):
+    """[h | mean_agg(h)][rows] x [W_self | W_neigh]^T + bias -> [R, out]: every row aggregated (the right half of the buffer fully
+    written: the weight gradient and every later reader see what SageMeanCatFn leaves), the listed rows projected -- read in place by
+    mgx_rows_gemm_rows where it has the shape, else gathered for the library GEMM."""
+    _cat_aggregate(be, gidx, cat, h)
+    wcat = torch.cat([w_self, w_neigh], dim=1)
+    y = be.rows_gemm(cat.buf, wcat, b_transposed=True, bias=bias, rows=rows) if config.ROWS_GEMM else None
+    if y is None:
+        y = torch.nn.functional.linear(cat.buf.index_select(0, rows), wcat, bias)
+    return y
+
+
+def _head_rows_dense_backward(be, gidx, cat, w_self, w_neigh, dyr, rows, need_dh, need_w, need_b, zero_fill):
+    """The dense half of the backward of _head_rows_forward from dyr [R, out], all of it on the R listed rows:
+    (d_self [R, K] compact, dn [N, K] = d neigh / deg on the listed rows -- the other rows zero (zero_fill) or unwritten --, dW_self,
+    dW_neigh, db).  The weight gradient reads the listed rows of the buffer in place (mgx_xty_colsum_rows)."""
+    K, n = cat.K, cat.buf.shape[0]
+    d_self = dn = dws = dwn = db = None
+    if need_dh:
+        wcat = torch.cat([w_self, w_neigh], dim=1)  # [out, 2K]
+        dn = (torch.zeros if zero_fill else torch.empty)((n, K), dtype=dyr.dtype, device=dyr.device)
+        inv_r = _row_inv_deg(rows, gidx.csc().inv_degrees())
+        pair = None
+        if config.ROWS_GEMM and K % 4 == 0:
+            pair = be.rows_gemm(dyr, wcat, row_scale=inv_r, scale_from=K, split_col=K, scatter_rows=rows, out2=dn)
+        if pair is None:
+            dcat = dyr @ wcat
+            dn.index_copy_(0, rows, dcat[:, K:] * inv_r.view(-1, 1))
+            d_self = dcat[:, :K]
+        else:
+            d_self = pair[0]
+    if need_w:
+        # over the listed rows, but summed as the layer over all rows sums them (mgx_xty_colsum_pos): a training run then stays on the
+        # bits of that layer -- sums of the listed rows alone in their own order (mgx_xty_rows) differ in the last place, and Adam on
+        # gradients near zero turns that into visibly different runs after a few steps
+        res = be.xty_pos(dyr, _row_pos(rows, n), cat.buf, colsum=need_b) if n >= be.XTY_MIN_ROWS and config.LINEAR_XTY and config.XTY_COLSUM else None
+        if res is None:
+            dy = torch.zeros((n, dyr.shape[1]), dtype=dyr.dtype, device=dyr.device).index_copy_(0, rows, dyr)
+            res = _weight_bias_grad(dy, cat.buf) if need_b else _weight_grad(dy, cat.buf)
+        dw, db = res if need_b else (res, None)
+        dws, dwn = dw[:, :K].contiguous(), dw[:, K:].contiguous()
+    elif need_b:
+        db = be.column_sum(dyr)
+    return d_self, dn, dws, dwn, db
+
+
+class SageMeanCatHeadFn(torch.autograd.Function):
     """SageMeanCatFn followed by the selection of DISTINCT output rows -- the loss rows, `model(g, feats)[train_idx]` at
-    main_dgl_product_sage.py:105 -- as one node (MGX_SAGE_SPARSE_LAST=1; off by default).  The forward is the whole layer, every row
-    aggregated and projected as the reference does; the backward uses what the selection implies: d y is zero outside `rows` (92 % of
-    the rows of ogbn-products), so the dense gradients are formed on those rows only and the reversed aggregation skips the gathers
-    of rows that are zero by construction (mgx_spmm_copy_u_masked with a bitmap of `rows`; they are never even written).  Exact."""
+    main_dgl_product_sage.py:105 -- as one node that does the layer's DENSE work on those rows only (config.SAGE_HEAD_ROWS, the
+    default): the projection, its input gradient and the weight / bias gradients run over the R listed rows through the row-list
+    operands of mgx_rows_gemm_rows and the position map of mgx_xty_colsum_pos instead of over all N rows, of which the loss reads 8 % on ogbn-products.
+    Both aggregations are untouched: every row is aggregated forward, and the reversed one gathers every source row over every edge
+    from d neigh / deg, which is zero outside the rows (a zero-filled [N, K] the GEMM scatters into), accumulating into d self.
+    Every sum is formed in the order the layer over all rows forms it, so the gradients are that layer's bit for bit.  No atomics,
+    no host synchronisation."""
 
     @staticmethod
     def forward(ctx, gidx, cat, h, w_self, w_neigh, bias, rows):
-        csc = gidx.csc()
         be = sparse.backend_for(h)
-        if not cat.holds(h):
-            cat.left.copy_(h)
-            cat.static_key = None
-        cat.generation += 1
-        be.spmm_copy_u_strided(csc, "mean", cat.left, cat.right)
+        y = _head_rows_forward(be, gidx, cat, h, w_self, w_neigh, bias, rows)
         ctx.gidx, ctx.cat, ctx.generation, ctx.rows = gidx, cat, cat.generation, rows
         ctx.save_for_backward(w_self, w_neigh)
-        y = torch.nn.functional.linear(cat.buf, torch.cat([w_self, w_neigh], dim=1), bias)
-        return y.index_select(0, rows)
+        return y
 
     @staticmethod
     @once_differentiable
@@ -1136,30 +1215,69 @@ class SageMeanCatRowsFn(torch.autograd.Function):
         dyr = dyr.contiguous()
         need = ctx.needs_input_grad
         be = sparse.backend_for(dyr)
-        K, n = cat.K, cat.buf.shape[0]
+        d_self, dn, dws, dwn, db = _head_rows_dense_backward(be, ctx.gidx, cat, w_self, w_neigh, dyr, rows, need[2], need[3] or need[4],
+                                                             need[5], True)
         dh = None
         if need[2]:
-            dcat = dyr @ torch.cat([w_self, w_neigh], dim=1)                     # [R, 2K]: d[h | neigh] on the loss rows
-            dn = torch.empty((n, K), dtype=dyr.dtype, device=dyr.device)          # rows outside `rows` stay unwritten: never gathered
-            dn.index_copy_(0, rows, dcat[:, K:] * ctx.gidx.csc().inv_degrees()[rows].view(-1, 1))
-            dh = be.spmm_copy_u_masked(ctx.gidx.csr(), "sum", dn, _row_bits(rows, n, be))
-            dh.index_add_(0, rows, dcat[:, :K])
-        dws = dwn = None
-        if need[3] or need[4]:
-            dw = _weight_grad(dyr, cat.buf.index_select(0, rows))                  # [out, 2K]
-            dws, dwn = dw[:, :K].contiguous(), dw[:, K:].contiguous()
-        db = be.column_sum(dyr) if need[5] else None
+            # d self on the rows of a zero matrix, the reversed aggregation accumulating into it: what the layer over all rows does,
+            # bit for bit (its d self is zero outside the rows).  Aggregating into a new matrix and adding d self afterwards saves the
+            # kernel's read of its output, but the kernel starts a row's sum from the value it accumulates into: other bits
+            dh = torch.zeros_like(dn).index_copy_(0, rows, d_self)
+            be.spmm_copy_u_strided(ctx.gidx.csr(), "sum", dn, dh, accumulate=True)
+        return None, None, dh, dws, dwn, db, None
+
+
+class SageMeanCatRowsFn(torch.autograd.Function):
+    """SageMeanCatHeadFn whose reversed aggregation ALSO skips the gathers of the source rows whose gradient is zero by construction
+    (mgx_spmm_copy_u_masked with a bitmap of `rows`; those rows of d neigh are never even written) -- MGX_SAGE_SPARSE_LAST=1, off by
+    default and off the headline, whose five aggregations gather every row.  Same forward, same dense backward on the listed rows.  Exact."""
+
+    @staticmethod
+    def forward(ctx, gidx, cat, h, w_self, w_neigh, bias, rows):
+        be = sparse.backend_for(h)
+        y = _head_rows_forward(be, gidx, cat, h, w_self, w_neigh, bias, rows)
+        ctx.gidx, ctx.cat, ctx.generation, ctx.rows = gidx, cat, cat.generation, rows
+        ctx.save_for_backward(w_self, w_neigh)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dyr):
+        w_self, w_neigh = ctx.saved_tensors
+        cat, rows = ctx.cat, ctx.rows
+        if cat.generation != ctx.generation:
+            raise DGLError("SAGEConv: a later forward pass overwrote the [h | neigh] buffer this backward pass needs")
+        dyr = dyr.contiguous()
+        need = ctx.needs_input_grad
+        be = sparse.backend_for(dyr)
+        d_self, dn, dws, dwn, db = _head_rows_dense_backward(be, ctx.gidx, cat, w_self, w_neigh, dyr, rows, need[2], need[3] or need[4],
+                                                             need[5], False)
+        dh = None
+        if need[2]:
+            dh = be.spmm_copy_u_masked(ctx.gidx.csr(), "sum", dn, _row_bits(rows, cat.buf.shape[0], be))
+            dh.index_add_(0, rows, d_self)
         return None, None, dh, dws, dwn, db, None
 
 
 def sage_mean_layer_rows(g, h, w_self, w_neigh, bias, cat, rows):
-    """The last SAGE layer of a model whose loss reads `rows` only (distinct): SageMeanCatRowsFn when it applies, else None."""
-    if (os.environ.get("MGX_SAGE_SPARSE_LAST", "0") != "1" or cat is None or hasattr(g, "sage_mean_layer") or rows is None
-            or sage_mean_layer.__globals__["_cat_eligible"](g, h, cat) is False or type(g) is not DGLGraph or not h.is_cuda
+    """The last SAGE layer of a model whose loss reads `rows` only (distinct) as one node with the row selection inside, or None:
+    SageMeanCatRowsFn under MGX_SAGE_SPARSE_LAST=1, else SageMeanCatHeadFn (config.SAGE_HEAD_ROWS; MGX_SAGE_HEAD_ROWS=0: neither --
+    the layer over all rows followed by select_distinct_rows).  The default form is for tall graphs like the other fused layers; the
+    number of rows in the list does not matter, an empty list included."""
+    if (cat is None or hasattr(g, "sage_mean_layer") or rows is None
+            or type(g) is not DGLGraph or not h.is_cuda or h.dim() != 2 or not _cat_eligible(g, h, cat)
             or not torch.is_grad_enabled() or h.dtype != torch.float32 or g.idtype != torch.int32 or _torch_ops() is not None
+            or rows.dtype != torch.int64 or rows.dim() != 1
             or (bias is not None and w_self.shape[0] > sparse.backend_for(h).COLUMN_SUM_MAX)):
         return None
-    return SageMeanCatRowsFn.apply(g._index, cat, h, w_self, w_neigh, bias, rows)
+    if os.environ.get("MGX_SAGE_SPARSE_LAST", "0") == "1":
+        return SageMeanCatRowsFn.apply(g._index, cat, h, w_self, w_neigh, bias, rows.contiguous())
+    be = sparse.backend_for(h)
+    if (not config.SAGE_HEAD_ROWS or os.environ.get("MGX_SAGE_HEAD_ROWS", "1") == "0" or not config.SAGE_FUSED_LAYER
+            or h.shape[0] < _ROWS_GEMM_MIN or g.is_block or g.number_of_src_nodes() != g.number_of_dst_nodes()
+            or h.shape[0] != g.number_of_src_nodes() or w_self.shape[0] > be.XTY_MAX[0] or 2 * cat.K > be.XTY_MAX[1]):
+        return None
+    return SageMeanCatHeadFn.apply(g._index, cat, h, w_self, w_neigh, bias, rows.contiguous())
 
 
 class SageMeanProjectFirstFn(torch.autograd.Function):

@@ -1077,9 +1077,65 @@ class HipBackend(object):
     XTY_MAX = (256, 1024)     # the grid of tiles in one launch goes up to this output shape
     XTY_MIN_ROWS = 1 << 16    # shorter reductions stay with the GEMM library
 
-    def xty(self, a2d, b2d, colsum=False):
+    def _xty_rows(self, a2d, b2d, rows, colsum):
+        """xty over the row list in the kernel (mgx_xty_rows / mgx_xty_colsum_rows); None when the library has no kernel for the shape."""
+        dev = self._check_dev(a2d, b2d, rows)
+        n, M = a2d.shape
+        K = b2d.shape[1]
+        tm, tk = self.XTY_TILE
+        if (M > tm or K > tk or a2d.stride(1) != 1 or b2d.stride(1) != 1 or a2d.dtype != torch.float32 or b2d.dtype != torch.float32):
+            return None
+        L = _lib.lib()
+        out = torch.empty((M, K), dtype=torch.float32, device=dev)
+        sums = torch.empty(M, dtype=torch.float32, device=dev) if colsum else None
+        ws = torch.empty(max(L.mgx_xty_workspace(M, K), 4) // 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            if colsum:
+                st = L.mgx_xty_colsum_rows(n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(b2d), max(b2d.stride(0), K), _ptr(rows),
+                                           _ptr(out), out.stride(0), _ptr(sums), _ptr(ws), _stream(dev))
+            else:
+                st = L.mgx_xty_rows(n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(b2d), max(b2d.stride(0), K), _ptr(rows),
+                                    _ptr(out), out.stride(0), _ptr(ws), _stream(dev))
+        if st == _lib.ERR_UNSUPPORTED:
+            return None
+        _lib.check(st)
+        return (out, sums) if colsum else out
+
+    def xty_pos(self, a2d, a_pos, b2d, colsum=False):
+        """a^T b over all n rows of b2d [n, K] for an a that is zero outside some rows and stored without them: a2d [R, M], a_pos int64 [n]
+        = the row of a2d that stands at row r, or -1 for a zero row (entries < R: not checked).  Bit for bit xty() of a2d scattered into
+        a zero [n, M] matrix (mgx_xty_colsum_pos).  None when the library has no kernel for the shape."""
+        dev = self._check_dev(a2d, b2d, a_pos)
+        n, K = b2d.shape
+        M = a2d.shape[1]
+        tm, tk = self.XTY_TILE
+        if (a_pos.dtype != torch.int64 or a_pos.shape != (n,) or not a_pos.is_contiguous() or a2d.shape[0] == 0 or M > tm or K > tk or a2d.stride(1) != 1
+                or b2d.stride(1) != 1 or a2d.dtype != torch.float32 or b2d.dtype != torch.float32):
+            return None
+        L = _lib.lib()
+        out = torch.empty((M, K), dtype=torch.float32, device=dev)
+        sums = torch.empty(M, dtype=torch.float32, device=dev) if colsum else None
+        ws = torch.empty(max(L.mgx_xty_workspace(M, K), 4) // 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = L.mgx_xty_colsum_pos(n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(a_pos), _ptr(b2d), max(b2d.stride(0), K),
+                                      _ptr(out), out.stride(0), _ptr(sums), _ptr(ws), _stream(dev))
+        if st == _lib.ERR_UNSUPPORTED:
+            return None
+        _lib.check(st)
+        return (out, sums) if colsum else out
+
+    def xty(self, a2d, b2d, colsum=False, rows=None):
         """a2d [n, M], b2d [n, K] -> a^T b [M, K] (the tall-skinny weight-gradient product).  colsum=True: (a^T b, column sums of a) --
-        the bias gradient from the same pass over a when the shape allows (mgx_xty_colsum), else by mgx_column_sum."""
+        the bias gradient from the same pass over a when the shape allows (mgx_xty_colsum), else by mgx_column_sum.
+        rows (int64 [n], in range -- not checked): row r of the reduction pairs a2d[r] with b2d[rows[r]], read in place by the kernel
+        where one is built for the shape (same bits as on the gathered copy), else from b2d.index_select(0, rows)."""
+        if rows is not None:
+            if rows.dtype != torch.int64 or rows.dim() != 1 or rows.shape[0] != a2d.shape[0] or not rows.is_contiguous():
+                raise DGLError("xty: rows must be a contiguous int64 vector with one entry per row of a")
+            res = self._xty_rows(a2d, b2d, rows, colsum)
+            if res is not None:
+                return res
+            b2d = b2d.index_select(0, rows)
         dev = self._check_dev(a2d, b2d)
         n, M = a2d.shape
         K = b2d.shape[1]
@@ -1122,10 +1178,56 @@ class HipBackend(object):
             return out
         return out, (sums if have_sums else self.column_sum(a2d if a2d.is_contiguous() else a2d.contiguous()))
 
-    def rows_gemm(self, a2d, b2d, b_transposed=False, bias=None, row_scale=None, scale_from=0, out=None, split_col=0):
+    def _rows_gemm_lists(self, a2d, b2d, b_transposed, bias, row_scale, scale_from, split_col, rows, scatter_rows, out2):
+        """rows_gemm with a row list in the kernel (mgx_rows_gemm_rows); None when the library has no kernel for the shape."""
+        dev = self._check_dev(a2d, b2d, bias, row_scale, rows, scatter_rows, out2)
+        n = int((rows if rows is not None else scatter_rows).shape[0])
+        K = a2d.shape[1]
+        M = b2d.shape[0] if b_transposed else b2d.shape[1]
+        if (a2d.stride(1) != 1 or b2d.stride(1) != 1 or (b2d.shape[1] if b_transposed else b2d.shape[0]) != K
+                or a2d.dtype != torch.float32 or b2d.dtype != torch.float32 or (rows is not None and scatter_rows is not None)):
+            return None
+        out = torch.empty((n, split_col if split_col else M), dtype=torch.float32, device=dev)
+        c2 = out2
+        if split_col and c2 is None:
+            c2 = torch.empty((n, M - split_col), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = _lib.lib().mgx_rows_gemm_rows(n, K, M, _ptr(a2d), a2d.stride(0), _ptr(rows), _ptr(b2d), b2d.stride(0),
+                                               1 if b_transposed else 0, _ptr(bias), _ptr(row_scale), int(scale_from), _ptr(out),
+                                               out.stride(0), _ptr(c2), 0 if c2 is None else c2.stride(0), int(split_col),
+                                               _ptr(scatter_rows), _stream(dev))
+        if st == _lib.ERR_UNSUPPORTED:
+            return None
+        _lib.check(st)
+        return out if c2 is None else (out, c2)
+
+    def rows_gemm(self, a2d, b2d, b_transposed=False, bias=None, row_scale=None, scale_from=0, out=None, split_col=0, rows=None,
+                  scatter_rows=None, out2=None):
         """a2d [n, K] (row-strided view allowed) x B -> [n, M]; B = b2d [K, M], or [M, K] when b_transposed (nn.Linear's layout);
         + bias; columns >= scale_from times row_scale[r].  split_col > 0 (a multiple of 4): TWO compact outputs, the columns before
-        and from split_col on, returned as a pair.  None when mgx_rows_gemm has no kernel for the shape (use a GEMM)."""
+        and from split_col on, returned as a pair.  None when mgx_rows_gemm has no kernel for the shape (use a GEMM).
+        rows (int64 [R]): the product of the rows a2d[rows] -- [R, M], compact.  scatter_rows (int64 [n], DISTINCT; with split_col and
+        out2 [., M - split_col]): row r of the second output is written to out2[scatter_rows[r]] and nothing else of out2 is touched;
+        the pair is (first output, out2).  row_scale is indexed by the product's rows.  Lists must be in range (not checked).  In the
+        kernel where one is built for the shape (mgx_rows_gemm_rows), else index_select / index_copy_ around the plain call: same bits."""
+        if rows is not None or scatter_rows is not None:
+            for lst in (rows, scatter_rows):
+                if lst is not None and (lst.dtype != torch.int64 or lst.dim() != 1 or not lst.is_contiguous()):
+                    raise DGLError("rows_gemm: a row list is a contiguous int64 vector")
+            if scatter_rows is not None and (not split_col or out2 is None or out2.dim() != 2 or out2.stride(1) != 1
+                                             or out2.dtype != torch.float32 or scatter_rows.shape[0] != (a2d if rows is None else rows).shape[0]):
+                raise DGLError("rows_gemm: scatter_rows needs split_col, a float32 out2 and one entry per row of the product")
+            if out is None:
+                res = self._rows_gemm_lists(a2d, b2d, b_transposed, bias, row_scale, scale_from, split_col, rows, scatter_rows, out2)
+                if res is not None:
+                    return res
+            if rows is not None:
+                a2d = a2d.index_select(0, rows)
+            res = self.rows_gemm(a2d, b2d, b_transposed, bias, row_scale, scale_from, out, split_col)
+            if res is None or scatter_rows is None:
+                return res
+            out2.index_copy_(0, scatter_rows, res[1])
+            return res[0], out2
         dev = self._check_dev(a2d, b2d, bias, row_scale, out)
         n, K = a2d.shape
         M = b2d.shape[0] if b_transposed else b2d.shape[1]

@@ -501,6 +501,24 @@ int32_t mgx_xty(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, co
  * 16-byte aligned), else MGX_ERR_UNSUPPORTED (mgx_xty + mgx_column_sum).  Same workspace. */
 int32_t mgx_xty_colsum(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int64_t ldc,
                        float* colsum, void* workspace, void* stream);
+/* mgx_xty / mgx_xty_colsum over a ROW LIST of b: row r of the reduction pairs a[r] (compact, n rows) with b[b_rows[r]] -- the weight
+ * gradient of a layer whose output gradient exists on n listed rows only, read from the layer's [N, 2K] input buffer in place.  The same
+ * rows per wave and the same MFMAs in the same order as the calls above on a gathered copy of b: the same bits.  b_rows: int64[n] on the
+ * device; every entry must lie in [0, rows of b) -- NOT checked on the device.  b_rows == NULL: the calls above.  Built for a of
+ * 33 .. 48 columns read by dword loads (the 47-class gradient) and b of 64 or 128 columns read by float4 loads (ldb % 4 == 0, 16-byte
+ * aligned); else MGX_ERR_UNSUPPORTED (gather b and use the calls above).  Same workspace. */
+int32_t mgx_xty_rows(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, const int64_t* b_rows,
+                     float* out, int64_t ldc, void* workspace, void* stream);
+int32_t mgx_xty_colsum_rows(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb,
+                            const int64_t* b_rows, float* out, int64_t ldc, float* colsum, void* workspace, void* stream);
+/* mgx_xty_colsum for an a that is ZERO outside some rows and stored without them: row r of the reduction (over all n rows of b) pairs
+ * a[a_pos[r]] with b[r]; a_pos[r] < 0 says that row r of a is zero -- neither it nor b[r] is read, and steps of four rows without any
+ * row of a issue no MFMA.  a_pos: int64[n] on the device, every entry < rows of a -- NOT checked on the device.  Bit for bit the result
+ * of mgx_xty_colsum on a scattered into a zero [n, M] matrix (same rows per wave, every row at the same place of its MFMA; the products
+ * of a zero row leave an accumulator unchanged -- for finite b: 0 x Inf / NaN would be NaN there and is skipped here), which is what keeps a training run on the bits of the layer over all rows.  colsum may
+ * be NULL.  Built for the shapes of mgx_xty_rows; else MGX_ERR_UNSUPPORTED.  a_pos == NULL: mgx_xty_colsum.  Same workspace. */
+int32_t mgx_xty_colsum_pos(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const int64_t* a_pos, const float* b,
+                           int64_t ldb, float* out, int64_t ldc, float* colsum, void* workspace, void* stream);
 
 /* C[n, M] = A[n, K] x B (+ bias[M]) for A with millions of rows and small K, M -- the dense projections either side of an aggregation
  * (SAGEConv's fc_self / fc_neigh on [h | mean_agg(h)], main_dgl_product_sage.py:23-24,64, and the input gradient d[h | neigh] = dY x W).
@@ -511,6 +529,17 @@ int32_t mgx_rows_gemm(int64_t n, int64_t K, int64_t M, const float* a, int64_t l
                       const float* bias /* [M] or NULL */, const float* row_scale /* [n] or NULL */, int64_t scale_from, float* c,
                       int64_t ldc, float* c2 /* NULL, or the matrix that receives the columns split_col .. M - 1 (as its columns 0 ..) */,
                       int64_t ldc2, int64_t split_col /* a multiple of 4 */, void* stream);
+/* mgx_rows_gemm with row lists (int64[n] on the device, either may be NULL; both NULL: mgx_rows_gemm).
+ *   a_rows:  row r of the product reads a[a_rows[r]]; c (and c2) stay compact [n, .] -- the projection of n listed rows of a tall matrix.
+ *   c2_rows: row r of the SECOND output is stored at c2[c2_rows[r]]; c stays compact and no other row of c2 is written -- the scatter
+ *            of one half of a gradient into a matrix the caller zeroed.  row_scale is indexed by r in both forms.
+ * PRECONDITIONS, not checked on the device: every entry lies inside the matrix it indexes, and the entries of c2_rows are distinct (two
+ * rows stored at one place would race).  The same MFMAs in the same order as mgx_rows_gemm on a gathered copy: the same bits.
+ * Built for: a_rows with K = 113 .. 128 in the float4 form (K % 4 == 0, lda % 4 == 0, a 16-byte aligned) and M <= 64; c2_rows with
+ * K = 37 .. 48 in the dword form and 65 <= M <= 128.  Everything else: MGX_ERR_UNSUPPORTED (gather / scatter around mgx_rows_gemm). */
+int32_t mgx_rows_gemm_rows(int64_t n, int64_t K, int64_t M, const float* a, int64_t lda, const int64_t* a_rows, const float* b, int64_t ldb,
+                           int32_t b_transposed, const float* bias, const float* row_scale, int64_t scale_from, float* c, int64_t ldc,
+                           float* c2, int64_t ldc2, int64_t split_col, const int64_t* c2_rows, void* stream);
 /* 1 when mgx_rows_gemm has a kernel for these sizes (lda: A's row stride in floats), else 0. */
 int32_t mgx_rows_gemm_supported(int64_t K, int64_t M, int64_t lda);
 /* Rows that one sweep of mgx_rows_gemm's grid covers on the current device for these sizes (relu_dropout != 0: of
