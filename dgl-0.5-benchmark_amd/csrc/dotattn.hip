@@ -49,8 +49,6 @@ struct DotArgs {
   float* partial2;     // BWD_SRC: [slots, D] of d v; FWD: [slots, 2H] chunk statistics (m_c, s_c)
 };
 
-__device__ __forceinline__ float dot4(const v4f& a, const v4f& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-
 // t[v,h] = <out[v,h,:], d out[v,h,:]> into stat[v,h,2] -- only when d q is not wanted but d k is (BWD_DST writes it otherwise)
 __global__ __launch_bounds__(kBlock) void dot_attn_t_kernel(int64_t rows, int H, int F, const float* out, const float* dout, float* stat) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;

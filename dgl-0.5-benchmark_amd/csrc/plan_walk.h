@@ -88,6 +88,9 @@ struct LaneUnroll {
 // max that keeps a NaN (fmaxf drops it): a NaN logit must reach the row's result
 __device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
 
+// a lane's 16 bytes of a row product (dotattn.hip, segattn.hip); lanes_sum<LPH> completes the head's dot product
+__device__ __forceinline__ float dot4(const v4f& a, const v4f& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
 // ---------------------------------------------------------------------------------------------- hub rows
 static inline dim3 hub_grid(const mgx_spmm_plan* plan) {  // one wave per hub row
   return dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock));

@@ -6,7 +6,9 @@ from mi355x_graph import DGLError, DGLGraph, DGLHeteroGraph, graph, create_block
 from mi355x_graph import heterograph, bipartite, hetero_from_relations  # noqa: F401
 from mi355x_graph.transform import (to_bidirected, add_self_loop, remove_self_loop, add_reverse_edges,  # noqa: F401
                                     reverse, from_networkx, from_scipy, batch, unbatch)
-from mi355x_graph import function, ops  # noqa: F401
+from mi355x_graph import function, ops, readout  # noqa: F401
+from mi355x_graph.readout import (readout_nodes, sum_nodes, mean_nodes, max_nodes, softmax_nodes, broadcast_nodes,  # noqa: F401
+                                  readout_edges, sum_edges, mean_edges, max_edges, softmax_edges, broadcast_edges)
 from . import nn, data, dataloading, utils, sampling, transform, backend  # noqa: F401
 from mi355x_graph.sampling import to_block, in_subgraph, NID, EID  # noqa: F401
 from mi355x_graph.ops import edge_softmax  # noqa: F401

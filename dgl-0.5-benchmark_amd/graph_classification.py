@@ -70,15 +70,28 @@ class GCNConv(nn.Module):
         return {"m": norm * F.relu(edges.src["x"] + edges.data["w"])}
 
 
+def make_readout(kind, emb_dim):
+    """(readout module, width of its output) for --readout: `mean` is the reference's AvgPooling (main_dgl_molhiv_gcn.py:75); `attention`
+    is dgl.nn.GlobalAttentionPooling with a Linear(emb_dim, 1) gate; `set2set` is dgl.nn.Set2Set(emb_dim, 3 iterations, 1 LSTM layer),
+    whose output is twice as wide.  Both attention readouts run ops.segment_attention (csrc/segattn.hip): one launch each way."""
+    if kind == "mean":
+        return dgl.nn.AvgPooling(), emb_dim
+    if kind == "attention":
+        return dgl.nn.GlobalAttentionPooling(nn.Linear(emb_dim, 1)), emb_dim
+    if kind == "set2set":
+        return dgl.nn.Set2Set(emb_dim, n_iters=3, n_layers=1), 2 * emb_dim
+    raise ValueError("unknown readout %r" % (kind,))
+
+
 class GCN(nn.Module):
-    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, bond_columns=3):
+    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, bond_columns=3, readout="mean"):
         super(GCN, self).__init__()
         self.atom_encoder = CategoricalEncoder(emb_dim, atom_columns)
         self.layers = nn.ModuleList([GCNConv(emb_dim, emb_dim, bond_columns) for _ in range(num_layers)])
         self.bns = nn.ModuleList([nn.BatchNorm1d(emb_dim) for _ in range(num_layers - 1)])
         self.dropout = nn.Dropout(p=dropout)
-        self.readout = dgl.nn.AvgPooling()
-        self.graph_pred_fc = nn.Linear(emb_dim, num_classes, bias=False)
+        self.readout, width = make_readout(readout, emb_dim)
+        self.graph_pred_fc = nn.Linear(width, num_classes, bias=False)
 
     def forward(self, g, atom, bond):
         x = self.atom_encoder(atom)
@@ -93,7 +106,7 @@ class GIN(nn.Module):
     copy_u/sum g-SpMM per layer on the batched graph; atom encoder, BatchNorm / relu / dropout and the mean readout as in
     the GCN above.  Bond features are not used (plain GIN)."""
 
-    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9):
+    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, readout="mean"):
         super(GIN, self).__init__()
         from dgl.nn.pytorch import GINConv
         self.atom_encoder = CategoricalEncoder(emb_dim, atom_columns)
@@ -102,8 +115,8 @@ class GIN(nn.Module):
         self.layers = nn.ModuleList([GINConv(mlp(), "sum", learn_eps=True) for _ in range(num_layers)])
         self.bns = nn.ModuleList([nn.BatchNorm1d(emb_dim) for _ in range(num_layers - 1)])
         self.dropout = nn.Dropout(p=dropout)
-        self.readout = dgl.nn.AvgPooling()
-        self.graph_pred_fc = nn.Linear(emb_dim, num_classes, bias=False)
+        self.readout, width = make_readout(readout, emb_dim)
+        self.graph_pred_fc = nn.Linear(width, num_classes, bias=False)
 
     def forward(self, g, atom, bond=None):
         x = self.atom_encoder(atom)
@@ -379,6 +392,8 @@ def main():
     p.add_argument("--dropout", type=float, default=0.5)
     p.add_argument("--model", default="gcn", choices=["gcn", "gin"],
                    help="gcn: the reference's main_dgl_molhiv_gcn.py model; gin: BASELINE.json's wording of config 5")
+    p.add_argument("--readout", default="mean", choices=["mean", "attention", "set2set"],
+                   help="mean: the reference's AvgPooling; attention: GlobalAttentionPooling; set2set: Set2Set (3 iterations)")
     args = p.parse_args()
     # batching is a handful of tiny CPU tensor ops per step: with torch's default of one thread per visible core (128 on
     # the GPU box, 16 usable) every one of them fans out and an iteration's host work takes 17 ms instead of 0.1 ms
@@ -388,7 +403,7 @@ def main():
     data = molhiv_like(args.num_graphs)
     loader = GraphDataLoader(data, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers)
     torch.manual_seed(0)
-    model = (GCN if args.model == "gcn" else GIN)(args.emb_dim, 1, args.num_layers, args.dropout).to(device)
+    model = (GCN if args.model == "gcn" else GIN)(args.emb_dim, 1, args.num_layers, args.dropout, readout=args.readout).to(device)
     loss_fn = nn.BCEWithLogitsLoss()
     trainer = None
     if args.hipgraph:

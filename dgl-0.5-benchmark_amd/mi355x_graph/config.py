@@ -31,6 +31,9 @@ GAT_PACK = True            # one packed gather operand per node for the fused wa
 # ---- dot-product attention (ops.dot_attention, nn.DotGatConv)
 DOT_ATTENTION_FUSED = True  # the fused walks of csrc/dotattn.hip; False: u_dot_v -> edge_softmax -> u_mul_e/sum through the existing operators
 
+# ---- graph readout (ops.segment_attention, nn.GlobalAttentionPooling, nn.Set2Set)
+SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: segment max -> gather -> exp -> segment sum -> gather -> multiply -> segment sum
+
 # ---- schedules (schedule.py, tileplan.py)
 PLAN_BUILDER = "device"    # "device" (mgx_spmm_plan_count / _fill) | "torch" | "host": the same tables three ways (tests compare them)
 HUB_SPLIT = 256            # rows longer than this become several work items (256 measured best on MI355X; 1024: +5..10 %)

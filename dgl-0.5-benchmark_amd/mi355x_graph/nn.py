@@ -4,6 +4,7 @@
   SAGEConv   main_dgl_arxiv_sage_nn.py:9,27-34
   GraphConv  main_dgl_enzymes_gcn_nn.py:12,29-36
   AvgPooling / SumPooling / MaxPooling   main_dgl_molhiv_gcn.py:75,93
+  GlobalAttentionPooling / Set2Set / WeightAndSum   dgl.nn.pytorch.glob (attention readouts, fused: ops.segment_attention)
 Parameter names, shapes and initialisation follow DGL v0.6.x so state_dicts and the scripts'
 reset_parameters() calls (main_dgl_reddit_gat.py:57-59) line up.
 """
@@ -544,3 +545,86 @@ class AvgPooling(_Pooling):
 
 class MaxPooling(_Pooling):
     _op = "max"
+
+
+class GlobalAttentionPooling(nn.Module):
+    """dgl.nn.GlobalAttentionPooling: r_g = sum_{i in g} softmax_g(gate_nn(x))_i * feat_nn(x_i) -> [B, D].  The softmax over the graph's
+    nodes and the weighted sum are ONE ops.segment_attention call in gate mode (csrc/segattn.hip; H = 1)."""
+
+    def __init__(self, gate_nn, feat_nn=None):
+        super(GlobalAttentionPooling, self).__init__()
+        self.gate_nn = gate_nn
+        self.feat_nn = feat_nn
+
+    def forward(self, graph, feat):
+        gate = self.gate_nn(feat)
+        if gate.shape[-1] != 1:
+            raise DGLError("The output of gate_nn should have size 1 at the last axis.")
+        feat = self.feat_nn(feat) if self.feat_nn is not None else feat
+        n = graph.number_of_nodes()
+        out = ops.segment_attention(graph.batch_num_nodes(), feat.reshape(n, 1, -1), logits=gate.reshape(n, 1), total=n)
+        return out.view(out.shape[0], -1)
+
+
+class Set2Set(nn.Module):
+    """dgl.nn.Set2Set (Vinyals et al., Order Matters): n_iters rounds of  q_t = LSTM(q*_{t-1});  a = softmax_g(<x_i, q_t>);
+    r_t = sum_i a_i x_i;  q*_t = [q_t, r_t]  ->  [B, 2 * input_dim].  Parameters are DGL's: an nn.LSTM(2 * input_dim, input_dim, n_layers)
+    named `lstm`.  Every round's softmax-weighted sum is ONE ops.segment_attention call in query mode (csrc/segattn.hip).  The LSTM sees a
+    sequence of length one per round, so its step is written out over the nn.LSTM parameters (two GEMMs and the gate arithmetic per
+    layer -- nn.LSTM's own formulas): plain tensor operators, which a HIP-graph capture of the training step records like any others."""
+
+    def __init__(self, input_dim, n_iters, n_layers):
+        super(Set2Set, self).__init__()
+        self.input_dim = input_dim
+        self.output_dim = 2 * input_dim
+        self.n_iters = n_iters
+        self.n_layers = n_layers
+        self.lstm = nn.LSTM(self.output_dim, self.input_dim, n_layers)
+        # _lstm_step writes the step out over this module's parameters and holds only for the options used here (DGL's): biases, no
+        # projection, one direction, no dropout between layers -- building self.lstm otherwise means changing _lstm_step with it
+        assert self.lstm.bias and self.lstm.proj_size == 0 and not self.lstm.bidirectional and self.lstm.dropout == 0
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.lstm.reset_parameters()
+
+    def _lstm_step(self, x, h, c):
+        """One time step of self.lstm: x [B, in], h / c lists of [B, input_dim] per layer -> (top layer's h, new h, new c)."""
+        hs, cs = [], []
+        for k in range(self.n_layers):
+            gates = (F.linear(x, getattr(self.lstm, "weight_ih_l%d" % k), getattr(self.lstm, "bias_ih_l%d" % k))
+                     + F.linear(h[k], getattr(self.lstm, "weight_hh_l%d" % k), getattr(self.lstm, "bias_hh_l%d" % k)))
+            i, f, g, o = gates.chunk(4, dim=1)
+            ck = torch.sigmoid(f) * c[k] + torch.sigmoid(i) * torch.tanh(g)
+            x = torch.sigmoid(o) * torch.tanh(ck)
+            hs.append(x)
+            cs.append(ck)
+        return x, hs, cs
+
+    def forward(self, graph, feat):
+        B, n = graph.batch_size, graph.number_of_nodes()
+        seglen = graph.batch_num_nodes()
+        feat3 = feat.reshape(n, 1, self.input_dim)
+        h = [feat.new_zeros((B, self.input_dim)) for _ in range(self.n_layers)]
+        c = [feat.new_zeros((B, self.input_dim)) for _ in range(self.n_layers)]
+        q_star = feat.new_zeros((B, self.output_dim))
+        for _ in range(self.n_iters):
+            q, h, c = self._lstm_step(q_star, h, c)
+            readout = ops.segment_attention(seglen, feat3, query=q.view(B, 1, self.input_dim), scale=1.0, total=n)
+            q_star = torch.cat([q, readout.view(B, self.input_dim)], dim=-1)
+        return q_star
+
+    def extra_repr(self):
+        return "n_iters={n_iters}".format(**self.__dict__)
+
+
+class WeightAndSum(nn.Module):
+    """dgl.nn.WeightAndSum: per-node weights sigmoid(Linear(in_feats, 1)) (named `atom_weighting`), then the weighted sum_nodes."""
+
+    def __init__(self, in_feats):
+        super(WeightAndSum, self).__init__()
+        self.in_feats = in_feats
+        self.atom_weighting = nn.Sequential(nn.Linear(in_feats, 1), nn.Sigmoid())
+
+    def forward(self, g, feats):
+        return ops.segment_reduce(g.batch_num_nodes(), feats * self.atom_weighting(feats), "sum", total=g.number_of_nodes())

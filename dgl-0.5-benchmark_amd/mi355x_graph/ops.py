@@ -8,6 +8,8 @@ Backward formulas are DGL's: dU of a sum-SpMM is the same Sp
 graph (out-CSR), dE is an SDDMM, etc.  `mean` is fused: the forward kernel divides by
 max(in_degree, 1) and the backward SpMM scales the gathered rows by the same factor, instead of
 DGL's separate elementwise divide.
+Graph readout over the row segments of a batched graph: segment_reduce, segment_softmax and segment_attention (the fused
+softmax-weighted sum of dgl.nn.GlobalAttentionPooling / Set2Set, csrc/segattn.hip); readout.py has DGL's sum_nodes ... softmax_nodes.
 """
 import os
 
@@ -19,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "segment_reduce", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -1511,6 +1513,187 @@ class SegmentReduce(torch.autograd.Function):
             valid = arg >= 0
             dx.scatter_add_(0, arg.clamp(min=0), dy * valid)
         return None, dx, None, None
+
+
+# ----------------------------------------------------------------------------- graph readout: segment softmax / attention
+def _segment_ids(offsets, n):
+    lens = offsets[1:] - offsets[:-1]
+    return torch.repeat_interleave(torch.arange(lens.shape[0], device=offsets.device), lens, output_size=n)
+
+
+class SegmentBroadcast(torch.autograd.Function):
+    """out[i] = x[segment of row i] (dgl.broadcast_nodes): a row gather forward, a segment sum backward."""
+
+    @staticmethod
+    def forward(ctx, x, offsets, n):
+        seg = _segment_ids(offsets, n)
+        ctx.save_for_backward(offsets)
+        ctx.n = n
+        return sparse.gather_rows_raw(x, seg) if x.is_cuda else x[seg]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        offsets, = ctx.saved_tensors
+        return sparse.segment_reduce_raw(offsets, dy.contiguous(), "sum", total=ctx.n)[0], None, None
+
+
+def _segment_softmax_composed(offsets, z, n):
+    """The softmax of every column over every segment from segment_reduce and row gathers: max, gather, exp, sum, gather, multiply.
+    The edge rules of csrc/segattn.hip: a segment of -inf logits only gives zeros."""
+    with torch.no_grad():
+        m = sparse.segment_reduce_raw(offsets, z, "max", total=n)[0]
+        m = torch.where(m == -float("inf"), torch.zeros_like(m), m)
+    e = torch.exp(z - SegmentBroadcast.apply(m, offsets, n))
+    s = SegmentReduce.apply("sum", e, offsets, n)
+    empty = s == 0
+    inv = torch.where(empty, torch.zeros_like(s), 1.0 / torch.where(empty, torch.ones_like(s), s))
+    return e * SegmentBroadcast.apply(inv, offsets, n)
+
+
+def _segment_attention_composed(offsets, feat, logits, query, scale, n):
+    """ops.segment_attention through the operators that existed before csrc/segattn.hip: the fallback and the comparison form."""
+    z = logits if query is None else (feat * SegmentBroadcast.apply(query, offsets, n)).sum(-1) * scale
+    a = _segment_softmax_composed(offsets, z, n)
+    return SegmentReduce.apply("sum", a.unsqueeze(-1) * feat, offsets, n)
+
+
+class SegmentSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, offsets):
+        out = sparse.backend_for(x).segment_softmax_fwd(offsets, x.contiguous().view(x.shape[0], -1)).view(x.shape)
+        ctx.save_for_backward(out, offsets)
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, dy):
+        out, offsets = ctx.saved_tensors
+        dx = sparse.backend_for(out).segment_softmax_bwd(offsets, out.view(out.shape[0], -1), dy.contiguous().view(out.shape[0], -1))
+        return dx.view(out.shape), None
+
+
+class SegmentAttention(torch.autograd.Function):
+    """out[g,h,:] = sum_{i in g} softmax_g(z)[i,h] feat[i,h,:] with z the gate column (logits) or scale <feat, query[g]>: the readout of
+    GlobalAttentionPooling / Set2Set in one walk each way, the weights rebuilt from per-segment statistics (csrc/segattn.hip)."""
+
+    @staticmethod
+    def forward(ctx, feat, logits, query, offsets, scale):
+        logits = None if logits is None else logits.contiguous()
+        query = None if query is None else query.contiguous()
+        out, stat = sparse.backend_for(feat).segment_attention_fwd(offsets, feat, logits, query, scale)
+        ctx.scale = scale
+        ctx.gate = logits is not None
+        ctx.save_for_backward(feat, logits if ctx.gate else query, offsets, out, stat)
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        feat, other, offsets, out, stat = ctx.saved_tensors
+        logits, query = (other, None) if ctx.gate else (None, other)
+        need = ctx.needs_input_grad
+        d_feat, d_logits, d_query = sparse.backend_for(feat).segment_attention_bwd(offsets, feat, logits, query, ctx.scale, out,
+                                                                                   d_out.contiguous(), stat, need[0], need[1], need[2])
+        return d_feat, d_logits, d_query, None, None
+
+
+def _offsets_of(seglen, device):
+    offsets = torch.zeros(seglen.shape[0] + 1, dtype=torch.int64, device=device)
+    torch.cumsum(seglen.to(device).long(), 0, out=offsets[1:])
+    return offsets
+
+
+def _segment_offsets(seglen, value, total, who):
+    """(offsets on value's device, number of rows): as segment_reduce builds them -- a cumsum on the device, the row count from the caller
+    or from host lengths, read back once otherwise."""
+    if not torch.is_tensor(seglen) or seglen.dim() != 1:
+        raise DGLError("%s: seglen must be a 1-D tensor of segment lengths" % who)
+    if total is None:
+        total = int(seglen.sum())
+    if int(total) != value.shape[0]:
+        raise DGLError("%s: segment lengths sum to %d, value has %d rows" % (who, total, value.shape[0]))
+    return _offsets_of(seglen, value.device), int(total)
+
+
+def _readout_kernels(t):
+    """The backend of `t` has csrc/segattn.hip (device tensors outside the MGX_TORCH_OPS=1 test mode); CPU backends compose."""
+    return t.is_cuda and _torch_ops() is None and hasattr(sparse.backend_for(t), "segment_attention_fwd")
+
+
+def segment_softmax(seglen, value, total=None):
+    """Softmax of every column of `value` [N, ...] over consecutive row segments (dgl.softmax_nodes / softmax_edges).  Device tensors run
+    csrc/segattn.hip (any width, one launch each way); CPU tensors -- under a registered CPU backend, as segment_reduce -- the
+    composition segment max -> gather -> exp -> segment sum -> gather -> multiply."""
+    if not torch.is_tensor(value) or value.dim() < 1:
+        raise DGLError("segment_softmax: expected a tensor [N, ...], got %s" % (type(value).__name__,))
+    if value.dtype != torch.float32:
+        raise DGLError("segment_softmax expects float32 input, got %s" % (value.dtype,))
+    offsets, n = _segment_offsets(seglen, value, total, "segment_softmax")
+    if value.numel() == 0:
+        return value.clone()
+    if _readout_kernels(value):
+        return SegmentSoftmax.apply(value, offsets)
+    sparse.backend_for(value)  # no CPU backend: DGLError
+    return _segment_softmax_composed(offsets, value, n)
+
+
+def _segment_attention_args(seglen, feat, logits, query, total):
+    if not torch.is_tensor(feat) or feat.dim() != 3:
+        raise DGLError("segment_attention: expected feat [N, H, F], got %s" % (tuple(feat.shape) if torch.is_tensor(feat) else type(feat).__name__,))
+    if (logits is None) == (query is None):
+        raise DGLError("segment_attention: exactly one of logits (gate mode) and query (query mode) must be given, got %s"
+                       % ("both" if logits is not None else "neither"))
+    other = logits if logits is not None else query
+    if not torch.is_tensor(other) or feat.dtype != torch.float32 or other.dtype != torch.float32:
+        raise DGLError("segment_attention expects float32 inputs, got %s / %s"
+                       % (feat.dtype, other.dtype if torch.is_tensor(other) else type(other).__name__))
+    if other.device != feat.device:
+        raise DGLError("segment_attention: operands on different devices: %s vs %s" % (feat.device, other.device))
+    offsets, n = _segment_offsets(seglen, feat, total, "segment_attention")
+    N, H, F = feat.shape
+    if logits is not None and tuple(logits.shape) != (N, H):
+        raise DGLError("segment_attention: expected logits [%d, %d] for feat %s, got %s" % (N, H, tuple(feat.shape), tuple(logits.shape)))
+    if query is not None and tuple(query.shape) != (seglen.shape[0], H, F):
+        raise DGLError("segment_attention: expected query [%d, %d, %d] for %d segments and feat %s, got %s"
+                       % (seglen.shape[0], H, F, seglen.shape[0], tuple(feat.shape), tuple(query.shape)))
+    return offsets, n
+
+
+def segment_attention_fused(seglen, feat, logits=None, query=None, scale=1.0, total=None):
+    """True when segment_attention(...) with these operands runs the fused pair of csrc/segattn.hip (else the composition)."""
+    other = logits if logits is not None else query
+    if (not torch.is_tensor(feat) or feat.dim() != 3 or not torch.is_tensor(other) or (logits is None) == (query is None)
+            or feat.dtype != torch.float32 or other.dtype != torch.float32 or other.device != feat.device
+            or not config.SEGMENT_ATTENTION_FUSED or feat.device.type not in sparse._BACKENDS or not _readout_kernels(feat)):
+        return False
+    return feat.shape[0] > 0 and seglen.shape[0] > 0 and sparse.backend_for(feat).segment_attention_supported(feat)
+
+
+def segment_attention(seglen, feat, logits=None, query=None, scale=1.0, total=None):
+    """Attention readout over consecutive row segments: out[g,h,:] = sum_{i in g} a[i,h] feat[i,h,:] with a the softmax over the segment
+    of z[i,h] = logits[i,h] (gate mode: GlobalAttentionPooling) or z[i,h] = scale * <feat[i,h,:], query[g,h,:]> (query mode: Set2Set).
+
+    feat [N, H, F], logits [N, H] or query [S, H, F] (fp32; feat may be a row-strided column block), result [S, H, F]: exactly 0 for an
+    empty segment or one whose logits are all -inf.  `total`: the row count when the caller knows it (no read-back of device lengths).
+    Device operands with F % 4 == 0, H*F <= 256 and (H == 1 or F in {4, 8, 16, 32, 64}) run csrc/segattn.hip (segment_attention_fused);
+    everything else -- CPU tensors under a registered CPU backend, other shapes, config.SEGMENT_ATTENTION_FUSED = False -- is segment
+    max -> gather -> exp -> segment sum -> gather -> multiply -> segment sum through segment_reduce and row gathers."""
+    offsets, n = _segment_attention_args(seglen, feat, logits, query, total)
+    scale = float(scale)
+    if segment_attention_fused(seglen, feat, logits, query, scale, n):
+        return SegmentAttention.apply(feat, logits, query, offsets, scale)
+    sparse.backend_for(feat)  # no CPU backend: DGLError
+    if feat.shape[0] == 0 or seglen.shape[0] == 0:
+        return feat.new_zeros((seglen.shape[0],) + tuple(feat.shape[1:]))
+    return _segment_attention_composed(offsets, feat, logits, query, scale, n)
+
+
+def segment_broadcast(seglen, value, total):
+    """out[i] = value[segment of row i] for `total` rows (dgl.broadcast_nodes / broadcast_edges)."""
+    if value.shape[0] != seglen.shape[0]:
+        raise DGLError("segment_broadcast: %d segments, value has %d rows" % (seglen.shape[0], value.shape[0]))
+    return SegmentBroadcast.apply(value, _offsets_of(seglen, value.device), int(total))
 
 
 # ----------------------------------------------------------------------------- public API

@@ -981,6 +981,86 @@ class HipBackend(object):
             _lib.check(_lib.lib().mgx_segment_reduce(n, _ptr(offsets), x2d.shape[1], REDUCE[reduce], _ptr(x2d), _ptr(out), _ptr(arg), _stream(dev)))
         return out, arg
 
+    # ---- graph readout (csrc/segattn.hip): nothing here reads `offsets` on the host
+    def segment_softmax_fwd(self, offsets, x2d):
+        dev = self._check_dev(offsets, x2d)
+        n, D = offsets.shape[0] - 1, int(x2d.shape[1])
+        out = torch.empty_like(x2d)
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_softmax_fwd", segments=int(n), rows=int(x2d.shape[0]), D=D):
+            _lib.check(_lib.lib().mgx_segment_softmax_fwd(n, _ptr(offsets), D, _ptr(x2d), _ptr(out), _stream(dev)))
+        return out
+
+    def segment_softmax_bwd(self, offsets, out2d, d_out2d):
+        dev = self._check_dev(offsets, out2d, d_out2d)
+        n, D = offsets.shape[0] - 1, int(out2d.shape[1])
+        dx = torch.empty_like(out2d)
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_softmax_bwd", segments=int(n), rows=int(out2d.shape[0]), D=D):
+            _lib.check(_lib.lib().mgx_segment_softmax_bwd(n, _ptr(offsets), D, _ptr(out2d), _ptr(d_out2d), _ptr(dx), _stream(dev)))
+        return dx
+
+    @staticmethod
+    def _seg_operand(x3d):
+        """(tensor, row stride in floats) of a [N, H, F] feature operand as the kernels take it: the H*F floats of a row contiguous, the
+        row stride a multiple of 4 floats, the base 16-byte aligned (a column block of a wider matrix qualifies); else a dense copy."""
+        H, F = int(x3d.shape[1]), int(x3d.shape[2])
+        if (x3d.shape[0] > 0 and x3d.stride(2) == 1 and x3d.stride(1) == F and x3d.stride(0) >= H * F and x3d.stride(0) % 4 == 0
+                and x3d.data_ptr() % 16 == 0):
+            return x3d, int(x3d.stride(0))
+        return HipBackend._dense16(x3d), H * F
+
+    @staticmethod
+    def _dense16(t):
+        """`t` as the kernels take a dense operand: contiguous with a 16-byte aligned base.  A contiguous tensor at an odd storage offset
+        (a slice of a flattened buffer, an upstream gradient cut out of a `cat`) is copied: the entry points refuse such a base."""
+        if t is None:
+            return None
+        t = t.contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+    @classmethod
+    def segment_attention_supported(cls, feat3d):
+        """Shapes mgx_segment_attention_* takes: F % 4 == 0, H*F <= 256; one head: any such F, several: F in {4, 8, 16, 32, 64}."""
+        H, F = int(feat3d.shape[1]), int(feat3d.shape[2])
+        if H < 1 or F < 1:
+            return False
+        return bool(_lib.lib().mgx_segment_attention_supported(H, F, H * F))  # a stride the kernels cannot take becomes a dense copy
+
+    def segment_attention_fwd(self, offsets, feat3d, logits2d, query3d, scale):
+        """feat3d [N, H, F] (row-strided views are taken as they are), logits2d [N, H] | None, query3d [S, H, F] | None ->
+        (out [S, H, F], stat [S, H, 2] = (m, 1/s))."""
+        dev = self._check_dev(offsets, feat3d, logits2d, query3d)
+        S, H, F = offsets.shape[0] - 1, int(feat3d.shape[1]), int(feat3d.shape[2])
+        feat, ld = self._seg_operand(feat3d)
+        logits2d = None if logits2d is None else logits2d.contiguous()
+        query3d = self._dense16(query3d)
+        out = torch.empty((S, H, F), dtype=torch.float32, device=dev)
+        stat = torch.empty((S, H, 2), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="seg_attn_fwd", H=H, F=F, segments=int(S), rows=int(feat3d.shape[0]),
+                                                mode="gate" if query3d is None else "query"):
+            _lib.check(_lib.lib().mgx_segment_attention_fwd(S, _ptr(offsets), H, F, _ptr(feat), ld, _ptr(logits2d), _ptr(query3d),
+                                                            ctypes.c_float(scale), _ptr(out), _ptr(stat), _stream(dev)))
+        return out, stat
+
+    def segment_attention_bwd(self, offsets, feat3d, logits2d, query3d, scale, out3d, d_out3d, stat, need_feat, need_logits, need_query):
+        """-> (d_feat | None, d_logits | None, d_query | None), each dense."""
+        dev = self._check_dev(offsets, feat3d, logits2d, query3d, out3d, d_out3d, stat)
+        S, H, F = offsets.shape[0] - 1, int(feat3d.shape[1]), int(feat3d.shape[2])
+        need_logits, need_query = need_logits and logits2d is not None, need_query and query3d is not None
+        if not (need_feat or need_logits or need_query):
+            return None, None, None
+        feat, ld = self._seg_operand(feat3d)
+        logits2d = None if logits2d is None else logits2d.contiguous()
+        query3d, out3d, d_out3d = self._dense16(query3d), self._dense16(out3d), self._dense16(d_out3d)
+        d_feat = torch.empty((feat3d.shape[0], H, F), dtype=torch.float32, device=dev) if need_feat else None
+        d_logits = torch.empty((feat3d.shape[0], H), dtype=torch.float32, device=dev) if need_logits else None
+        d_query = torch.empty((S, H, F), dtype=torch.float32, device=dev) if need_query else None
+        with torch.cuda.device(dev), timed_call(dev, kernel="seg_attn_bwd", H=H, F=F, segments=int(S), rows=int(feat3d.shape[0]),
+                                                mode="gate" if query3d is None else "query"):
+            _lib.check(_lib.lib().mgx_segment_attention_bwd(S, _ptr(offsets), H, F, _ptr(feat), ld, _ptr(logits2d), _ptr(query3d),
+                                                            ctypes.c_float(scale), _ptr(out3d), _ptr(d_out3d), _ptr(stat), _ptr(d_feat),
+                                                            _ptr(d_logits), _ptr(d_query), _stream(dev)))
+        return d_feat, d_logits, d_query
+
     @staticmethod
     def _row_strided(t):
         return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 4 == 0 and t.shape[1] % 4 == 0

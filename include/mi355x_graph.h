@@ -581,6 +581,46 @@ int32_t mgx_relu_dropout_bwd_slots(int64_t rows, const float* dy, int64_t dy_str
 int32_t mgx_relu_dropout_fwd_counter(int64_t rows, int64_t cols, const float* x, int64_t x_stride, float p, uint64_t seed,
                                      const uint64_t* counter, float* y, int64_t y_stride, uint8_t* mask, void* stream);
 
+/* ------------------------------------------------------------------ graph readout: segment softmax, segment attention
+ * (csrc/segattn.hip).  Segments are the contiguous row slices of a batched graph: offsets int64 [num_segments+1] on the device
+ * (the array mgx_segment_reduce takes), offsets[num_segments] = number of rows.  Nothing is read back to the host: every entry
+ * point can be captured in a HIP graph.  All operands fp32.
+ *
+ * Segment softmax (dgl.softmax_nodes / softmax_edges), per column, any D >= 1, one launch each way:
+ *   out[i,c] = exp(x[i,c] - m[g,c]) / s[g,c]          m, s = max and sum over the rows of segment g
+ *   d_x      = out * (d_out - sum_{j in g} out[j,c] * d_out[j,c])
+ *
+ * Segment attention (dgl.nn.GlobalAttentionPooling, dgl.nn.Set2Set), one launch each way, no N-sized temporary:
+ *   gate mode  (logits given):  z[i,h] = logits[i,h]                                      (scale ignored)
+ *   query mode (query given):   z[i,h] = scale * sum_f feat[i,h,f] * query[g,h,f]         (scale applied once, after the sum)
+ *   a[i,h] = exp(z[i,h] - m[g,h]) / s[g,h];   out[g,h,:] = sum_{i in g} a[i,h] * feat[i,h,:]
+ *   fwd: writes out [S, H*F] and stat [S, H, 2] = (m, 1/s), from which the backward rebuilds a; `a` is never written.
+ *   bwd: t[g,h] = <out[g,h,:], d_out[g,h,:]>, dp[i,h] = <feat[i,h,:], d_out[g,h,:]>, dz = a * (dp - t);
+ *        gate:  d_logits = dz, d_feat[i] = a * d_out[g];
+ *        query: d_feat[i] = a * d_out[g] + dz * scale * query[g], d_query[g] = scale * sum_i dz * feat[i].
+ *        d_feat [N, H*F], d_logits [N, H] (gate mode), d_query [S, H*F] (query mode) may each be NULL.
+ * Exactly one of logits [N, H] and query [S, H*F] is non-NULL (else MGX_ERR_INVALID_ARGUMENT).  feat [N, feat_ld]: the first H*F
+ * floats of a row are the operand, so feat may be a column block of a wider matrix.  feat, query, out, d_out, d_feat, d_query:
+ * 16-byte aligned; everything but feat dense.
+ * Supported (mgx_segment_attention_supported; everything else is MGX_ERR_UNSUPPORTED and the caller composes mgx_segment_reduce
+ * and mgx_gather_rows): F % 4 == 0, H*F <= 256, feat_ld % 4 == 0 and >= H*F; H == 1: any such F; H > 1: F in {4, 8, 16, 32, 64}.
+ * Edge rules: an empty segment gives out = 0, stat = (0, 0) and zero gradients; a -inf logit has weight 0; a segment whose logits
+ * are all -inf behaves like an empty one (out = 0, not NaN); a NaN logit makes that (segment, head) NaN -- for the softmax that
+ * (segment, column) -- and leaves every other one untouched.
+ * One wave walks one segment whatever its length (as in mgx_segment_reduce): a few very long segments have little parallelism.
+ * Deterministic: no atomics, lane groups merged in a fixed order.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_segment_softmax_fwd(int64_t num_segments, const int64_t* offsets, int64_t D, const float* x, float* out, void* stream);
+int32_t mgx_segment_softmax_bwd(int64_t num_segments, const int64_t* offsets, int64_t D, const float* out, const float* d_out,
+                                float* d_x, void* stream);
+int32_t mgx_segment_attention_supported(int64_t H, int64_t F, int64_t feat_ld);
+int32_t mgx_segment_attention_fwd(int64_t num_segments, const int64_t* offsets, int64_t H, int64_t F, const float* feat,
+                                  int64_t feat_ld, const float* logits /* [N, H] or NULL */, const float* query /* [S, H*F] or NULL */,
+                                  float scale, float* out, float* stat, void* stream);
+int32_t mgx_segment_attention_bwd(int64_t num_segments, const int64_t* offsets, int64_t H, int64_t F, const float* feat,
+                                  int64_t feat_ld, const float* logits, const float* query, float scale, const float* out,
+                                  const float* d_out, const float* stat, float* d_feat, float* d_logits, float* d_query,
+                                  void* stream);
+
 /* ------------------------------------------------------------------ formats (integer, bit-exact)
  * Replace the lazy COO->CSR/CSC construction behind g.formats(...)/first kernel call
  * (main_dgl_product_sage.py:158, kernel/dgl-new.py:63) and g.in_degrees()
