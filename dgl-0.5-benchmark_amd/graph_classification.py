@@ -44,8 +44,12 @@ class CategoricalEncoder(nn.Module):
 
 
 class GCNConv(nn.Module):
-    def __init__(self, in_feats, out_feats, bond_columns=3):
+    """fused=True (--fused-message): the message-and-sum of the UDF below as ONE operator, dgl.ops.gine_sum -- the same values with
+    no [E, D] tensor written (csrc/gine.hip); `norm` is then formed once per batch by GCN.forward and handed in."""
+
+    def __init__(self, in_feats, out_feats, bond_columns=3, fused=False):
         super(GCNConv, self).__init__()
+        self.fused = fused
         self.fc = nn.Linear(in_feats, out_feats, bias=False)
         self.root_emb = nn.Embedding(1, in_feats)
         self.bond_encoder = CategoricalEncoder(in_feats, bond_columns)
@@ -55,10 +59,13 @@ class GCNConv(nn.Module):
         nn.init.xavier_uniform_(self.fc.weight, gain=nn.init.calculate_gain("relu"))
         self.root_emb.reset_parameters()
 
-    def forward(self, graph, feat, bond):
+    def forward(self, graph, feat, bond, norm=None):
         graph = graph.local_var()
         x = self.fc(feat)
         deg = graph.in_degrees().float().unsqueeze(1) + 1
+        if self.fused:
+            h = dgl.ops.gine_sum(graph, x, self.bond_encoder(bond), scale=norm)
+            return h + F.relu(x + self.root_emb.weight) * 1. / deg
         graph.ndata["c"] = deg.pow(-0.5)
         graph.ndata["x"] = x
         graph.edata["w"] = self.bond_encoder(bond)
@@ -84,20 +91,28 @@ def make_readout(kind, emb_dim):
 
 
 class GCN(nn.Module):
-    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, bond_columns=3, readout="mean"):
+    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, bond_columns=3, readout="mean", fused=False):
         super(GCN, self).__init__()
+        self.fused = fused
         self.atom_encoder = CategoricalEncoder(emb_dim, atom_columns)
-        self.layers = nn.ModuleList([GCNConv(emb_dim, emb_dim, bond_columns) for _ in range(num_layers)])
+        self.layers = nn.ModuleList([GCNConv(emb_dim, emb_dim, bond_columns, fused=fused) for _ in range(num_layers)])
         self.bns = nn.ModuleList([nn.BatchNorm1d(emb_dim) for _ in range(num_layers - 1)])
         self.dropout = nn.Dropout(p=dropout)
         self.readout, width = make_readout(readout, emb_dim)
         self.graph_pred_fc = nn.Linear(width, num_classes, bias=False)
 
+    def edge_norm(self, g):
+        """[E] c[src] * c[dst], c = (in_degree + 1) ** -0.5: the `norm` of GCNConv.message, the same for every layer of a batch"""
+        c = (g.in_degrees().float() + 1).pow(-0.5)
+        src, dst = g.edges()
+        return c[src.long()] * c[dst.long()]
+
     def forward(self, g, atom, bond):
         x = self.atom_encoder(atom)
+        extra = (self.edge_norm(g),) if self.fused else ()
         for i, layer in enumerate(self.layers[:-1]):
-            x = self.dropout(F.relu(self.bns[i](layer(g, x, bond))))
-        x = self.layers[-1](g, x, bond)
+            x = self.dropout(F.relu(self.bns[i](layer(g, x, bond, *extra))))
+        x = self.layers[-1](g, x, bond, *extra)
         return self.graph_pred_fc(self.readout(g, x))
 
 
@@ -378,7 +393,7 @@ def train_epoch(model, device, loader, optimizer, loss_fn):
     return loss.item()
 
 
-def main():
+def make_parser():
     p = argparse.ArgumentParser("molhiv-shaped GCN on the MI355X message-passing backend")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--num_layers", type=int, default=5)
@@ -394,7 +409,14 @@ def main():
                    help="gcn: the reference's main_dgl_molhiv_gcn.py model; gin: BASELINE.json's wording of config 5")
     p.add_argument("--readout", default="mean", choices=["mean", "attention", "set2set"],
                    help="mean: the reference's AvgPooling; attention: GlobalAttentionPooling; set2set: Set2Set (3 iterations)")
-    args = p.parse_args()
+    p.add_argument("--fused-message", action="store_true",
+                   help="gcn: run every layer's norm * relu(x_u + w_e) message and its sum as ONE operator (dgl.ops.gine_sum) instead "
+                        "of the UDF's gathers, add / relu / mul and copy_e/sum g-SpMM")
+    return p
+
+
+def main():
+    args = make_parser().parse_args()
     # batching is a handful of tiny CPU tensor ops per step: with torch's default of one thread per visible core (128 on
     # the GPU box, 16 usable) every one of them fans out and an iteration's host work takes 17 ms instead of 0.1 ms
     torch.set_num_threads(max(1, min(int(os.environ.get("MGX_HOST_THREADS", "4")), os.cpu_count() or 1)))
@@ -403,7 +425,8 @@ def main():
     data = molhiv_like(args.num_graphs)
     loader = GraphDataLoader(data, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers)
     torch.manual_seed(0)
-    model = (GCN if args.model == "gcn" else GIN)(args.emb_dim, 1, args.num_layers, args.dropout, readout=args.readout).to(device)
+    extra = {"fused": True} if args.fused_message and args.model == "gcn" else {}
+    model = (GCN if args.model == "gcn" else GIN)(args.emb_dim, 1, args.num_layers, args.dropout, readout=args.readout, **extra).to(device)
     loss_fn = nn.BCEWithLogitsLoss()
     trainer = None
     if args.hipgraph:

@@ -86,6 +86,10 @@ SIGNATURES = {
     "mgx_dot_attention_fwd": (_i32, [_csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, ctypes.c_float, _fp, _fp, _vp, _vp]),
     "mgx_dot_attention_bwd": (_i32, [_csr_p, _vp, _csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, ctypes.c_float, _fp, _fp, _fp,
                                      _fp, _fp, _fp, _vp, _vp]),
+    "mgx_gine_supported": (_i32, [_csr_p, _i64]),
+    "mgx_gine_workspace": (_i64, [_vp, _i64]),
+    "mgx_gine_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _vp, _vp]),
+    "mgx_gine_bwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),
     "mgx_head_dot_fwd": (_i32, [_i64, _i64, _i64, _fp, _fp, _fp, _fp, _fp, _vp]),
     "mgx_head_dot_bwd_workspace": (_i64, [_i64, _i64]),
     "mgx_head_dot_bwd": (_i32, [_i64, _i64, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),

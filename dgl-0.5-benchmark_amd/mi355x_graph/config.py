@@ -30,6 +30,8 @@ GAT_PACK = True            # one packed gather operand per node for the fused wa
 
 # ---- dot-product attention (ops.dot_attention, nn.DotGatConv)
 DOT_ATTENTION_FUSED = True  # the fused walks of csrc/dotattn.hip; False: u_dot_v -> edge_softmax -> u_mul_e/sum through the existing operators
+# ---- relu(x_u + w_e) messages summed per destination (ops.gine_sum, nn.GINEConv, graph_classification.py --fused-message)
+GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> relu -> mul -> copy_e/sum through the existing operators
 
 # ---- graph readout (ops.segment_attention, nn.GlobalAttentionPooling, nn.Set2Set)
 SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: segment max -> gather -> exp -> segment sum -> gather -> multiply -> segment sum

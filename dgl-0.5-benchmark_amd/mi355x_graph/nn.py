@@ -1,6 +1,7 @@
 """dgl.nn.pytorch modules used by the benchmark scripts, written against this backend's ops:
   GATConv    main_dgl_reddit_gat.py:10,31-55 (u_add_v SDDMM + fused edge_softmax + u_mul_e/sum SpMM)
   DotGatConv dgl.nn.pytorch.DotGatConv (u_dot_v SDDMM + edge_softmax + u_mul_e/sum SpMM, fused: ops.dot_attention)
+  GINEConv   dgl.nn.pytorch.GINEConv (sum of relu(h_u + e_uv) messages, fused: ops.gine_sum)
   SAGEConv   main_dgl_arxiv_sage_nn.py:9,27-34
   GraphConv  main_dgl_enzymes_gcn_nn.py:12,29-36
   AvgPooling / SumPooling / MaxPooling   main_dgl_molhiv_gcn.py:75,93
@@ -474,6 +475,26 @@ class GINConv(nn.Module):
             if self.apply_func is not None:
                 rst = self.apply_func(rst)
             return rst
+
+
+class GINEConv(nn.Module):
+    """dgl.nn.pytorch.GINEConv (UPSTREAM): h_v = f((1 + eps) h_v + sum_{u->v} relu(h_u + e_uv)) -- GIN with edge features of the node
+    width.  The aggregation is ops.gine_sum (csrc/gine.hip when it takes the shape: no [E, D] message tensor), then `apply_func`."""
+
+    def __init__(self, apply_func=None, init_eps=0, learn_eps=False):
+        super(GINEConv, self).__init__()
+        self.apply_func = apply_func
+        if learn_eps:
+            self.eps = nn.Parameter(torch.FloatTensor([init_eps]))
+        else:
+            self.register_buffer("eps", torch.FloatTensor([init_eps]))
+
+    def forward(self, graph, node_feat, edge_feat):
+        feat_src, feat_dst = expand_as_pair(node_feat, graph)
+        rst = (1 + self.eps) * feat_dst + ops.gine_sum(graph, feat_src, edge_feat)
+        if self.apply_func is not None:
+            rst = self.apply_func(rst)
+        return rst
 
 
 def _hetero_aggregate(name):

@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -476,6 +476,90 @@ def dot_attention(graph, q, k, v, scale=None):
     if not dot_attention_fused(graph, q, k, v):
         return gspmm(gidx, "mul", "sum", v, edge_softmax(gidx, gsddmm(gidx, "dot", k, q, "u", "v") * scale))
     return DotAttention.apply(gidx, q, k, v, scale)
+
+
+class GineSum(torch.autograd.Function):
+    """out[v,:] = sum_{e: u->v} s[e] relu(x[u,:] + w[e,:]) -- a `s * relu(src.x + edge.w)` UDF message reduced with fn.sum, in one walk
+    of the in-CSR forward and one of the out-CSR backward (d x and d w together), with no E-sized temporary: the relu mask is rebuilt
+    from x and w where it is needed (csrc/gine.hip).  Saves x, w and scale only."""
+
+    @staticmethod
+    def forward(ctx, gidx, x, w, scale):
+        x, w = x.contiguous(), w.contiguous()
+        scale = None if scale is None else scale.contiguous()
+        out = sparse.backend_for(x).gine_fwd(gidx.csc(), x, w, scale)
+        ctx.gidx, ctx.has_scale = gidx, scale is not None
+        ctx.save_for_backward(*((x, w, scale) if scale is not None else (x, w)))
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        x, w = ctx.saved_tensors[:2]
+        scale = ctx.saved_tensors[2] if ctx.has_scale else None
+        need = ctx.needs_input_grad
+        d_x, d_w = sparse.backend_for(x).gine_bwd(ctx.gidx.csr(), x, w, scale, d_out.contiguous(), need[1], need[2])
+        return None, d_x, d_w, None
+
+
+def _gine_args(graph, x, w, scale):
+    """(graph index, scale as [E] or None) of a gine_sum call, or DGLError."""
+    gidx = _gidx(graph)
+    if not (torch.is_tensor(x) and torch.is_tensor(w) and x.dim() == 2 and w.dim() == 2):
+        raise DGLError("gine_sum: expected x [N_src, D] and w [E, D], got %s"
+                       % (", ".join(str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__ for t in (x, w)),))
+    if x.dtype != torch.float32 or w.dtype != torch.float32 or (scale is not None and torch.is_tensor(scale) and scale.dtype != torch.float32):
+        raise DGLError("gine_sum expects float32 inputs, got %s / %s%s"
+                       % (x.dtype, w.dtype, "" if scale is None else " / %s" % (scale.dtype,)))
+    E = gidx.num_edges()
+    if x.shape[0] != gidx.num_src or w.shape[0] != E or w.shape[1] != x.shape[1]:
+        raise DGLError("gine_sum: expected x [%d, D] and w [%d, D], got x %s, w %s" % (gidx.num_src, E, tuple(x.shape), tuple(w.shape)))
+    if scale is not None:
+        if not torch.is_tensor(scale) or tuple(scale.shape) not in ((E,), (E, 1)):
+            raise DGLError("gine_sum: expected scale [%d] or [%d, 1], got %s"
+                           % (E, E, tuple(scale.shape) if torch.is_tensor(scale) else type(scale).__name__))
+        if scale.requires_grad:
+            raise DGLError("gine_sum: scale gets no gradient; pass it detached")
+        scale = scale.reshape(E)
+    return gidx, scale
+
+
+def gine_sum_fused(graph, x, w, scale=None):
+    """True when gine_sum(graph, x, w, scale) runs the fused kernels (else it is gather -> add -> relu -> mul -> copy_e/sum)."""
+    gidx = _gidx(graph)
+    if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == x.device
+                for t in (x, w) + (() if scale is None else (scale,)))
+            or x.dim() != 2 or w.dim() != 2 or not config.GINE_FUSED or _torch_ops() is not None or x.device.type not in sparse._BACKENDS):
+        return False
+    be = sparse.backend_for(x)
+    E = gidx.num_edges()
+    if (not hasattr(be, "gine_fwd") or not hasattr(be, "gine_bwd") or x.shape[0] != gidx.num_src or tuple(w.shape) != (E, x.shape[1])
+            or (scale is not None and scale.numel() != E) or E == 0):
+        return False
+    # the kernels read 16 bytes per lane: a contiguous view at an odd storage offset is not theirs (a strided one is copied, and a
+    # fresh allocation is aligned)
+    if any(t.is_contiguous() and t.data_ptr() % 16 for t in (x, w)):
+        return False
+    return be.gine_supported(gidx.csc(), int(x.shape[1]))
+
+
+def gine_sum(graph, x, w, scale=None):
+    """Sum of relu messages with edge features: out[v,:] = sum_{e: u->v} scale[e] * relu(x[u,:] + w[e,:]).
+
+    x: [N_src, D], w: [E, D] and scale: [E] | [E, 1] | None (= 1) by edge id, fp32; result [N_dst, D], exactly 0 for destinations without
+    in-edges.  scale gets no gradient.  Device operands (16-byte aligned) with D % 4 == 0 and 4 <= D <= 256 on an int32 graph run csrc/gine.hip
+    (gine_sum_fused) and write nothing of size E but d w; everything else takes
+    gspmm(g, "copy_rhs", "sum", None, relu(gsddmm(g, "copy_lhs", x, None, "u", "v") + w) * scale) -- the same values through the existing
+    operators."""
+    gidx, scale = _gine_args(graph, x, w, scale)
+    if gidx.num_edges() == 0:  # no message: zeros (tied to x and w so that both get a zero gradient), no kernel of this library
+        return x.new_zeros((gidx.num_dst, x.shape[1])) + (x[:0].sum() + w.sum())
+    if not gine_sum_fused(gidx, x, w, scale):
+        m = torch.relu(gsddmm(gidx, "copy_lhs", x, None, "u", "v") + w)
+        if scale is not None:
+            m = m * scale.unsqueeze(-1)
+        return gspmm(gidx, "copy_rhs", "sum", None, m)
+    return GineSum.apply(gidx, x, w, scale)
 
 
 class HeadDot(torch.autograd.Function):

@@ -926,6 +926,43 @@ class HipBackend(object):
                                                         _ptr(dv), _ptr(ws), _stream(dev)))
         return dq, dk, dv
 
+    # ---- sum of relu(x_u + w_e) messages (csrc/gine.hip)
+    @staticmethod
+    def gine_supported(csr, D):
+        """Shapes mgx_gine_* takes: D % 4 == 0, 4 <= D <= 256, 32-bit indices, at least one edge, x / w / d_w below 4 GiB each."""
+        return bool(_lib.lib().mgx_gine_supported(ctypes.byref(csr.c_struct()), D))
+
+    def _gine_ws(self, plan, D, dev):
+        need = _lib.lib().mgx_gine_workspace(self._plan_ptr(plan), D)
+        return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+
+    def gine_fwd(self, csc, x2d, w2d, scale1d):
+        """x2d [n_src, D], w2d [E, D] and scale1d [E] | None by edge id (all contiguous) -> out [n_dst, D]."""
+        dev = self._check_dev(csc.indptr, x2d, w2d, scale1d)
+        D = int(x2d.shape[1])
+        out = torch.empty((csc.num_rows, D), dtype=torch.float32, device=dev)
+        plan = csc.plan()
+        ws = self._gine_ws(plan, D, dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="gine_fwd", D=D, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
+            _lib.check(_lib.lib().mgx_gine_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), D, _ptr(x2d), _ptr(w2d), _ptr(scale1d),
+                                               _ptr(out), _ptr(ws), _stream(dev)))
+        return out
+
+    def gine_bwd(self, csr, x2d, w2d, scale1d, d_out2d, need_x, need_w):
+        """csr: the out-CSR (rows = sources) -> (d_x [n_src, D] | None, d_w [E, D] by edge id | None)."""
+        dev = self._check_dev(csr.indptr, x2d, w2d, scale1d, d_out2d)
+        D = int(x2d.shape[1])
+        if not (need_x or need_w):
+            return None, None
+        d_x = torch.empty((csr.num_rows, D), dtype=torch.float32, device=dev) if need_x else None
+        d_w = torch.empty((csr.nnz, D), dtype=torch.float32, device=dev) if need_w else None
+        plan = csr.plan()
+        ws = self._gine_ws(plan, D, dev) if need_x else None
+        with torch.cuda.device(dev), timed_call(dev, kernel="gine_bwd", D=D, nnz=csr.nnz, n_src=csr.num_rows, n_dst=csr.num_cols):
+            _lib.check(_lib.lib().mgx_gine_bwd(ctypes.byref(csr.c_struct()), self._plan_ptr(plan), D, _ptr(x2d), _ptr(w2d), _ptr(scale1d),
+                                               _ptr(d_out2d), _ptr(d_x), _ptr(d_w), _ptr(ws), _stream(dev)))
+        return d_x, d_w
+
     @staticmethod
     def head_dot_supported(H, F):
         return H * F <= 256 and (F <= 64 or F in (128, 256))

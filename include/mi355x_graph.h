@@ -449,6 +449,40 @@ int32_t mgx_dot_attention_bwd(const mgx_csr* csc, const mgx_spmm_plan* csc_plan 
                               const float* k, int64_t k_ld, const float* v, int64_t v_ld, float scale, const float* out,
                               const float* d_out, float* stat, float* dq, float* dk, float* dv, void* workspace, void* stream);
 
+/* Sum aggregation of relu(x_u + w_e) messages with NO E-sized temporary (the UDF message of main_dgl_molhiv_gcn.py:37-52 and
+ * main_dgl_ppa_gcn.py:44-51 reduced with fn.sum; with scale = NULL upstream's dgl.nn.GINEConv; csrc/gine.hip):
+ *   out[v,:] = sum_{e: u->v} s[e] * relu(x[u,:] + w[e,:])             (exactly 0 for a destination without in-edges)
+ *   fwd: ONE walk of the in-CSR `csc`; w and s are indexed by EDGE ID: position p of the CSR reads w[eid(p)], s[eid(p)] with
+ *        eid(p) = csc->eids[p], or p when eids is NULL.  scale NULL means s = 1.  Nothing of size E is written or kept.
+ *   bwd: ONE walk of the transpose `csr` (rows = source nodes, its eids the same edge ids), where every edge is met exactly once:
+ *        m[e,:] = s[e] * 1[x[u,:] + w[e,:] > 0] * d_out[v,:],   d_w[e,:] = m[e,:] (written exactly once per edge),
+ *        d_x[u,:] = sum_{e: u->...} m[e,:] (exactly 0 for a source without out-edges).  d_x and d_w may each be NULL; s gets no gradient.
+ *        The mask is recomputed from x and w (x[u,:] is loaded once per work item): fp32 x + w is one rounding, its sign is exact, so
+ *        forward and backward agree on it.  relu'(0) = 0.
+ * A NaN in x[u,c] + w[e,c] makes out[v,c] NaN and leaves every other (row, column) bitwise untouched; gradients at such an element
+ * are unspecified.  +inf passes through.
+ * x [csc->num_cols, D], w [nnz, D], scale [nnz], out [csc->num_rows, D]; d_out [csr->num_cols, D], d_x [csr->num_rows, D],
+ * d_w [nnz, D]: fp32, dense, 16-byte aligned, allocated by the caller.
+ * Supported (mgx_gine_supported): D % 4 == 0 and 4 <= D <= 256 (one pass of a wave; wider rows are NOT taken), 32-bit indices,
+ * nnz > 0, and max(num_rows, num_cols, nnz) * D * 4 below 4 GiB -- gathered rows, w and d_w included, are addressed by 32-bit byte
+ * offsets, so a graph whose nnz * D * 4 reaches 4 GiB is refused rather than addressed with 64-bit offsets.
+ * Errors: a D that is not a positive multiple of 4, NULL or misaligned operands and a malformed plan are MGX_ERR_INVALID_ARGUMENT;
+ * D > 256, 64-bit indices, nnz == 0 and operands of 4 GiB are MGX_ERR_UNSUPPORTED (the caller composes mgx_sddmm_* and mgx_spmm_csr).
+ * The argument checks of the graph, D and the plan come before the supported-set checks: a malformed plan on an empty graph is an argument error.
+ * plan: the CSR's mgx_spmm_plan or NULL (one work item per row); workspace: mgx_gine_workspace(plan, D) bytes (NULL when the plan
+ * splits no row; the backward needs it only for d_x).  Nothing is read back to the host: every entry point can be captured in a graph.
+ * mgx_last_spmm_kernel(): "gine_fwd" / "gine_bwd" after the respective launch.
+ * Deterministic: no atomics, lane groups merged in a fixed order, hub partial sums combined in slot order -- the result is a function
+ * of the arguments only.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_gine_supported(const mgx_csr* csr, int64_t D);
+int64_t mgx_gine_workspace(const mgx_spmm_plan* plan /* may be NULL */, int64_t D);
+int32_t mgx_gine_fwd(const mgx_csr* csc, const mgx_spmm_plan* plan /* may be NULL */, int64_t D, const float* x /* [num_cols, D] */,
+                     const float* w /* [nnz, D] by edge id */, const float* scale /* [nnz] by edge id, or NULL */,
+                     float* out /* [num_rows, D] */, void* workspace, void* stream);
+int32_t mgx_gine_bwd(const mgx_csr* csr /* transpose: rows = sources */, const mgx_spmm_plan* plan /* may be NULL */, int64_t D,
+                     const float* x, const float* w, const float* scale, const float* d_out /* [csr->num_cols, D] */,
+                     float* d_x /* or NULL */, float* d_w /* or NULL */, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ GAT attention terms
  * el[n,h] = sum_f feat[n,h,f] * attn[h,f] -- GATConv's `(feat * attn_l).sum(-1)` (main_dgl_reddit_gat.py:10, UPSTREAM
  * dgl.nn.pytorch.GATConv.forward), one pass; attn_b/out_b (may be NULL) apply a second attention vector to the same
