@@ -59,6 +59,11 @@ struct SpmmFastArgs {
                    // 2: ... and this is the head of a two-part plan (no item above 32 edges)
   int lds;    // row stride of `src` in floats (>= D; == D unless mgx_spmm_copy_u_strided)
   int ldo;    // row stride of `out` in floats
+  // mgx_spmm_copy_u_strided_init (the INIT instantiations only): row v's sum starts from init[init_pos[v] * ldi + :] where
+  // init_pos[v] >= 0, from +0.0f elsewhere; `out` is never read
+  const float* init;
+  const int64_t* init_pos;
+  int ldi;
 };
 
 // Work items per workgroup.  Workgroups are dispatched in blockIdx order, so a SMALL value makes
@@ -319,7 +324,10 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave_kernel(const SpmmFastArgs
 // (dword-aligned accesses); the lane that owns the last 1-3 columns loads the LAST FOUR floats of the row instead -- no
 // read past the row, its own columns are the tail components of that window -- and only the epilogue distinguishes it.
 // (8 waves per SIMD -- 64 VGPRs, two spilled -- was measured and changes nothing: profiles/r02_spmm_variants.txt.)
-template <int VEC, int G, int MODE, int WMODE, bool LANEMASK, bool RAGGED = false, bool MASKED = false>
+// INIT (mgx_spmm_copy_u_strided_init; plain copy_u sums only): the accumulating launch whose initial value comes from a COMPACT matrix --
+// a.init[a.init_pos[row]] where the map says so, +0.0f elsewhere -- and never from `out`, which is write-only.  The map entry of the NEXT
+// item's row is fetched with that item's bounds, so the initial-value load is the one round trip the accumulating launch pays.
+template <int VEC, int G, int MODE, int WMODE, bool LANEMASK, bool RAGGED = false, bool MASKED = false, bool INIT = false>
 __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastArgs<int32_t> a) {
   typedef typename VecT<VEC>::type VA;
   typedef VA VU __attribute__((aligned(4)));  // RAGGED: gathers / stores are only dword-aligned
@@ -347,7 +355,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastAr
   const char* __restrict__ srcb = reinterpret_cast<const char*>(a.src);
   const int bidx0 = sub * 4;  // byte index of this lane group's first edge for ds_bpermute
 
-  auto load_meta = [&](int64_t item, int64_t& row, int32_t& beg, int32_t& end) {
+  auto load_meta = [&](int64_t item, int64_t& row, int32_t& beg, int32_t& end, int32_t& ipos) {
     if (a.item_row) {
       row = (int64_t)a.item_row[item];
       beg = a.item_beg[item];
@@ -357,6 +365,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastAr
       beg = a.indptr[item];
       end = a.indptr[item + 1];
     }
+    if (INIT) ipos = row >= 0 ? (int32_t)a.init_pos[row] : -1;  // (a chunk of a split row starts from zero: its row's value enters in the fix-up)
   };
   // lane j's slice of the edge list: byte offset of the gathered row, edge id, per-edge scalar
   // `cnt`: edges of this 64-edge chunk to gather.  MASKED (row-sparse gathered matrix, e.g. the gradient of a loss taken on
@@ -439,8 +448,8 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastAr
   if (r >= a.rpb || item_base + r >= item_stop) return;
   const bool early_accum = a.accum && !a.mean && a.dst_scale == nullptr;  // wave-uniform: see the accumulator's initial value below
   int64_t row;
-  int32_t beg, end;
-  load_meta(item_base + r, row, beg, end);
+  int32_t beg, end, ipos = -1;
+  load_meta(item_base + r, row, beg, end, ipos);
   uint32_t goff;
   int32_t eid;
   float sc;
@@ -453,13 +462,13 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastAr
     const int rn = r + kWavesPerBlock;
     const bool has_next = rn < a.rpb && item_base + rn < item_stop;
     int64_t nrow = 0;
-    int32_t nbeg = 0, nend = 0, neid = 0;
+    int32_t nbeg = 0, nend = 0, neid = 0, nipos = -1;
     uint32_t ngoff = 0;
     float nsc = 1.f;
     int ncnt0 = 0;
     int32_t ngidx = -1;
     if (has_next) {
-      load_meta(item_base + rn, nrow, nbeg, nend);
+      load_meta(item_base + rn, nrow, nbeg, nend, nipos);
       load_ids(nbeg, nend, ngoff, neid, nsc, ncnt0, ngidx);
     }
     // out += result (MGX_SPMM_ACCUMULATE: the backward aggregation of the one-node SAGE layer): the row to add to is requested
@@ -467,8 +476,14 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastAr
     // (products D = 64: the accumulating launch ran 2.63 ms against 2.26 ms for the plain one for 0.11 ms worth of bytes)
     // -- as the INITIAL value of lane group 0's accumulator (no register of its own: 65 VGPRs, 7 waves per SIMD as before), which is
     // exact when nothing scales the sum afterwards (no mean, no dst_scale: the backward launches); scaled sums add it in the epilogue.
+    // INIT: the same place, the value read from the compact matrix -- for the listed rows only; every other row starts from +0.0f
     V acc = (V)(0.f);
-    if (early_accum && row >= 0 && factive && sub == 0 && !tail) acc = *reinterpret_cast<const V*>(a.out + row * (int64_t)a.ldo + f);
+    if (INIT) {
+      if (ipos >= 0 && factive && sub == 0)  // (32-bit byte offsets like the gathers: the entry point checked that `init` is under 4 GiB)
+        acc = *reinterpret_cast<const V*>(reinterpret_cast<const char*>(a.init) + ((uint32_t)ipos * ((uint32_t)a.ldi * 4u) + (uint32_t)f * 4u));
+    } else if (early_accum && row >= 0 && factive && sub == 0 && !tail) {
+      acc = *reinterpret_cast<const V*>(a.out + row * (int64_t)a.ldo + f);
+    }
     for (int32_t cbase = beg; cbase < end; cbase += kWave) {
       int cnt = cnt0;
       if (cbase != beg) {
@@ -509,7 +524,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastAr
       if (!tail) {
         if (row >= 0) {  // separate pointers: the output store keeps its non-temporal hint
           float* op = a.out + row * (int64_t)a.ldo + f;
-          if (a.accum && !early_accum) acc += *reinterpret_cast<const V*>(op);
+          if (!INIT && a.accum && !early_accum) acc += *reinterpret_cast<const V*>(op);
           __builtin_nontemporal_store((VA)acc, reinterpret_cast<V*>(op));
         } else {
           *reinterpret_cast<V*>(a.partial + (-(row + 1)) * (int64_t)a.D + f) = acc;
@@ -526,7 +541,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastAr
     }
     if (!has_next) break;
     r = rn;
-    row = nrow; beg = nbeg; end = nend;
+    row = nrow; beg = nbeg; end = nend; ipos = nipos;
     goff = ngoff; eid = neid; sc = nsc;
     cnt0 = ncnt0;
     if (MASKED) mask_compact(nword, ngidx, goff, cnt0);
@@ -546,7 +561,9 @@ __global__ __launch_bounds__(kBlock) void spmm_rowwave32_kernel(const SpmmFastAr
 // matrix below 4 GiB, D % 4 == 0.  The next batch's bounds and ids are requested before the current batch's gathers.
 // LONG = false: the head of a two-part plan, whose items are short by contract -- the whole-wave path for long items is compiled out
 // (registers: see launch_rowgroup32); a longer item would still be summed correctly, by its lane group alone.
-template <int VEC, int G, int MODE, bool LANEMASK, bool LONG>
+// INIT (mgx_spmm_copy_u_strided_init): the value a row's sum is added to comes from a.init[a.init_pos[row]] (+0.0f where the map says -1)
+// instead of from `out`; its map entry travels with the item's bounds and the value is requested before the gathers.
+template <int VEC, int G, int MODE, bool LANEMASK, bool LONG, bool INIT = false>
 __global__ __launch_bounds__(kBlock) void spmm_rowgroup32_kernel(const SpmmFastArgs<int32_t> a) {
   typedef typename VecT<VEC>::type V;
   constexpr int NB = kWave / G;
@@ -566,7 +583,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowgroup32_kernel(const SpmmFastA
   const char* __restrict__ srcb = reinterpret_cast<const char*>(a.src);
   const int gbase = sub * G;
 
-  auto load_meta = [&](int r, bool& ok, int64_t& row, int32_t& beg, int32_t& end) {
+  auto load_meta = [&](int r, bool& ok, int64_t& row, int32_t& beg, int32_t& end, int32_t& ipos) {
     const int64_t item = item_base + r;
     ok = r < a.rpb && item < item_stop;
     row = 0; beg = 0; end = 0;
@@ -581,6 +598,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowgroup32_kernel(const SpmmFastA
         end = a.indptr[item + 1];
       }
     }
+    if (INIT) ipos = (ok && row >= 0) ? (int32_t)a.init_pos[row] : -1;
   };
   auto load_ids = [&](int32_t base, int32_t end) -> uint32_t {  // lane l of the group: byte offset of neighbour base + l
     const int32_t q = base + l;
@@ -597,21 +615,24 @@ __global__ __launch_bounds__(kBlock) void spmm_rowgroup32_kernel(const SpmmFastA
   int r = wave * NB + sub;  // this group's item inside the workgroup's stretch; batches of kWavesPerBlock * NB items
   bool ok;
   int64_t row;
-  int32_t beg, end;
-  load_meta(r, ok, row, beg, end);
+  int32_t beg, end, ipos = -1;
+  load_meta(r, ok, row, beg, end, ipos);
   uint32_t goff = load_ids(beg, end);
   for (;;) {
     const int rn = r + kWavesPerBlock * NB;
     const bool more = __builtin_amdgcn_readfirstlane(rn - sub) < a.rpb && item_base + (rn - sub) < item_stop;  // wave-uniform
     bool nok = false;
     int64_t nrow = 0;
-    int32_t nbeg = 0, nend = 0;
+    int32_t nbeg = 0, nend = 0, nipos = -1;
     uint32_t ngoff = 0;
     if (more) {
-      load_meta(rn, nok, nrow, nbeg, nend);
+      load_meta(rn, nok, nrow, nbeg, nend, nipos);
       ngoff = load_ids(nbeg, nend);
     }
     V acc = (V)(0.f);
+    V iv = (V)(0.f);  // INIT: what the epilogue adds the sum to, requested here so that it travels under the gathers
+    if (INIT && ipos >= 0 && factive)
+      iv = *reinterpret_cast<const V*>(reinterpret_cast<const char*>(a.init) + ((uint32_t)ipos * ((uint32_t)a.ldi * 4u) + (uint32_t)f * 4u));
     // items longer than kLong edges are NOT walked by their lane group alone (one group gathering 256 edges, 4 in flight, is 64
     // dependent round trips -- the tail of the whole launch on a skewed graph): the wave takes them together below
     const bool deferred = LONG && ok && (end - beg) > kLong;
@@ -681,7 +702,8 @@ __global__ __launch_bounds__(kBlock) void spmm_rowgroup32_kernel(const SpmmFastA
         }
         if (a.dst_scale) acc = acc * a.dst_scale[row];
         float* op = a.out + row * (int64_t)a.ldo + f;
-        if (a.accum) acc += *reinterpret_cast<const V*>(op);
+        if (INIT) acc += iv;
+        else if (a.accum) acc += *reinterpret_cast<const V*>(op);
         __builtin_nontemporal_store(acc, reinterpret_cast<V*>(op));
       } else {
         *reinterpret_cast<V*>(a.partial + (-(row + 1)) * (int64_t)a.D + f) = acc;
@@ -689,7 +711,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rowgroup32_kernel(const SpmmFastA
     }
     if (!more) break;
     r = rn;
-    ok = nok; row = nrow; beg = nbeg; end = nend; goff = ngoff;
+    ok = nok; row = nrow; beg = nbeg; end = nend; goff = ngoff; ipos = nipos;
   }
 }
 
@@ -709,6 +731,19 @@ static bool launch_rowgroup32(SpmmFastArgs<int32_t> a, int64_t nnz, hipStream_t 
     note_spmm_kernel("rowgroup32");
     a.rpb = 2 * kWavesPerBlock * NB;  // two batches per wave: the second's ids travel under the first's gathers
     const dim3 grid((unsigned)xcd_ranges(a.plan, a.n_items, a.rpb, a.xcd), (unsigned)((a.D + G * VEC - 1) / (G * VEC)));
+    if (a.init_pos) {  // mgx_spmm_copy_u_strided_init (plain copy_u sums: its entry point checked)
+      if constexpr (MODE == MODE_COPY_LHS) {
+        const bool lm = a.D % (G * VEC) != 0;
+        if (a.short_rows == 2) {
+          if (lm) hipLaunchKernelGGL((spmm_rowgroup32_kernel<VEC, G, MODE, true, false, true>), grid, dim3(kBlock), 0, s, a);
+          else hipLaunchKernelGGL((spmm_rowgroup32_kernel<VEC, G, MODE, false, false, true>), grid, dim3(kBlock), 0, s, a);
+        } else {
+          if (lm) hipLaunchKernelGGL((spmm_rowgroup32_kernel<VEC, G, MODE, true, true, true>), grid, dim3(kBlock), 0, s, a);
+          else hipLaunchKernelGGL((spmm_rowgroup32_kernel<VEC, G, MODE, false, true, true>), grid, dim3(kBlock), 0, s, a);
+        }
+      }
+      return true;
+    }
     if (a.short_rows == 2) {  // head of a two-part plan: every item short
       if (a.D % (G * VEC) != 0) hipLaunchKernelGGL((spmm_rowgroup32_kernel<VEC, G, MODE, true, false>), grid, dim3(kBlock), 0, s, a);
       else hipLaunchKernelGGL((spmm_rowgroup32_kernel<VEC, G, MODE, false, false>), grid, dim3(kBlock), 0, s, a);
@@ -724,18 +759,23 @@ static bool launch_rowgroup32(SpmmFastArgs<int64_t>, int64_t, hipStream_t) { ret
 
 // Sums the partial slots of every split (hub) row in slot order -- deterministic -- and applies
 // the mean / dst_scale epilogue.  One wave per hub row, lanes along the feature dimension.
-template <typename Idx>
+// INIT (mgx_spmm_copy_u_strided_init): the total is added to init[init_pos[row]] (+0.0f where the map says -1), never to `out`.
+template <typename Idx, bool INIT = false>
 __global__ __launch_bounds__(kBlock) void spmm_hub_fixup_kernel(const Idx* indptr, const int32_t* hub_row,
                                                                 const int32_t* hub_slot_ptr, int64_t num_hubs,
                                                                 const float* partial, const float* dst_scale,
-                                                                float* out, int D, int mean, int accum, int ldo) {
+                                                                float* out, int D, int mean, int accum, int ldo,
+                                                                const float* init = nullptr, const int64_t* init_pos = nullptr, int ldi = 0) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t h = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
   if (h >= num_hubs) return;
   const int64_t row = hub_row[h];
   const int s0 = hub_slot_ptr[h], s1 = hub_slot_ptr[h + 1];
   float scale = 1.f;
+  const int64_t ipos = INIT ? init_pos[row] : -1;
   for (int k = lane; k < D; k += kWave) {
+    float iv = 0.f;  // requested before the slots are walked
+    if (INIT && ipos >= 0) iv = init[ipos * ldi + k];
     float acc = 0.f;
     int s = s0;
     for (; s + 4 <= s1; s += 4) {  // four slots in flight, added in slot order (the same bits as one at a time)
@@ -749,7 +789,8 @@ __global__ __launch_bounds__(kBlock) void spmm_hub_fixup_kernel(const Idx* indpt
       acc = acc / (float)(deg > 1 ? deg : 1);
     }
     if (dst_scale) acc *= dst_scale[row];
-    if (accum) acc += out[row * ldo + k];
+    if (INIT) acc += iv;
+    else if (accum) acc += out[row * ldo + k];
     out[row * ldo + k] = acc * scale;
   }
 }
@@ -877,6 +918,13 @@ static bool launch_rowwave32(const SpmmFastArgs<int32_t>& a, int64_t src_rows, d
   int wmode = 0;
   if (MODE == MODE_MUL_EDGE) wmode = a.H == 1 ? 1 : 2;
   else if (a.src_scale) wmode = 1;
+  if (a.init_pos) {  // mgx_spmm_copy_u_strided_init: plain copy_u sums with 16-byte lanes (its entry point checked)
+    if constexpr (MODE == MODE_COPY_LHS && VEC == 4) {
+      if (lanemask) hipLaunchKernelGGL((spmm_rowwave32_kernel<VEC, G, MODE, 0, true, false, false, true>), grid, dim3(kBlock), 0, s, a);
+      else hipLaunchKernelGGL((spmm_rowwave32_kernel<VEC, G, MODE, 0, false, false, false, true>), grid, dim3(kBlock), 0, s, a);
+    }
+    return true;
+  }
   if (MODE == MODE_COPY_LHS && a.src_bits && wmode == 0) {  // row-sparse gathered matrix: skip rows flagged all-zero
     if (lanemask) hipLaunchKernelGGL((spmm_rowwave32_kernel<VEC, G, MODE, 0, true, false, true>), grid, dim3(kBlock), 0, s, a);
     else hipLaunchKernelGGL((spmm_rowwave32_kernel<VEC, G, MODE, 0, false, false, true>), grid, dim3(kBlock), 0, s, a);
@@ -991,7 +1039,8 @@ static int32_t spmm_impl(const mgx_csr* csr, const mgx_spmm_plan* plan, float* p
                          int64_t u_len, int64_t e_len, int64_t out_len, const int64_t* u_off,
                          const int64_t* e_off, const float* src_scale, const float* dst_scale, float* out,
                          void* arg_u, void* arg_e, hipStream_t s, const uint32_t* src_bits = nullptr, int64_t u_stride = 0,
-                         int64_t out_stride = 0, const void* slots = nullptr, const void* edge_tail = nullptr) {
+                         int64_t out_stride = 0, const void* slots = nullptr, const void* edge_tail = nullptr, const float* init = nullptr,
+                         const int64_t* init_pos = nullptr, int64_t init_stride = 0) {
   const int64_t n_rows = csr->num_rows;
   const int accumulate = (flag_bits & MGX_SPMM_ACCUMULATE) ? 1 : 0;
   if (n_rows == 0 || out_len == 0) return MGX_OK;
@@ -1005,11 +1054,13 @@ static int32_t spmm_impl(const mgx_csr* csr, const mgx_spmm_plan* plan, float* p
     mgx_spmm_plan head = *plan;
     head.rest = nullptr;
     int32_t st = spmm_impl<Idx>(csr, &head, partial_ws, flag_bits | kSpmmPartialPlan, op, reduce, U, E, u_len, e_len, out_len, u_off, e_off,
-                                src_scale, dst_scale, out, arg_u, arg_e, s, src_bits, u_stride, out_stride, slots, edge_tail);
+                                src_scale, dst_scale, out, arg_u, arg_e, s, src_bits, u_stride, out_stride, slots, edge_tail, init, init_pos,
+                                init_stride);
     if (st != MGX_OK) return st;
     const char* head_kernel = mgx_last_spmm_kernel();
     st = spmm_impl<Idx>(csr, plan->rest, partial_ws, (flag_bits & ~MGX_SPMM_SHORT_ROWS) | kSpmmPartialPlan, op, reduce, U, E, u_len, e_len,
-                        out_len, u_off, e_off, src_scale, dst_scale, out, arg_u, arg_e, s, src_bits, u_stride, out_stride, slots, edge_tail);
+                        out_len, u_off, e_off, src_scale, dst_scale, out, arg_u, arg_e, s, src_bits, u_stride, out_stride, slots, edge_tail, init,
+                        init_pos, init_stride);
     if (slots && st == MGX_OK) return st;  // (the name of the family that walked `rest` -- "slots" or not -- is what a caller of the packed form asks for)
     note_spmm_kernel(head_kernel);  // the family that walked the short items (the bulk of such a plan)
     return st;
@@ -1040,6 +1091,7 @@ static int32_t spmm_impl(const mgx_csr* csr, const mgx_spmm_plan* plan, float* p
     a.ragged = 0;
     a.lds = u_stride ? (int)u_stride : (int)out_len;
     a.ldo = out_stride ? (int)out_stride : (int)out_len;
+    a.init = init; a.init_pos = init_pos; a.ldi = (int)init_stride;
     a.item_row = nullptr; a.item_beg = nullptr; a.item_end = nullptr; a.partial = nullptr; a.n_items = n_rows;
     a.plan = plan;
     if (plan) {
@@ -1048,7 +1100,12 @@ static int32_t spmm_impl(const mgx_csr* csr, const mgx_spmm_plan* plan, float* p
     }
     MGX_CHECK_ARG(a.n_items / 4 < (int64_t(1) << 31) - 16, "mgx_spmm_csr: too many work items");
     auto fixup = [&]() -> int32_t {
-      if (plan && plan->num_hubs > 0) {
+      if (plan && plan->num_hubs > 0 && init_pos) {
+        hipLaunchKernelGGL((spmm_hub_fixup_kernel<Idx, true>), dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)),
+                           dim3(kBlock), 0, s, a.indptr, plan->hub_row, plan->hub_slot_ptr, plan->num_hubs,
+                           (const float*)partial_ws, dst_scale, out, a.D, a.mean, a.accum, a.ldo, init, init_pos, a.ldi);
+        MGX_CHECK_LAUNCH();
+      } else if (plan && plan->num_hubs > 0) {
         hipLaunchKernelGGL((spmm_hub_fixup_kernel<Idx>), dim3((unsigned)((plan->num_hubs + kWavesPerBlock - 1) / kWavesPerBlock)),
                            dim3(kBlock), 0, s, a.indptr, plan->hub_row, plan->hub_slot_ptr, plan->num_hubs,
                            (const float*)partial_ws, dst_scale, out, a.D, a.mean, a.accum, a.ldo);
@@ -1236,6 +1293,34 @@ extern "C" int32_t mgx_spmm_copy_u_strided(const mgx_csr* csr, const mgx_spmm_pl
   return spmm_impl<int32_t>(csr, plan, partial_ws, flags & (MGX_SPMM_ACCUMULATE | MGX_SPMM_SHORT_ROWS), MGX_OP_COPY_LHS, reduce, ufeat, nullptr, D, 0,
                             D, nullptr, nullptr, nullptr, dst_scale, out, nullptr, nullptr, (hipStream_t)stream, nullptr, u_stride,
                             out_stride);
+}
+
+extern "C" int32_t mgx_spmm_copy_u_strided_init(const mgx_csr* csr, const mgx_spmm_plan* plan, int32_t reduce, const float* ufeat, int64_t D,
+                                                int64_t u_stride, const float* dst_scale, const float* init, int64_t init_rows,
+                                                int64_t init_stride, const int64_t* init_pos, float* out, int64_t out_stride, float* partial_ws, int32_t flags,
+                                                void* stream) {
+  using namespace mgx;
+  MGX_ENTER();
+  MGX_CHECK_ARG(csr != nullptr, "mgx_spmm_copy_u_strided_init: csr is NULL");
+  MGX_CHECK_ARG(csr->num_rows >= 0 && csr->nnz >= 0, "mgx_spmm_copy_u_strided_init: negative sizes");
+  MGX_CHECK_ARG(csr->num_rows == 0 || csr->indptr != nullptr, "mgx_spmm_copy_u_strided_init: indptr is NULL");
+  MGX_CHECK_ARG(csr->nnz == 0 || csr->indices != nullptr, "mgx_spmm_copy_u_strided_init: indices is NULL");
+  MGX_CHECK_ARG(reduce == MGX_REDUCE_SUM || reduce == MGX_REDUCE_MEAN, "mgx_spmm_copy_u_strided_init: SUM or MEAN only, got %d", reduce);
+  MGX_CHECK_ARG(D >= 0 && u_stride >= D && out_stride >= D && init_stride >= D && init_rows >= 0,
+                "mgx_spmm_copy_u_strided_init: strides must be >= D, init_rows >= 0");
+  MGX_CHECK_ARG((ufeat != nullptr || csr->num_cols == 0) && (out != nullptr || csr->num_rows == 0 || D == 0),
+                "mgx_spmm_copy_u_strided_init: ufeat / out is NULL");
+  MGX_CHECK_ARG(init_pos != nullptr || csr->num_rows == 0, "mgx_spmm_copy_u_strided_init: init_pos is NULL");
+  MGX_CHECK_ARG(init != nullptr || init_rows == 0, "mgx_spmm_copy_u_strided_init: init is NULL");
+  if (csr->idx_bits != 32 || reduce != MGX_REDUCE_SUM || dst_scale != nullptr || D % 4 != 0 || u_stride % 4 != 0 || out_stride % 4 != 0 ||
+      init_stride % 4 != 0 || (uintptr_t)ufeat % 16 != 0 || (uintptr_t)out % 16 != 0 || (uintptr_t)init % 16 != 0 ||
+      csr->num_cols * u_stride * 4 >= (int64_t(1) << 32) || init_rows * init_stride * 4 >= (int64_t(1) << 32))
+    MGX_UNSUPPORTED("mgx_spmm_copy_u_strided_init: plain sums (no mean, no dst_scale) on int32 graphs, D and the three strides multiples "
+                    "of 4, 16-byte aligned pointers, gathered and initial matrix under 4 GiB");
+  // (strides equal to D are passed as such: spmm_impl treats 0 as "contiguous")
+  return spmm_impl<int32_t>(csr, plan, partial_ws, MGX_SPMM_ACCUMULATE | (flags & MGX_SPMM_SHORT_ROWS), MGX_OP_COPY_LHS, reduce, ufeat, nullptr,
+                            D, 0, D, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, (hipStream_t)stream, nullptr, u_stride, out_stride,
+                            nullptr, nullptr, init, init_pos, init_stride);
 }
 
 extern "C" int32_t mgx_edge_tail_fill(const mgx_csr* csr, const float* x, int64_t x_stride, float* edge_tail, void* stream) {

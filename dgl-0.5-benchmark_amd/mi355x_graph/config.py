@@ -20,6 +20,8 @@ SAGE_FUSED_ADD = True      # fc_self(h) + fc_neigh(neigh) as two GEMMs, the seco
 SAGE_FUSED_ACT = True      # relu + dropout in the layer GEMM's epilogue (mgx_rows_gemm_relu_dropout)
 SAGE_PROJECT_FIRST = True  # project before aggregating when that moves fewer columns (reddit: 602 -> 16)
 SAGE_HEAD_ROWS = True      # the last layer's dense work on the loss rows only (ops.SageMeanCatHeadFn; MGX_SAGE_HEAD_ROWS=0 turns it off)
+SAGE_HEAD_INIT = True      # ... its reversed aggregation started from the compact d self (mgx_spmm_copy_u_strided_init), d neigh / deg scattered into
+                           # one [N, K] matrix kept zero elsewhere between steps (ops._head_dn): no zero fill, no copy of d self into one
 ROWS_GEMM = True           # mgx_rows_gemm for the projections of a layer over >= 65 536 rows (else the library GEMM)
 LINEAR_XTY = True          # tall-skinny weight gradients by mgx_xty (else the library GEMM)
 XTY_COLSUM = True          # ... with the bias gradient from the same pass (mgx_xty_colsum)

@@ -1239,6 +1239,33 @@ def _head_rows_forward(be, gidx, cat, h, w_self, w_neigh, bias, rows):
     return y
 
 
+def _head_dn(csr, K, rows, n, like):
+    """The [N, K] matrix SageMeanCatHeadFn's backward scatters d neigh / deg into, zero outside `rows`: ONE matrix, kept between steps
+    instead of a zero fill per step (config.SAGE_HEAD_INIT) -- on the CSR the reversed aggregation gathers it over, which lives as long
+    as the graph (the CatBuffer of a hidden layer's output is a new one every forward pass; steps over one graph run one after the
+    other on one stream, like everything else that shares its formats and plans).  The scatter overwrites all K columns of every listed row,
+    so with the list of the last step -- the same tensor object, unwritten (version counter), as for the _ROW_* caches -- nothing needs
+    clearing; with another list the rows of the previous one are cleared first (the whole matrix when that list was written to since).
+    Internal to the node: the aggregation reads it, autograd never sees it.  Inside a HIP-graph capture the step gets a zero matrix
+    of its own, filled in the captured step: a replay runs none of this bookkeeping, and eager steps with other lists in between
+    must not leave their rows in what it reads."""
+    if torch.cuda.is_current_stream_capturing():
+        return torch.zeros((n, K), dtype=like.dtype, device=like.device)
+    held = csr._head_dn
+    if held is None or held[0].shape != (n, K) or held[0].dtype != like.dtype or held[0].device != like.device:
+        buf = torch.zeros((n, K), dtype=like.dtype, device=like.device)
+    else:
+        buf, prev, version = held
+        if prev is rows and version == rows._version:
+            pass
+        elif prev._version == version:
+            buf.index_fill_(0, prev, 0.0)
+        else:
+            buf.zero_()
+    csr._head_dn = (buf, rows, rows._version)
+    return buf
+
+
 def _head_rows_dense_backward(be, gidx, cat, w_self, w_neigh, dyr, rows, need_dh, need_w, need_b, zero_fill):
     """The dense half of the backward of _head_rows_forward from dyr [R, out], all of it on the R listed rows:
     (d_self [R, K] compact, dn [N, K] = d neigh / deg on the listed rows -- the other rows zero (zero_fill) or unwritten --, dW_self,
@@ -1247,7 +1274,10 @@ def _head_rows_dense_backward(be, gidx, cat, w_self, w_neigh, dyr, rows, need_dh
     d_self = dn = dws = dwn = db = None
     if need_dh:
         wcat = torch.cat([w_self, w_neigh], dim=1)  # [out, 2K]
-        dn = (torch.zeros if zero_fill else torch.empty)((n, K), dtype=dyr.dtype, device=dyr.device)
+        if zero_fill and config.SAGE_HEAD_INIT:
+            dn = _head_dn(gidx.csr(), K, rows, n, dyr)
+        else:
+            dn = (torch.zeros if zero_fill else torch.empty)((n, K), dtype=dyr.dtype, device=dyr.device)
         inv_r = _row_inv_deg(rows, gidx.csc().inv_degrees())
         pair = None
         if config.ROWS_GEMM and K % 4 == 0:
@@ -1279,7 +1309,10 @@ class SageMeanCatHeadFn(torch.autograd.Function):
     default): the projection, its input gradient and the weight / bias gradients run over the R listed rows through the row-list
     operands of mgx_rows_gemm_rows and the position map of mgx_xty_colsum_pos instead of over all N rows, of which the loss reads 8 % on ogbn-products.
     Both aggregations are untouched: every row is aggregated forward, and the reversed one gathers every source row over every edge
-    from d neigh / deg, which is zero outside the rows (a zero-filled [N, K] the GEMM scatters into), accumulating into d self.
+    from d neigh / deg, which is zero outside the rows: an [N, K] matrix the GEMM scatters into, kept zero elsewhere from step to step
+    (_head_dn).  Its sums start from d self, which stays the compact [R, K] matrix the GEMM wrote: the aggregation takes it through
+    the position map (mgx_spmm_copy_u_strided_init) and writes every row of d h once.  config.SAGE_HEAD_INIT = False, or operands
+    that entry point declines: a zero-filled [N, K] per step, d self copied into a second one, the accumulating aggregation.
     Every sum is formed in the order the layer over all rows forms it, so the gradients are that layer's bit for bit.  No atomics,
     no host synchronisation."""
 
@@ -1307,9 +1340,15 @@ class SageMeanCatHeadFn(torch.autograd.Function):
         if need[2]:
             # d self on the rows of a zero matrix, the reversed aggregation accumulating into it: what the layer over all rows does,
             # bit for bit (its d self is zero outside the rows).  Aggregating into a new matrix and adding d self afterwards saves the
-            # kernel's read of its output, but the kernel starts a row's sum from the value it accumulates into: other bits
-            dh = torch.zeros_like(dn).index_copy_(0, rows, d_self)
-            be.spmm_copy_u_strided(ctx.gidx.csr(), "sum", dn, dh, accumulate=True)
+            # kernel's read of its output, but the kernel starts a row's sum from the value it accumulates into: other bits.
+            # config.SAGE_HEAD_INIT: the same sums started from the compact d self through the position map
+            # (mgx_spmm_copy_u_strided_init) -- no zero matrix, no copy into it, no read of it; the sequence below where it declines
+            dh = None
+            if config.SAGE_HEAD_INIT and d_self.stride(1) == 1:
+                dh = be.spmm_copy_u_strided_init(ctx.gidx.csr(), "sum", dn, d_self, _row_pos(rows, dn.shape[0]), torch.empty_like(dn))
+            if dh is None:
+                dh = torch.zeros_like(dn).index_copy_(0, rows, d_self)
+                be.spmm_copy_u_strided(ctx.gidx.csr(), "sum", dn, dh, accumulate=True)
         return None, None, dh, dws, dwn, db, None
 
 

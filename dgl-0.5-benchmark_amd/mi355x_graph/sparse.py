@@ -66,7 +66,7 @@ class CsrView(object):
     """An immutable CSR over torch tensors (in-CSR: rows = destination nodes)."""
 
     __slots__ = ("__weakref__", "num_rows", "num_cols", "indptr", "indices", "eids", "_c", "_deg", "_inv_deg", "_plan", "_sm_plan",
-                 "_row_order", "dst_is_src_prefix", "_tile_plan", "_short", "short_hint", "_rows", "_gate")
+                 "_row_order", "dst_is_src_prefix", "_tile_plan", "_short", "short_hint", "_rows", "_gate", "_head_dn")
 
     def __init__(self, num_rows, num_cols, indptr, indices, eids):
         self.num_rows, self.num_cols = int(num_rows), int(num_cols)
@@ -83,6 +83,8 @@ class CsrView(object):
         self._row_order = (None, None)  # (row order, kind) computed with the first plan
         self._rows = None  # row id of every stored position (the expanded indptr), built on first use by the permuted g-SDDMM walk
         self._gate = None  # ops._SlotGate of untagged 64-column operands aggregated over this CSR (ops._gspmm_over_slots)
+        self._head_dn = None  # (matrix, row list, its version): the [N, K] operand ops.SageMeanCatHeadFn's backward gathers over this CSR, kept
+                              # zero outside the list between steps (ops._head_dn)
         self.dst_is_src_prefix = False  # block graphs whose destination nodes are the first source nodes
 
     @property
@@ -583,6 +585,45 @@ class HipBackend(object):
                     ctypes.byref(csr.c_struct()), None if plan is None else ctypes.byref(plan.c_struct()), REDUCE[reduce], _ptr(U2d), D,
                     int(U2d.stride(0)), _ptr(dst_scale), _ptr(out2d), int(out2d.stride(0)), _ptr(partial),
                     (1 if accumulate else 0) | (2 if short else 0), _stream(dev)))
+            if rec is not None:
+                rec["end"].record(torch.cuda.current_stream(dev))
+                PROFILE.append(rec)
+        return out2d
+
+    def spmm_copy_u_strided_init(self, csr, reduce, U2d, init2d, init_pos, out2d, dst_scale=None):
+        """out2d[v] = (init2d[init_pos[v]] where init_pos[v] >= 0, else +0.0) + sum_u U2d[u]: spmm_copy_u_strided(accumulate=True) into
+        `zeros.index_copy_(0, rows, init2d)` bit for bit, without the zero matrix -- out2d is write-only and every row of it is written
+        (mgx_spmm_copy_u_strided_init).  init_pos: int64 [num_rows], -1 or a row of init2d (ops._row_pos).  Returns out2d, or None when
+        the library has no kernel for these operands (mean, a dst_scale, D % 4, an int64 graph, a CSR on the tile kernel): the caller
+        keeps the zero matrix and the accumulating call."""
+        dev = self._check_dev(csr.indptr, U2d, init2d, init_pos, out2d, dst_scale)
+        D = int(U2d.shape[1])
+        if (U2d.dim() != 2 or out2d.dim() != 2 or init2d.dim() != 2 or U2d.stride(1) != 1 or out2d.stride(1) != 1 or out2d.shape[1] != D
+                or init2d.shape[1] != D or (init2d.stride(1) != 1 and init2d.shape[0] > 0) or U2d.shape[0] != csr.num_cols
+                or out2d.shape[0] != csr.num_rows or init_pos.dtype != torch.int64 or init_pos.shape != (csr.num_rows,)
+                or not init_pos.is_contiguous()):
+            raise DGLError("spmm_copy_u_strided_init: expected row-strided [num_cols, D] -> [num_rows, D] views, a row-strided [R, D] "
+                           "initial matrix and an int64 [num_rows] position map")
+        if D >= config.TILE_MIN_WIDTH and D % 4 == 0 and csr.idx_bits == 32 and csr.tile_plan(D) is not None:  # (the tile kernel has no such operand)
+            return None
+        plan, short = csr.spmm_plan_for(D)
+        partial = torch.empty((plan.total_slots, D), dtype=torch.float32, device=dev) if plan is not None and plan.total_slots else None
+        with torch.cuda.device(dev):
+            rec = None
+            if PROFILE is not None:
+                rec = {"op": "copy_lhs", "reduce": reduce, "out_len": D, "n_rows": csr.num_rows, "n_cols": csr.num_cols,
+                       "nnz": csr.nnz, "accumulate": True, "strides": (int(U2d.stride(0)), int(out2d.stride(0))),
+                       "start": torch.cuda.Event(enable_timing=True), "end": torch.cuda.Event(enable_timing=True)}
+                if short:
+                    rec["variant"] = _short_variant(plan)
+                rec["start"].record(torch.cuda.current_stream(dev))
+            st = _lib.lib().mgx_spmm_copy_u_strided_init(
+                ctypes.byref(csr.c_struct()), None if plan is None else ctypes.byref(plan.c_struct()), REDUCE[reduce], _ptr(U2d), D,
+                int(U2d.stride(0)), _ptr(dst_scale), _ptr(init2d) if init2d.shape[0] else None, int(init2d.shape[0]),
+                max(int(init2d.stride(0)), D) if init2d.shape[0] else D, _ptr(init_pos), _ptr(out2d), int(out2d.stride(0)), _ptr(partial), 2 if short else 0, _stream(dev))
+            if st == _lib.ERR_UNSUPPORTED:
+                return None
+            _lib.check(st)
             if rec is not None:
                 rec["end"].record(torch.cuda.current_stream(dev))
                 PROFILE.append(rec)

@@ -197,6 +197,27 @@ int32_t mgx_spmm_copy_u_strided(const mgx_csr* csr, const mgx_spmm_plan* plan /*
                                 const float* ufeat, int64_t D, int64_t u_stride, const float* dst_scale /* may be NULL */,
                                 float* out, int64_t out_stride, float* partial_ws, int32_t flags, void* stream);
 
+/* mgx_spmm_copy_u_strided with MGX_SPMM_ACCUMULATE semantics whose INITIAL VALUE comes from a compact matrix instead of from `out`:
+ *     out[v, :] = (init_pos[v] >= 0 ? init[init_pos[v], :] : +0.0f) + SUM_{u -> v} ufeat[u, :]
+ * The backward of a layer whose loss reads R of N rows (main_dgl_product_sage.py:105-106) has d self as a compact [R, D] matrix; the
+ * accumulating launch wanted it scattered into a zero-filled [N, D] first -- a fill, a copy and a read of N rows of which 92 % are the
+ * zeros just written.  Here `out` is WRITE-ONLY and every row of it is written (rows without in-edges with their initial value); the
+ * value enters the arithmetic exactly where the accumulated value enters in mgx_spmm_copy_u_strided -- a row outside the list goes
+ * through the same add with +0.0f, so a sum of -0.0f still ends as +0.0f -- and the result is bit for bit that of
+ *     zeros [N, D]; rows listed by init_pos copied from init; mgx_spmm_copy_u_strided(..., MGX_SPMM_ACCUMULATE)
+ * on the same graph and plan (two-part plans and split rows included: a split row's value enters in the fix-up).
+ *   init      fp32 [R, D] (R = init_rows), rows init_stride floats apart (a multiple of 4, >= D), 16-byte aligned; NULL only with R = 0
+ *   init_pos  int64 [num_rows]: the row of `init` a destination row starts from, or -1.  The entries MUST be -1 or in [0, R): the
+ *             kernels follow them unchecked (an entry outside is a read outside `init`).  Two rows may name the same row of `init`.
+ * reduce = MGX_REDUCE_SUM, dst_scale = NULL, int32 graph, D and the three strides multiples of 4, 16-byte aligned pointers, gathered
+ * and initial matrix below 4 GiB each; anything else (MEAN, a dst_scale, D = 62, an int64 graph) returns MGX_ERR_UNSUPPORTED and the caller keeps the
+ * sequence above.  flags: MGX_SPMM_SHORT_ROWS only (accumulation is implied).  plan / partial_ws as for mgx_spmm_csr.
+ * Deterministic: no atomics.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_spmm_copy_u_strided_init(const mgx_csr* csr, const mgx_spmm_plan* plan /* may be NULL */, int32_t reduce, const float* ufeat,
+                                     int64_t D, int64_t u_stride, const float* dst_scale /* must be NULL */, const float* init,
+                                     int64_t init_rows /* R */, int64_t init_stride, const int64_t* init_pos, float* out,
+                                     int64_t out_stride, float* partial_ws, int32_t flags, void* stream);
+
 /* copy_u / sum | mean of a CONSTANT matrix of exactly 100 columns (round 5; csrc/spmm_tail.inc) -- the layer-1 aggregation of
  * ogbn-products' input features (main_dgl_product_sage.py:61-62), the largest launch of the epoch.  The row kernel's time is the number of
  * cache-line requests per edge, and a 400-byte row costs a fourth (4.125 on average) for its last 16 bytes.  The features never change, so
