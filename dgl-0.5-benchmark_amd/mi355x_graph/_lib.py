@@ -133,6 +133,11 @@ SIGNATURES = {
     "mgx_sample_count_positive": (_i32, [_csr_p, _i64, _vp, _fp, _vp, _vp, _vp]),
     "mgx_sample_neighbors_weighted": (_i32, [_csr_p, _i64, _vp, _i32, _fp, _i32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "mgx_select_topk": (_i32, [_csr_p, _i64, _vp, _i32, _fp, _i32, _vp, _vp, _vp, _vp]),
+    "mgx_to_block_workspace": (_i64, [_i64, _i64]),
+    "mgx_to_block": (_i32, [_i64, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mgx_node_subgraph_workspace": (_i64, [_i64]),
+    "mgx_node_subgraph_count": (_i32, [_csr_p, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mgx_node_subgraph_fill": (_i32, [_csr_p, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "mgx_gather_rows": (_i32, [_i64, _vp, _i32, _i64, _fp, _fp, _vp]),
     "mgx_gather_rows_strided": (_i32, [_i64, _vp, _i32, _i64, _fp, _i64, _fp, _i64, _vp]),
     "mgx_scatter_add_rows": (_i32, [_i64, _vp, _i32, _i64, _fp, _fp, _vp]),

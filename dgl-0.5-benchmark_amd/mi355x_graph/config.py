@@ -38,6 +38,10 @@ GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> r
 # ---- graph readout (ops.segment_attention, nn.GlobalAttentionPooling, nn.Set2Set)
 SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: segment max -> gather -> exp -> segment sum -> gather -> multiply -> segment sum
 
+# ---- sampled blocks and induced subgraphs (sampling.to_block, sampling.node_subgraph)
+DEVICE_BLOCKS = True    # the relabelling kernels of csrc/relabel.hip; False: look-up table -> unique -> gathers -> bincount + cumsum in torch ops
+DEVICE_SUBGRAPH = True  # a wave per selected row of a materialised in-CSR (csrc/relabel.hip); False: the look-up table gathered at both ends of every parent edge
+
 # ---- schedules (schedule.py, tileplan.py)
 PLAN_BUILDER = "device"    # "device" (mgx_spmm_plan_count / _fill) | "torch" | "host": the same tables three ways (tests compare them)
 HUB_SPLIT = 256            # rows longer than this become several work items (256 measured best on MI355X; 1024: +5..10 %)

@@ -17,12 +17,14 @@ weight 0 is never picked), without replacement (a row with no more than `fanout`
 (`fanout` independent draws for every row that has an eligible edge; duplicates stay, as multi-edges); select_topk is
 the deterministic sibling.  Every mode returns its edges grouped by seed in seed order, CSR positions non-decreasing
 inside a seed.  Destination nodes of a block are a prefix of its source nodes (block.srcdata[NID][:num_dst] ==
-block.dstdata[NID]).
+block.dstdata[NID]).  The relabelling that follows -- to_block, g.subgraph(nodes) -- runs on the device too (csrc/relabel.hip),
+next to the torch compositions it is compared with (config.DEVICE_BLOCKS, config.DEVICE_SUBGRAPH).
 """
 import math
 
 import torch
 
+from . import config
 from ._lib import DGLError
 from .graph import DGLGraph, GraphIndex
 
@@ -31,6 +33,7 @@ EID = "_ID"
 
 
 DEVICE_MAX_FANOUT = 64  # fanout / k the HIP kernels take (include/mi355x_graph.h); above it the torch formulation runs
+DEVICE_MAX_BLOCK_IDS = 2 ** 31  # mgx_to_block keeps local ids in 32 bits: destinations + edges below this, else the torch formulation
 
 
 def _rng_seed(generator):
@@ -244,20 +247,30 @@ def to_block(g_or_edges, dst_nodes, num_nodes=None, idtype=torch.int64, dst_sort
     dst_nodes = torch.as_tensor(dst_nodes, device=dev).long()
     if num_nodes is None:
         num_nodes = int(max(src.max().item() if src.numel() else 0, dst_nodes.max().item() if dst_nodes.numel() else 0)) + 1
-    lut = torch.full((num_nodes,), -1, dtype=torch.int64, device=dev)
-    lut[dst_nodes] = torch.arange(dst_nodes.shape[0], device=dev)
-    if int((lut[dst] < 0).sum().item()):
-        raise DGLError("to_block: every edge destination must be one of dst_nodes")
-    uniq = torch.unique(src)
-    extra = uniq[lut[uniq] < 0]
-    lut[extra] = dst_nodes.shape[0] + torch.arange(extra.shape[0], device=dev)
-    src_nodes = torch.cat([dst_nodes, extra])
-    l_src, l_dst = lut[src].to(idtype).contiguous(), lut[dst].to(idtype).contiguous()
+    indptr = None
+    if src.is_cuda and config.DEVICE_BLOCKS and dst_nodes.shape[0] + src.shape[0] < DEVICE_MAX_BLOCK_IDS:
+        # device path: mgx_to_block (csrc/relabel.hip) -- a bitmap gives the ascending order of the other sources without a sort, the
+        # in-CSR's row pointer comes from the same pass as the local ids; one host read.  The composition below is kept for CPU graphs
+        from . import sparse
+        dst_nodes = dst_nodes.contiguous()
+        src_nodes, l_src, l_dst, indptr = sparse.backend_for(src).to_block(int(num_nodes), dst_nodes, src.contiguous(), dst.contiguous(),
+                                                                           dst_sorted, idtype)
+    else:
+        lut = torch.full((num_nodes,), -1, dtype=torch.int64, device=dev)
+        lut[dst_nodes] = torch.arange(dst_nodes.shape[0], device=dev)
+        if int((lut[dst] < 0).sum().item()):
+            raise DGLError("to_block: every edge destination must be one of dst_nodes")
+        uniq = torch.unique(src)
+        extra = uniq[lut[uniq] < 0]
+        lut[extra] = dst_nodes.shape[0] + torch.arange(extra.shape[0], device=dev)
+        src_nodes = torch.cat([dst_nodes, extra])
+        l_src, l_dst = lut[src].to(idtype).contiguous(), lut[dst].to(idtype).contiguous()
     csc = None
     if dst_sorted:  # edges arrive grouped by destination in dst_nodes order: the in-CSR is a cumsum away (no sort)
         from .sparse import CsrView
-        indptr = torch.zeros(dst_nodes.shape[0] + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(torch.bincount(l_dst.long(), minlength=dst_nodes.shape[0]), 0, out=indptr[1:])
+        if indptr is None:
+            indptr = torch.zeros(dst_nodes.shape[0] + 1, dtype=torch.int64, device=dev)
+            torch.cumsum(torch.bincount(l_dst.long(), minlength=dst_nodes.shape[0]), 0, out=indptr[1:])
         csc = CsrView(dst_nodes.shape[0], src_nodes.shape[0], indptr.to(idtype), l_src, None)
         csc.dst_is_src_prefix = True
         if max_in_degree is not None and max_in_degree <= 256:
@@ -330,6 +343,33 @@ class NodeDataLoader(object):
             yield blocks[0].srcdata[NID], blocks[-1].dstdata[NID], blocks
 
 
+def _node_subgraph_device(g, parent_csc, nodes):
+    """node_subgraph over the parent's materialised in-CSR (mgx_node_subgraph_count / _fill, csrc/relabel.hip): only the rows of the
+    selected nodes are read, not every edge of the parent.  Same result as the composition in node_subgraph."""
+    from . import sparse
+    n_sel = nodes.shape[0]
+    l_src, l_dst, parent_eid, offsets, rows_by_eid = sparse.backend_for(nodes).node_subgraph(parent_csc, nodes, g.idtype)
+    sorted_eid, order = torch.sort(parent_eid)  # the kept edges only; edge order of the subgraph: ascending parent edge id
+    csc = None
+    if rows_by_eid:
+        # the kernel's row-by-row order IS the subgraph's in-CSR (what a stable sort of its COO by destination gives): hand it over
+        # and save the first aggregation that sort.  eids: CSR position -> new edge id, the inverse of `order`
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(order.shape[0], device=order.device)
+        csc = sparse.CsrView(n_sel, n_sel, offsets.to(g.idtype), l_src, inv.to(g.idtype))
+    sub = DGLGraph(GraphIndex(n_sel, n_sel, coo=(l_src[order], l_dst[order]), csc=csc))
+    sub._index.ephemeral = True  # a cluster / mini-batch subgraph: see GraphIndex.ephemeral
+    if csc is not None:
+        sub._index._mark_ephemeral(csc)
+    for k, v in g.ndata.items():
+        sub.ndata[k] = v[nodes.to(v.device)]
+    for k, v in g.edata.items():
+        sub.edata[k] = v[sorted_eid.to(v.device)]
+    sub.ndata[NID] = nodes
+    sub.edata[EID] = sorted_eid
+    return sub
+
+
 def node_subgraph(g, nodes):
     """g.subgraph(nodes | mask): induced subgraph with relabelled nodes; node features are sliced."""
     dev = g.device
@@ -342,6 +382,9 @@ def node_subgraph(g, nodes):
         nodes = torch.nonzero(nodes).flatten()
     nodes = nodes.long()
     n = g.number_of_nodes()
+    parent_csc = g._index._csc if g._index._csc is not None else g._index._hidden_csc
+    if nodes.is_cuda and config.DEVICE_SUBGRAPH and parent_csc is not None and not g.is_block:
+        return _node_subgraph_device(g, parent_csc, nodes.contiguous())
     lut = torch.full((n,), -1, dtype=torch.int64, device=dev)
     lut[nodes] = torch.arange(nodes.shape[0], device=dev)
     src, dst = g.edges()

@@ -1523,6 +1523,67 @@ class HipBackend(object):
                                                   1 if ascending else 0, _ptr(offsets), _ptr(src), _ptr(eid), _stream(dev)))
         return src, eid, counts
 
+    # ---- sampled blocks and induced subgraphs (csrc/relabel.hip)
+    def to_block(self, num_nodes, dst_nodes, src, dst, dst_sorted, idtype):
+        """dst_nodes, src, dst: contiguous int64 global ids on one device.  Returns (src_nodes int64, l_src, l_dst, indptr or None) with
+        the local ids and the dst-sorted in-CSR's row pointer in `idtype`.  One host read: the number of sources and the error bits."""
+        dev = self._check_dev(src, dst, dst_nodes)
+        L = _lib.lib()
+        num_dst, nnz = int(dst_nodes.shape[0]), int(src.shape[0])
+        bits = 32 if idtype == torch.int32 else 64
+        src_nodes = torch.empty(num_dst + min(nnz, num_nodes), dtype=torch.int64, device=dev)
+        l_src = torch.empty(nnz, dtype=idtype, device=dev)
+        l_dst = torch.empty(nnz, dtype=idtype, device=dev)
+        indptr = torch.empty(num_dst + 1, dtype=idtype, device=dev) if dst_sorted else None
+        with torch.cuda.device(dev):
+            ws_bytes = L.mgx_to_block_workspace(num_nodes, nnz)
+            if ws_bytes < 0:
+                raise DGLError("to_block: negative num_nodes")
+            ws = torch.empty(ws_bytes // 8 + 2, dtype=torch.int64, device=dev)  # the last two words: {num_src, error bits}
+            result = ws[-2:]
+            _lib.check(L.mgx_to_block(num_nodes, num_dst, _ptr(dst_nodes), nnz, _ptr(src), _ptr(dst), 1 if dst_sorted else 0, bits,
+                                      _ptr(ws), _ptr(src_nodes), _ptr(l_src), _ptr(l_dst), _ptr(indptr), _ptr(result), _stream(dev)))
+        num_src, err = result.tolist()
+        if err & 4:
+            raise DGLError("to_block: a node id is outside [0, %d)" % num_nodes)
+        if err & 1:
+            raise DGLError("to_block: dst_nodes holds a node more than once")
+        if err & 2:
+            raise DGLError("to_block: every edge destination must be one of dst_nodes")
+        if err & 8:
+            raise DGLError("to_block: dst_sorted=True, but the edges are not grouped by destination in dst_nodes order")
+        return src_nodes[:num_src], l_src, l_dst, indptr
+
+    def node_subgraph(self, csc, nodes, idtype):
+        """csc: the parent's in-CSR; nodes: contiguous int64 ids on its device.  Returns (l_src, l_dst in `idtype`, parent_eid int64,
+        offsets int64 [n + 1], rows_by_eid): the kept edges row by row of the selection, CSR order inside a row; rows_by_eid: the edge
+        ids of every selected row ascend (the rows then are in the order a stable sort of the kept edges by destination gives)."""
+        dev = self._check_dev(csc.indptr, nodes)
+        L = _lib.lib()
+        n = int(nodes.shape[0])
+        c = ctypes.byref(csc.c_struct())
+        bits = 32 if idtype == torch.int32 else 64
+        counts = torch.empty(n, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            ws_bytes = L.mgx_node_subgraph_workspace(csc.num_rows)
+            ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=dev)  # the last word: error bits
+            result = ws[-1:]
+            _lib.check(L.mgx_node_subgraph_count(c, n, _ptr(nodes), _ptr(ws), _ptr(counts), _ptr(result), _stream(dev)))
+        offsets = self._sample_offsets(counts)
+        total, err = torch.stack([offsets[-1], result[0]]).tolist()  # output size and the error bits in one host read
+        if err & 4:
+            raise DGLError("subgraph: a node id is outside [0, %d)" % csc.num_rows)
+        if err & 1:
+            raise DGLError("subgraph: a node is selected more than once")
+        l_src = torch.empty(total, dtype=idtype, device=dev)
+        l_dst = torch.empty(total, dtype=idtype, device=dev)
+        parent_eid = torch.empty(total, dtype=torch.int64, device=dev)
+        if total:
+            with torch.cuda.device(dev):
+                _lib.check(L.mgx_node_subgraph_fill(c, n, _ptr(nodes), _ptr(ws), _ptr(offsets), bits, _ptr(l_src), _ptr(l_dst),
+                                                    _ptr(parent_eid), _stream(dev)))
+        return l_src, l_dst, parent_eid, offsets, not (err & 16)
+
     # ---- halo rows as bitmaps + packed values (csrc/rowpack.hip; dist.SparseHalo)
     ROWPACK_MAX_D = 256
 

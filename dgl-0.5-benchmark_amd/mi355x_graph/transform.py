@@ -283,6 +283,8 @@ def metis_partition(g, k, extra_cached_hops=0, reshuffle=False, balance_ntypes=N
     order = torch.sort(assign, stable=True)[1]
     counts = torch.bincount(assign, minlength=int(k)).tolist()
     parts, off = {}, 0
+    if g.device.type != "cpu":
+        g._index.csc()  # built once: every g.subgraph below then reads its own rows of the in-CSR, not every edge of g
     for i, c in enumerate(counts):
         if c:
             parts[i] = g.subgraph(order[off:off + c])

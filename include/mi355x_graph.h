@@ -790,6 +790,42 @@ int32_t mgx_sample_neighbors_weighted(const mgx_csr* csr, int64_t num_seeds, con
 int32_t mgx_select_topk(const mgx_csr* csr, int64_t num_seeds, const void* seeds, int32_t k, const float* weight, int32_t ascending,
                         const int64_t* out_offsets, void* out_src, void* out_eid, void* stream);
 
+/* ------------------------------------------------------------------ sampled blocks and induced subgraphs (csrc/relabel.hip)
+ * What follows the sampler on every step: global node ids -> the local ids of a bipartite block (dgl.to_block) or of a node-induced
+ * subgraph (g.subgraph).  Integer kernels over a look-up table int32[num_nodes] (-1 = not in the output) that the entry point fills
+ * itself (hipMemsetAsync): nothing is kept between calls.  Every id read from a caller's array is checked against [0, num_nodes)
+ * before it indexes anything; a bad id sets an error bit and is skipped.  Purely additive: mgx_abi_version() stays 35.
+ *
+ * mgx_to_block: dst_nodes[num_dst], src[nnz], dst[nnz] are int64 global ids (what the sampler returns).  Writes
+ *   src_nodes   int64, capacity num_dst + min(nnz, num_nodes): dst_nodes, then every other source in ASCENDING global id (the order
+ *               a sort + unique gives; here from a bitmap of the nodes, walked word by word)
+ *   l_src/l_dst [nnz] the edges in local ids, 32- or 64-bit by `out_bits`
+ *   indptr      [num_dst + 1] in the same width, only when dst_sorted != 0 (the caller promises that the edges arrive grouped by
+ *               destination in dst_nodes order): the row pointer of the in-CSR whose indices are l_src.  May be NULL otherwise.
+ *   result      device int64[2]: {num_src, error bits}; error bits: 1 a node twice in dst_nodes, 2 an edge destination that is not in
+ *               dst_nodes, 4 an id outside [0, num_nodes), 8 dst_sorted promised but l_dst decreases somewhere.  With an error bit
+ *               set the other outputs are unspecified (nothing is written out of bounds).
+ *   workspace   mgx_to_block_workspace(num_nodes, nnz) bytes (-1: bad arguments).  num_dst + nnz < 2^31. */
+int64_t mgx_to_block_workspace(int64_t num_nodes, int64_t nnz);
+int32_t mgx_to_block(int64_t num_nodes, int64_t num_dst, const int64_t* dst_nodes, int64_t nnz, const int64_t* src, const int64_t* dst,
+                     int32_t dst_sorted, int32_t out_bits, void* workspace, int64_t* src_nodes, void* l_src, void* l_dst,
+                     void* indptr /* may be NULL without dst_sorted */, int64_t* result /* [2] */, void* stream);
+/* Node-induced subgraph over the parent's in-CSR `csr` (num_rows == num_cols, either index width): sel_nodes[num_sel] int64, the
+ * selected nodes; node sel_nodes[i] becomes i.
+ *   _count  fills the look-up table in `workspace` (mgx_node_subgraph_workspace(num_nodes) bytes) and writes counts[i] (int64) = the
+ *           in-edges of sel_nodes[i] whose source is selected too.  result: device int64[1] of error bits -- 1 a node twice in
+ *           sel_nodes, 4 an id outside [0, num_rows), 16 (no error) the edge ids inside some selected row do not ascend.
+ *   The caller takes offsets = exclusive cumsum of counts ([num_sel + 1], int64), reads offsets[num_sel] and the error bits, allocates
+ *   l_src / l_dst (out_bits wide) and parent_eid (int64) with offsets[num_sel] entries and calls
+ *   _fill   with the same csr / sel_nodes / workspace (unchanged since _count): row i's kept edges go to [offsets[i], offsets[i+1]) in
+ *           CSR order -- local source, local destination i, parent edge id (eids[p], or p without eids); never past offsets[i+1].
+ * Ballot + prefix popcount inside a row, no atomics: deterministic. */
+int64_t mgx_node_subgraph_workspace(int64_t num_nodes);
+int32_t mgx_node_subgraph_count(const mgx_csr* csr, int64_t num_sel, const int64_t* sel_nodes, void* workspace, int64_t* counts,
+                                int64_t* result /* [1] */, void* stream);
+int32_t mgx_node_subgraph_fill(const mgx_csr* csr, int64_t num_sel, const int64_t* sel_nodes, const void* workspace,
+                               const int64_t* offsets, int32_t out_bits, void* l_src, void* l_dst, int64_t* parent_eid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
