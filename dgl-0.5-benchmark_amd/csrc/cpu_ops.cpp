@@ -159,9 +159,13 @@ inline void sddmm_edge(int op, const float* L, const float* R, int64_t li, int64
   const float* lr = L ? L + li * l_len : nullptr;
   const float* rr = R ? R + ri * r_len : nullptr;
   if (op == MGX_OP_DOT) {
+    // as csrc/sddmm.hip: the lookup (table or head-wise rule) is over the out_len OUTPUT positions and names a vector of rs elements
+    const Lookup lk{lo.table, lo.len / rs, out_len}, rk{ro.table, ro.len / rs, out_len};
     for (int64_t k = 0; k < out_len; ++k) {
+      const float* lv = lr + lk.at(k) * rs;
+      const float* rv = rr + rk.at(k) * rs;
       float acc = 0.f;
-      for (int64_t j = 0; j < rs; ++j) acc += lr[lo.at(k * rs + j)] * rr[ro.at(k * rs + j)];
+      for (int64_t j = 0; j < rs; ++j) acc += lv[j] * rv[j];
       o[k] = acc;
     }
     return;

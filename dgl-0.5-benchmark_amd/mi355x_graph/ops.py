@@ -134,8 +134,21 @@ def _need_reduce_last_dim(ushp, eshp):
     return ushp[1:-1] == eshp[1:-1] and eshp[-1] == 1 and ushp[-1] > 1
 
 
-def _expand(x, shape):
-    return x.expand(-1, *shape)
+def _align(a, b):
+    """a and b (rows first) with their FEATURE dimensions right-aligned, the way sparse._bcast_plan aligns them for the kernels:
+    (E, 4) against (E, 2, 4) becomes (E, 1, 4) -- plain torch would line the row dimension of one up with a feature dimension of
+    the other."""
+    nd = max(a.dim(), b.dim())
+
+    def pad(t):
+        return t if t.dim() == nd else t.reshape((t.shape[0],) + (1,) * (nd - t.dim()) + tuple(t.shape[1:]))
+    return pad(a), pad(b)
+
+
+def _expand(x, like):
+    """x broadcast to the feature shape of `like`, feature dimensions right-aligned first (_align): the operand of a max / min
+    backward `gather` may have fewer of them than the gradient, (N, 4) against (N_dst, 2, 4)."""
+    return _align(x, like)[0].expand(-1, *like.shape[1:])
 
 
 class GSpMM(torch.autograd.Function):
@@ -195,7 +208,7 @@ class GSpMM(torch.autograd.Function):
                 idx = argX.clamp(min=0).long()
                 g = dZ
                 if op == "mul":
-                    yexp = _expand(Y, dZ.shape[1:]) if Y.shape[1:] != dZ.shape[1:] else Y
+                    yexp = _expand(Y, dZ) if Y.shape[1:] != dZ.shape[1:] else Y
                     g = dZ * yexp.gather(0, argY.clamp(min=0).long())
                 g = g * valid
                 full = torch.zeros((ctx.x_shape[0],) + tuple(dZ.shape[1:]), dtype=dZ.dtype, device=dZ.device)
@@ -206,7 +219,7 @@ class GSpMM(torch.autograd.Function):
                 idx = argY.clamp(min=0).long()
                 g = dZ
                 if op == "mul":
-                    xexp = _expand(X, dZ.shape[1:]) if X.shape[1:] != dZ.shape[1:] else X
+                    xexp = _expand(X, dZ) if X.shape[1:] != dZ.shape[1:] else X
                     g = dZ * xexp.gather(0, argX.clamp(min=0).long())
                 g = g * valid
                 full = torch.zeros((ctx.y_shape[0],) + tuple(dZ.shape[1:]), dtype=dZ.dtype, device=dZ.device)
@@ -256,7 +269,8 @@ class GSDDMM(torch.autograd.Function):
                     dX, _, _ = _raw_gspmm(gidx.csc(), "mul", "sum", Y, dZ)
                 else:
                     y_e = _raw_gsddmm(gidx, "copy_rhs", None, Y, lt, rt) if rt != "e" else Y
-                    ge = dZ * y_e if op in ("mul", "dot") else dZ / y_e
+                    dz, y_e = _align(dZ, y_e)
+                    ge = dz * y_e if op in ("mul", "dot") else dz / y_e
                     dX = GSDDMM._to_target(gidx, lt, ge.contiguous())
             dX = _reduce_grad(dX, ctx.x_shape)
         if op != "copy_lhs" and ctx.needs_input_grad[3]:
@@ -265,17 +279,20 @@ class GSDDMM(torch.autograd.Function):
             elif op == "sub":
                 dY = GSDDMM._to_target(gidx, rt, (-dZ).contiguous())
             elif op in ("mul", "dot"):
-                if lt == "u" and rt == "v":
-                    dY, _, _ = sparse.gspmm_raw(gidx.csc(), "mul", "sum", X, dZ)
+                if lt == "u" and rt == "v":  # the same route as dX above
+                    dY, _, _ = _raw_gspmm(gidx.csc(), "mul", "sum", X, dZ)
                 elif lt == "v" and rt == "u":
-                    dY, _, _ = sparse.gspmm_raw(gidx.csr(), "mul", "sum", X, dZ)
+                    dY, _, _ = _raw_gspmm(gidx.csr(), "mul", "sum", X, dZ)
                 else:
                     x_e = _raw_gsddmm(gidx, "copy_lhs", X, None, lt, rt) if lt != "e" else X
-                    dY = GSDDMM._to_target(gidx, rt, (dZ * x_e).contiguous())
+                    dz, x_e = _align(dZ, x_e)
+                    dY = GSDDMM._to_target(gidx, rt, (dz * x_e).contiguous())
             else:  # div: d(x/y)/dy = -x / y^2
                 x_e = _raw_gsddmm(gidx, "copy_lhs", X, None, lt, rt) if lt != "e" else X
                 y_e = _raw_gsddmm(gidx, "copy_rhs", None, Y, lt, rt) if rt != "e" else Y
-                dY = GSDDMM._to_target(gidx, rt, (-dZ * x_e / (y_e * y_e)).contiguous())
+                dz, x_e = _align(dZ, x_e)
+                dz, y_e = _align(dz, y_e)
+                dY = GSDDMM._to_target(gidx, rt, (-dz * x_e / (y_e * y_e)).contiguous())
             dY = _reduce_grad(dY, ctx.y_shape)
         return None, None, dX, dY, None, None
 

@@ -167,8 +167,17 @@ def test_general_broadcast_tables(oracle):
         out = ops.gspmm(g, op, "sum", T(X), T(E))
         assert out.shape == (n, 4, 6)
         assert rel(out.cpu(), oracle.spmm(ip, ix, ei, op, "sum", X, E)) < RTOL
-    out = ops.gsddmm(g, "mul", T(X), T(rng.random((n, 4, 1), dtype=np.float32)))
+    V = rng.random((n, 4, 1), dtype=np.float32)
+    out = ops.gsddmm(g, "mul", T(X), T(V))
     assert out.shape == (nnz, 4, 6)
+    assert np.array_equal(out.cpu().numpy(), oracle.sddmm(src, dst, "mul", X, V))  # one rounding per element: bit-exact, as in test_gsddmm
+    # (n, 4, 6) x (n, 4, 1) is head-wise (NULL tables); (n, 6) x (n, 4, 6) right-aligns to (1, 6) and takes a real lhs table
+    X2, V2 = np.ascontiguousarray(X[:, 0, :]), rng.random((n, 4, 6), dtype=np.float32)
+    assert sparse._bcast_plan(X2.shape[1:], V2.shape[1:])[1] is not None
+    for op in ("mul", "sub"):
+        out = ops.gsddmm(g, op, T(X2), T(V2))
+        assert out.shape == (nnz, 4, 6)
+        assert np.array_equal(out.cpu().numpy(), oracle.sddmm(src, dst, op, X2, V2))
 
 
 def test_max_min_arg_indices_exact(oracle):
