@@ -370,6 +370,159 @@ __global__ __launch_bounds__(kBlock) void xty_colsum_finish_kernel(int M, int mt
   for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, kWave);
   if (lane == 0) colsum[m] = s;
 }
+
+// mgx_xty_colsum_masked: relu_dropout_bwd_kernel + xty_partial_v4_kernel<1, 0, ...> per 128-column block of B + the column sums in ONE
+// pass.  dZ[r][4c + t] = bit t of mask[r * 16 + c] ? dy[r][4c + t] * scale : 0.f is formed in registers from the float2 a lane loads anyway
+// and never stored.  The bits are those of the composition by construction: partition gw of xty_waves(n) walks the rows the composition's
+// wave gw walks, a 16 x 16 accumulator (A component i, B tile j) sees the same MFMAs in the same order (steps in row order, s = 0 .. 3
+// inside a step), B's tiles are cut as the composition's launches cut them (per block of 128 columns: float4 groups of 64, then dword
+// tiles of 16), and the partials are added by the finish kernels' own code.  Which physical wave holds which accumulator is free:
+// TWO waves per partition split A's four components (h = 0: x, y; h = 1: z, w), so both carry 2 x BT + 2 tiles -- the same MFMA count --
+// and run the same code; each reads all of B, the later one from L1 / L2 (same workgroup, same rows at the same time).
+// Operands live in a ring of the step's four 4-row slices: slice s of the NEXT step is loaded right after the MFMAs of slice s, so a load has
+// three slices of MFMAs (>= 1 us) to land while the registers of one step, not two, are held.
+// VG0 / ST0: float4 groups / dword tiles of block 0 (columns 0 .. 127), VG1 / ST1: of block 1 (columns 128 ..).
+template <int VG0, int ST0, int VG1, int ST1>
+__global__ __launch_bounds__(kBlock) void xty_masked_partial_kernel(int64_t n, int K, int waves, const float* __restrict__ dy, int64_t lddy,
+                                                                    const uint8_t* __restrict__ mask, float scale,
+                                                                    const float* __restrict__ B, int64_t ldb, float* __restrict__ part,
+                                                                    float* __restrict__ part_sum) {
+  constexpr int NG = VG0 + VG1, NS = ST0 + ST1, BT = NG * 4 + NS;
+  constexpr int kDword0 = VG0 * 64, kDword1 = 128 + VG1 * 64;  // first dword-tile column of either block
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int h = wave & 1;                                                         // which two components of A's float4
+  const int64_t gw = (int64_t)blockIdx.x * (kWavesPerBlock / 2) + (wave >> 1);  // the partition: the composition's wave number
+  const int c = lane % 16, q = lane / 16;
+  v4f acc[2][BT];
+  v4f accs[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    accs[i] = (v4f)(0.f);
+#pragma unroll
+    for (int j = 0; j < BT; ++j) acc[i][j] = (v4f)(0.f);
+  }
+  const float one = c == 0 ? 1.f : 0.f;
+  const int64_t stride = (int64_t)waves * 16;
+  v2f ra[4];                         // the ring: dy[row][4c + 2h .. + 1], its mask byte, B's float4 groups and dword tiles, per slice
+  uint32_t rm[4];
+  v4f rg[4][NG > 0 ? NG : 1];
+  float rs[4][NS > 0 ? NS : 1];
+  // Every load is issued unconditionally from a clamped address, and what a row >= n (the tail of the last step, the step after a wave's
+  // last) or a column >= K brought is replaced by zero where the slice is CONSUMED: no branch and no use of the loaded registers sits
+  // between a load and the MFMAs it feeds three slices later, so the wait before them leaves the younger loads in flight.
+  auto fetch = [&](int64_t r0, int s) {
+    const int64_t row = r0 + s * 4 + q;
+    const int64_t rc = row < n ? row : n - 1;
+    ra[s] = *reinterpret_cast<const v2f*>(dy + rc * lddy + 4 * c + 2 * h);
+    rm[s] = mask[rc * 16 + c];
+    const float* b = B + rc * ldb;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) rg[s][g] = *reinterpret_cast<const v4f*>(b + (g < VG0 ? g * 64 : 128 + (g - VG0) * 64) + 4 * c);
+#pragma unroll
+    for (int t = 0; t < NS; ++t) {
+      const int col = (t < ST0 ? kDword0 + t * 16 : kDword1 + (t - ST0) * 16) + c;
+      rs[s][t] = b[col < K ? col : K - 1];
+    }
+    // keeps the loads HERE: without a barrier the compiler turns "loaded in step i, carried round the loop, used in step i + 1" into a
+    // load at the use (a phi of loads becomes the load of a phi), and the ring into load-wait-multiply
+    asm volatile("" ::: "memory");
+  };
+  if (gw * 16 < n) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) fetch(gw * 16, s);
+  }
+  for (int64_t r0 = gw * 16; r0 < n; r0 += stride) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const bool ok = r0 + s * 4 + q < n;
+      const uint32_t m = ok ? rm[s] >> (2 * h) : 0u;
+      float a[2];
+      a[0] = (m & 1) ? ra[s].x * scale : 0.f;  // a select, as relu_dropout_bwd_kernel writes it: nothing behind a cleared bit is multiplied
+      a[1] = (m & 2) ? ra[s].y * scale : 0.f;
+      float b[BT];
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const v4f v = ok ? rg[s][g] : (v4f)(0.f);
+        b[g * 4 + 0] = v.x; b[g * 4 + 1] = v.y; b[g * 4 + 2] = v.z; b[g * 4 + 3] = v.w;
+      }
+#pragma unroll
+      for (int t = 0; t < NS; ++t) {
+        const int col = (t < ST0 ? kDword0 + t * 16 : kDword1 + (t - ST0) * 16) + c;
+        b[NG * 4 + t] = (ok & (col < K)) ? rs[s][t] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < BT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
+      const float ones = ok ? one : 0.f;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) accs[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], ones, accs[i], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);  // the slice's MFMAs, THEN its refill: the scheduler would gather all four refills at the loop's end
+      fetch(r0 + stride, s);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  // accumulator element r of (component i, tile j) in lane (c, q) is C[m][k], m = 4 (4q + r) + 2h + i; partial [64][K] + sums [64] per partition
+  float* p = part + gw * (int64_t)64 * K;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int mrow = 4 * (4 * q + r) + 2 * h + i;
+      if (c == 0) part_sum[gw * 64 + mrow] = accs[i][r];
+#pragma unroll
+      for (int j = 0; j < BT; ++j) {
+        int k;
+        if (j < NG * 4) {
+          const int g = j / 4;
+          k = (g < VG0 ? g * 64 : 128 + (g - VG0) * 64) + 4 * c + (j % 4);
+        } else {
+          const int t = j - NG * 4;
+          k = (t < ST0 ? kDword0 + t * 16 : kDword1 + (t - ST0) * 16) + c;
+        }
+        if (k < K) p[mrow * K + k] = acc[i][j][r];
+      }
+    }
+}
+
+// One finish launch for out [64, K] and colsum [64]: the element workgroups run xty_finish_kernel's additions (16 slices of the partition
+// list, four running sums per slice, slices added in slice order), the last 16 workgroups xty_colsum_finish_kernel's (one wave per column).
+__global__ __launch_bounds__(kBlock) void xty_masked_finish_kernel(int K, int waves, const float* __restrict__ part,
+                                                                   const float* __restrict__ part_sum, float* __restrict__ out, int64_t ldc,
+                                                                   float* __restrict__ colsum) {
+  __shared__ float red[16][17];
+  const int elem_blocks = 64 * K / 16;
+  if ((int)blockIdx.x >= elem_blocks) {
+    const int m = ((int)blockIdx.x - elem_blocks) * kWavesPerBlock + threadIdx.x / kWave;
+    const int lane = threadIdx.x % kWave;
+    float s = 0.f;
+    for (int w = lane; w < waves; w += kWave) s += part_sum[(int64_t)w * 64 + m];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, kWave);
+    if (lane == 0) colsum[m] = s;
+    return;
+  }
+  const int e = threadIdx.x % 16, sl = threadIdx.x / 16;
+  const int idx = blockIdx.x * 16 + e;  // over 64 * K, a multiple of 16
+  const int tile = 64 * K;
+  const float* p = part + idx;
+  const int per = waves / 16;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  for (int w = sl * per; w < (sl + 1) * per; w += 4) {
+    s0 += p[(int64_t)w * tile];
+    s1 += p[(int64_t)(w + 1) * tile];
+    s2 += p[(int64_t)(w + 2) * tile];
+    s3 += p[(int64_t)(w + 3) * tile];
+  }
+  red[sl][e] = (s0 + s1) + (s2 + s3);
+  __syncthreads();
+  if (sl == 0) {
+    float s = 0.f;
+    for (int i = 0; i < 16; ++i) s += red[i][e];
+    out[(int64_t)(idx / K) * ldc + idx % K] = s;
+  }
+}
 }  // namespace mgx
 
 extern "C" int64_t mgx_xty_workspace(int64_t M, int64_t K) {
@@ -469,5 +622,55 @@ static int32_t xty_impl(int64_t n, int64_t M, int64_t K, const float* a, int64_t
                        mt * 16, waves, (const float*)part_sum, colsum);
     MGX_CHECK_LAUNCH();
   }
+  return MGX_OK;
+}
+
+extern "C" int64_t mgx_xty_masked_workspace(int64_t K) {
+  if (K < 64 || K > 256 || K % 4) return -1;
+  return (int64_t)mgx::kXtyWaves * (64 * K + 64) * (int64_t)sizeof(float);  // a [64, K] partial tile + 64 column sums per partition
+}
+
+extern "C" int32_t mgx_xty_colsum_masked(int64_t n, int64_t K, const float* dy, int64_t lddy, const uint8_t* mask, float p, const float* b,
+                                         int64_t ldb, float* out, int64_t ldc, float* colsum, void* workspace, void* stream) {
+  using namespace mgx;
+  MGX_ENTER();
+  MGX_CHECK_ARG(n >= 0 && K >= 1, "mgx_xty_colsum_masked: bad sizes");
+  MGX_CHECK_ARG(p >= 0.f && p < 1.f, "mgx_xty_colsum_masked: p must be in [0, 1)");
+  if (K < 64 || K > 256 || K % 4) MGX_UNSUPPORTED("mgx_xty_colsum_masked: needs 64 <= K <= 256, K %% 4 == 0 (got %lld)", (long long)K);
+  MGX_CHECK_ARG(out && colsum, "mgx_xty_colsum_masked: out or colsum is NULL");
+  MGX_CHECK_ARG(lddy >= 64 && ldb >= K && ldc >= K, "mgx_xty_colsum_masked: leading dimensions smaller than the tile (lddy %lld, ldb %lld, ldc %lld)",
+                (long long)lddy, (long long)ldb, (long long)ldc);
+  hipStream_t s = (hipStream_t)stream;
+  if (n == 0) {
+    MGX_CHECK_HIP(hipMemset2DAsync(out, (size_t)ldc * sizeof(float), 0, (size_t)K * sizeof(float), 64, s));
+    MGX_CHECK_HIP(hipMemsetAsync(colsum, 0, 64 * sizeof(float), s));
+    return MGX_OK;
+  }
+  MGX_CHECK_ARG(dy && mask && b && workspace, "mgx_xty_colsum_masked: NULL pointer");
+  if (lddy % 4 || (uintptr_t)dy % 16 || ldb % 4 || (uintptr_t)b % 16)
+    MGX_UNSUPPORTED("mgx_xty_colsum_masked: needs the 16-byte-load form of both operands (row strides %% 4 == 0, 16-byte aligned)");
+  // the tiles of either 128-column block as mgx_xty_colsum cuts them (launch_xty_v4): float4 groups of 64 columns, dword tiles of 16 for the rest
+  const int64_t k0 = K < 128 ? K : 128, k1 = K - k0;
+  if (k1 > 0 && k1 < 64) MGX_UNSUPPORTED("mgx_xty_colsum_masked: a second block of %lld columns has no 16-byte-load form", (long long)k1);
+  const int vg0 = k0 >= 128 ? 2 : 1, st0 = (int)((k0 - vg0 * 64 + 15) / 16);
+  const int vg1 = k1 >= 128 ? 2 : k1 >= 64 ? 1 : 0, st1 = (int)((k1 - vg1 * 64 + 15) / 16);
+  const int waves = xty_waves(n);
+  float* part = (float*)workspace;
+  float* part_sum = part + (int64_t)kXtyWaves * 64 * K;
+  const float scale = 1.f / (1.f - p);
+  bool ok = false;
+#define MGX_XTYM(A, B, C, D)                                                                                                             \
+  if (vg0 == A && st0 == B && vg1 == C && st1 == D) {                                                                                    \
+    hipLaunchKernelGGL((xty_masked_partial_kernel<A, B, C, D>), dim3(waves / (kWavesPerBlock / 2)), dim3(kBlock), 0, s, n, (int)K, waves, \
+                       dy, lddy, mask, scale, b, ldb, part, part_sum);                                                                   \
+    ok = true;                                                                                                                           \
+  }
+  MGX_XTYM(1, 0, 0, 0) MGX_XTYM(1, 1, 0, 0) MGX_XTYM(2, 0, 0, 0) MGX_XTYM(2, 0, 1, 1) MGX_XTYM(2, 0, 2, 0)
+#undef MGX_XTYM
+  if (!ok) MGX_UNSUPPORTED("mgx_xty_colsum_masked: no kernel for K = %lld (built: 64, 68 .. 80, 128, 196 .. 208, 256)", (long long)K);
+  MGX_CHECK_LAUNCH();
+  hipLaunchKernelGGL(xty_masked_finish_kernel, dim3((unsigned)(64 * K / 16 + 64 / kWavesPerBlock)), dim3(kBlock), 0, s, (int)K, waves,
+                     (const float*)part, (const float*)part_sum, out, ldc, colsum);
+  MGX_CHECK_LAUNCH();
   return MGX_OK;
 }

@@ -115,6 +115,8 @@ SIGNATURES = {
     "mgx_xty_rows": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _vp, _fp, _i64, _vp, _vp]),
     "mgx_xty_colsum_rows": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _vp, _fp, _i64, _fp, _vp, _vp]),
     "mgx_xty_colsum_pos": (_i32, [_i64, _i64, _i64, _fp, _i64, _vp, _fp, _i64, _fp, _i64, _fp, _vp, _vp]),
+    "mgx_xty_masked_workspace": (_i64, [_i64]),
+    "mgx_xty_colsum_masked": (_i32, [_i64, _i64, _fp, _i64, _vp, ctypes.c_float, _fp, _i64, _fp, _i64, _fp, _vp, _vp]),
     "mgx_rows_gemm_rows": (_i32, [_i64, _i64, _i64, _fp, _i64, _vp, _fp, _i64, _i32, _fp, _fp, _i64, _fp, _i64, _fp, _i64, _i64, _vp, _vp]),
     "mgx_rows_gemm_supported": (_i32, [_i64, _i64, _i64]),
     "mgx_rows_gemm_sweep_rows": (_i64, [_i64, _i64, _i64, _i32]),

@@ -2,7 +2,7 @@
 
 USER switches are environment variables, read where they are used; the complete list is the table in README.md ("Switches"):
     MGX_LIB_PATH  MGX_DATA_ROOT  MGX_CACHE_DIR  MGX_SCHEDULE  MGX_TILE  MGX_GAT_TILE  MGX_GAT_FUSED  MGX_TORCH_OPS  MGX_SDDMM_WALK
-    MGX_SPARSE_HALO  MGX_ACCELERATE_LINEAR  MGX_SAGE_SPARSE_LAST  MGX_SAGE_HEAD_ROWS  MGX_SAGE_L1_PROJECT_FIRST  MGX_PLAIN_MODEL  MGX_HOST_THREADS
+    MGX_SPARSE_HALO  MGX_ACCELERATE_LINEAR  MGX_SAGE_SPARSE_LAST  MGX_SAGE_HEAD_ROWS  MGX_XTY_MASKED  MGX_SAGE_L1_PROJECT_FIRST  MGX_PLAIN_MODEL  MGX_HOST_THREADS
 (+ the bench / test hooks MGX_DIST_BACKEND, MGX_BENCH_SHARE_GPU, MGX_BENCH_TUNABLEOP, MGX_BENCH_STEP_TIMES, MGX_DATASET_SCALE).
 
 Everything below is NOT a user switch: module attributes with fixed defaults that choose between a fused form and the composition it
@@ -25,6 +25,8 @@ SAGE_HEAD_INIT = True      # ... its reversed aggregation started from the compa
 ROWS_GEMM = True           # mgx_rows_gemm for the projections of a layer over >= 65 536 rows (else the library GEMM)
 LINEAR_XTY = True          # tall-skinny weight gradients by mgx_xty (else the library GEMM)
 XTY_COLSUM = True          # ... with the bias gradient from the same pass (mgx_xty_colsum)
+XTY_MASKED = True          # ... and, behind relu + dropout where d z is needed for nothing else, the mask applied on load: d z is never
+                           # stored (mgx_xty_colsum_masked, same bits; MGX_XTY_MASKED=0 restores relu_dropout_bwd + xty)
 
 # ---- GAT (nn.py, sparse.py)
 GAT_AGG_FIRST = True       # aggregate before projecting when in_feats < heads * out_feats

@@ -656,6 +656,16 @@ class DistSageMeanCatFn(torch.autograd.Function):
             w_self, w_neigh, mask = ctx.saved_tensors
             if not dy.is_contiguous() and not (hasattr(be, "_row_strided") and be._row_strided(dy)):
                 dy = dy.contiguous()
+            need = ctx.needs_input_grad
+            masked = None
+            if not need[3] and (need[4] or need[5]) and need[6] and ops._xty_masked_wanted(be, dy, cat.buf):
+                masked = be.xty_masked(dy, mask, ctx.p, cat.buf)  # as ops.SageMeanCatFn.backward: d z is needed by the weight gradient only
+            if masked is not None:
+                comm.mark("dense (inside the exchange window)")
+                dw, db = masked
+                dws, dwn = dw[:, :cat.K].contiguous(), dw[:, cat.K:].contiguous()
+                comm.mark("dense")
+                return None, None, None, None, dws, dwn, db, None, None, None
             dy = be.relu_dropout_bwd(dy, mask, ctx.p)  # the gradient of the pre-activation, as ops.ReluDropout.backward forms it
         else:
             w_self, w_neigh = ctx.saved_tensors

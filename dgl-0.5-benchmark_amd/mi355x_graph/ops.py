@@ -929,6 +929,14 @@ def _weight_bias_grad(dy2, x2):
     return _weight_grad(dy2, x2), be.column_sum(dy2 if dy2.is_contiguous() else dy2.contiguous())
 
 
+def _xty_masked_wanted(be, dy2, x2):
+    """The conditions of _weight_bias_grad's one-pass form, for a backend that has the masked kernel (config.XTY_MASKED; MGX_XTY_MASKED=0:
+    the composition relu_dropout_bwd + xty)."""
+    return (config.XTY_MASKED and os.environ.get("MGX_XTY_MASKED", "1") != "0" and hasattr(be, "xty_masked") and dy2.dim() == 2
+            and x2.shape[0] >= be.XTY_MIN_ROWS and dy2.shape[1] <= be.XTY_MAX[0] and x2.shape[1] <= be.XTY_MAX[1]
+            and config.LINEAR_XTY and config.XTY_COLSUM)
+
+
 class LinearSumFn(torch.autograd.Function):
     """y = x1 W1^T + x2 W2^T + b in two GEMMs, the second accumulating into the first's output (no separate add pass);
     gradients as LinearFn.  SAGEConv's `fc_self(h) + fc_neigh(h_neigh)` (main_dgl_product_sage.py:64)."""
@@ -1150,6 +1158,7 @@ class SageMeanCatFn(torch.autograd.Function):
         K = cat.K
         dh = None
         aggregated_first = False
+        masked = None
         if ctx.p is not None:
             w_self, w_neigh, mask = ctx.saved_tensors
             if not dy.is_contiguous() and not be._row_strided(dy):
@@ -1177,9 +1186,17 @@ class SageMeanCatFn(torch.autograd.Function):
                     dh = dcat @ torch.cat([w_self, w_neigh], dim=0)
                 aggregated_first = True
             else:
-                dy = be.relu_dropout_bwd(dy, mask, ctx.p)  # the gradient of the pre-activation, as ReluDropout.backward forms it
+                if not need[2] and (need[3] or need[4]) and need[5] and _xty_masked_wanted(be, dy, cat.buf):
+                    # layer 1 (its input takes no gradient): d z = relu_dropout_bwd(d y) would be written once and read twice by the weight
+                    # gradient's two launches and for nothing else -- the mask is applied as that kernel loads d y instead, same bits
+                    masked = be.xty_masked(dy, mask, ctx.p, cat.buf)
+                if masked is None:
+                    dy = be.relu_dropout_bwd(dy, mask, ctx.p)  # the gradient of the pre-activation, as ReluDropout.backward forms it
         else:
             w_self, w_neigh = ctx.saved_tensors
+        if masked is not None:
+            dw, db = masked
+            return None, None, None, dw[:, :K].contiguous(), dw[:, K:].contiguous(), db, None
         if not aggregated_first:
             dy = dy.contiguous()
         if need[2] and not aggregated_first:

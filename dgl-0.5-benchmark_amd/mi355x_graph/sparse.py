@@ -1282,6 +1282,31 @@ class HipBackend(object):
         _lib.check(st)
         return (out, sums) if colsum else out
 
+    def xty_masked(self, dy, mask, p, b2d):
+        """(dz^T b2d [64, K], column sums of dz [64]) for dz = relu_dropout_bwd(dy, mask, p), which is never stored: the mask is applied
+        to dy as the kernel loads it (mgx_xty_colsum_masked).  Bit for bit xty(relu_dropout_bwd(dy, mask, p), b2d, colsum=True).
+        dy [n, 64] and b2d [n, K]: unit column stride, row strides % 4 == 0, 16-byte aligned; mask: the uint8 [n * 16] of relu_dropout_fwd.
+        None -- nothing launched -- when no kernel is built for the operands (K outside the built 64, 68 .. 80, 128, 196 .. 208, 256)."""
+        dev = self._check_dev(dy, mask, b2d)
+        if (dy.dim() != 2 or b2d.dim() != 2 or dy.shape[1] != 64 or b2d.shape[0] != dy.shape[0] or dy.dtype != torch.float32
+                or b2d.dtype != torch.float32 or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != dy.shape[0] * 16):
+            return None
+        n, K = b2d.shape
+        if (K < 64 or K > 256 or K % 4 or dy.stride(1) != 1 or b2d.stride(1) != 1 or max(dy.stride(0), 64) % 4 or max(b2d.stride(0), K) % 4
+                or dy.data_ptr() % 16 or b2d.data_ptr() % 16):
+            return None
+        L = _lib.lib()
+        out = torch.empty((64, K), dtype=torch.float32, device=dev)
+        sums = torch.empty(64, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.mgx_xty_masked_workspace(K) // 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = L.mgx_xty_colsum_masked(n, K, _ptr(dy), max(dy.stride(0), 64), _ptr(mask), ctypes.c_float(p), _ptr(b2d), max(b2d.stride(0), K),
+                                         _ptr(out), out.stride(0), _ptr(sums), _ptr(ws), _stream(dev))
+        if st == _lib.ERR_UNSUPPORTED:
+            return None
+        _lib.check(st)
+        return out, sums
+
     def xty(self, a2d, b2d, colsum=False, rows=None):
         """a2d [n, M], b2d [n, K] -> a^T b [M, K] (the tall-skinny weight-gradient product).  colsum=True: (a^T b, column sums of a) --
         the bias gradient from the same pass over a when the shape allows (mgx_xty_colsum), else by mgx_column_sum.

@@ -574,6 +574,17 @@ int32_t mgx_xty_colsum_rows(int64_t n, int64_t M, int64_t K, const float* a, int
  * be NULL.  Built for the shapes of mgx_xty_rows; else MGX_ERR_UNSUPPORTED.  a_pos == NULL: mgx_xty_colsum.  Same workspace. */
 int32_t mgx_xty_colsum_pos(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const int64_t* a_pos, const float* b,
                            int64_t ldb, float* out, int64_t ldc, float* colsum, void* workspace, void* stream);
+/* mgx_xty_colsum of dZ [n, 64] against b [n, K] where dZ is the gradient behind relu + dropout and is never stored: dZ[r][j] =
+ * dy[r][j] * (1 / (1 - p)) where bit j % 4 of mask[r * 16 + j / 4] is set, else 0.f (a select: an Inf or NaN behind a cleared bit does
+ * not reach a sum) -- mask as mgx_relu_dropout_fwd / mgx_rows_gemm_relu_dropout write it for 64 columns, uint8 [n * 16].  One pass over
+ * dy, mask and b and one finish launch instead of mgx_relu_dropout_bwd + one mgx_xty(_colsum) per 128 columns of b.  Bit for bit the
+ * result of that composition (out[:, k0 : k0 + 128] = mgx_xty of b's column block k0 = 0, 128; colsum from the first): the same row
+ * partitions, the same MFMAs in the same order per accumulator, the same order of the partial sums.  64 <= K <= 256, K % 4 == 0; dy
+ * and b 16-byte aligned with row strides % 4 == 0; built for K = 64, 68 .. 80, 128, 196 .. 208 and 256, else MGX_ERR_UNSUPPORTED
+ * (nothing is launched).  Workspace of mgx_xty_masked_workspace(K) bytes (-1 outside 64 .. 256 or K % 4 != 0). */
+int64_t mgx_xty_masked_workspace(int64_t K);
+int32_t mgx_xty_colsum_masked(int64_t n, int64_t K, const float* dy, int64_t lddy, const uint8_t* mask, float p, const float* b,
+                              int64_t ldb, float* out, int64_t ldc, float* colsum, void* workspace, void* stream);
 
 /* C[n, M] = A[n, K] x B (+ bias[M]) for A with millions of rows and small K, M -- the dense projections either side of an aggregation
  * (SAGEConv's fc_self / fc_neigh on [h | mean_agg(h)], main_dgl_product_sage.py:23-24,64, and the input gradient d[h | neigh] = dY x W).
