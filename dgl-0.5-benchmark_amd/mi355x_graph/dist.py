@@ -600,12 +600,7 @@ class DistSageMeanCatFn(torch.autograd.Function):
                 work = comm.all_to_all_async(recv, send, plan.recv_splits, plan.send_splits)
             if static_cache is not None:
                 static_cache["version"], static_cache["recv"] = h._version, recv
-        if not cat.holds(h):  # the layer-1 input lives elsewhere: copied into the left half unless it is the same unmodified tensor
-            same = cat.static_key is not None and cat.static_key[0] is h and cat.static_key[1] == h._version
-            if not same or h.requires_grad or not config.SAGE_STATIC_CAT:
-                cat.left.copy_(h)
-                cat.static_key = None if h.requires_grad else (h, h._version)
-        cat.generation += 1
+        cat.take_input(h)  # the layer-1 input lives elsewhere: copied into the left half unless it is the same unmodified tensor
         comm.mark("owned-source aggregation")
         from . import ops
         tail_ops = ops._edge_tail_operands(be, plan.loc.csc(), cat, h) if hasattr(be, "edge_tail_of") else None
@@ -626,52 +621,37 @@ class DistSageMeanCatFn(torch.autograd.Function):
         ctx.plan, ctx.comm, ctx.cat, ctx.generation = plan, comm, cat, cat.generation
         ctx.halo_x = halo_x
         comm.mark("dense")
-        wcat = torch.cat([w_self, w_neigh], dim=1)
-        if act is not None:
-            # dropout(relu(.)) in the GEMM's epilogue, written into the next layer's left half (ops.SageMeanCatFn's fused form: same
-            # position in the random stream as ops.relu_dropout would take, same bits); the N x out pre-activation is never stored
-            p, into = act
-            seed = torch.initial_seed() & (2 ** 64 - 1)
-            offset = (ops.ReluDropout._calls * 0x9E3779B97F4A7C15) & (2 ** 63 - 1)
-            ops.ReluDropout._calls += 1
-            out = None if into is None else into.t
-            fused = be.rows_gemm_relu_dropout(cat.buf, wcat, True, bias, float(p), seed, offset, out=out)
-            y, mask = fused if fused is not None else be.relu_dropout_fwd(ops._rows_linear(be, cat.buf, wcat, bias), float(p), seed, offset, out=out)
-            ctx.save_for_backward(w_self, w_neigh, mask)
-            ctx.p = float(p)
-            return y
-        ctx.save_for_backward(w_self, w_neigh)
-        ctx.p = None
-        return ops._rows_linear(be, cat.buf, wcat, bias)
+        # act: dropout(relu(.)) in the GEMM's epilogue, written into the next layer's left half, as in ops.SageMeanCatFn (a backend
+        # without mgx_rows_gemm_relu_dropout is never handed one: DistGraph.sage_mean_layer_act)
+        y, mask = ops._cat_project(be, cat, w_self, w_neigh, bias, act)
+        ctx.save_for_backward(*((w_self, w_neigh) if mask is None else (w_self, w_neigh, mask)))
+        ctx.p = None if act is None else float(act[0])
+        return y
 
     @staticmethod
     @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
     def backward(ctx, dy):
         from . import ops
         plan, comm, cat = ctx.plan, ctx.comm, ctx.cat
-        if cat.generation != ctx.generation:
-            raise DGLError("SAGEConv: a later forward pass overwrote the [h | neigh] buffer this backward pass needs")
+        cat.check_generation(ctx.generation)
         be = sparse.backend_for(dy)
+        need = ctx.needs_input_grad
+        need_w = need[4] or need[5]
+        K = cat.K
         if ctx.p is not None:
             w_self, w_neigh, mask = ctx.saved_tensors
             if not dy.is_contiguous() and not (hasattr(be, "_row_strided") and be._row_strided(dy)):
                 dy = dy.contiguous()
-            need = ctx.needs_input_grad
-            masked = None
-            if not need[3] and (need[4] or need[5]) and need[6] and ops._xty_masked_wanted(be, dy, cat.buf):
-                masked = be.xty_masked(dy, mask, ctx.p, cat.buf)  # as ops.SageMeanCatFn.backward: d z is needed by the weight gradient only
-            if masked is not None:
+            # as ops.SageMeanCatFn.backward: where d z is needed by the weight gradient only, the mask is applied as that kernel loads d y
+            grads = ops._cat_param_grads_masked(be, dy, mask, ctx.p, cat.buf, K, need[3], need_w, need[6])
+            if grads is not None:
                 comm.mark("dense (inside the exchange window)")
-                dw, db = masked
-                dws, dwn = dw[:, :cat.K].contiguous(), dw[:, cat.K:].contiguous()
                 comm.mark("dense")
-                return None, None, None, None, dws, dwn, db, None, None, None
+                return (None, None, None, None) + grads + (None, None, None)
             dy = be.relu_dropout_bwd(dy, mask, ctx.p)  # the gradient of the pre-activation, as ops.ReluDropout.backward forms it
         else:
             w_self, w_neigh = ctx.saved_tensors
         dy = dy.contiguous()
-        need = ctx.needs_input_grad
-        K = cat.K
         dh = None
         if need[3]:
             dh_own, dn = ops._rows_dgrad(be, dy, torch.cat([w_self, w_neigh], dim=1), plan.inv_deg, K)  # d h, d neigh / deg: [n_own, K] each
@@ -691,15 +671,7 @@ class DistSageMeanCatFn(torch.autograd.Function):
         # the parameter gradients need nothing from the peers: formed while the halo-row gradients travel (the scaling model,
         # profiles/r04_scale_model.txt, has the exchange at 2x the reversed aggregation it used to hide behind at P = 8)
         comm.mark("dense (inside the exchange window)")
-        dws = dwn = db = None
-        if (need[4] or need[5]) and need[6]:
-            dw, db = ops._weight_bias_grad(dy, cat.buf)  # the bias gradient from the weight-gradient kernel's own pass over dy
-            dws, dwn = dw[:, :K].contiguous(), dw[:, K:].contiguous()
-        elif need[4] or need[5]:
-            dw = ops._weight_grad(dy, cat.buf)
-            dws, dwn = dw[:, :K].contiguous(), dw[:, K:].contiguous()
-        elif need[6]:
-            db = be.column_sum(dy)
+        dws, dwn, db = ops._cat_param_grads(be, dy, cat.buf, K, need_w, need[6])  # (the bias gradient from the weight gradient's own pass over dy)
         if need[3]:
             if halo_x is not None:
                 comm.mark("return-add")
@@ -954,7 +926,7 @@ class DistGraph(DGLGraph):
                 or (out is not None and (out.shape != (h.shape[0], w_self.shape[0]) or out.stride(1) != 1 or out.stride(0) % 4
                                          or out.data_ptr() % 16 or out.requires_grad))):
             return None
-        y = self.sage_mean_layer(h, w_self, w_neigh, bias, cat, act=(float(p), None if out is None else ops._Into(out)))
+        y = self.sage_mean_layer(h, w_self, w_neigh, bias, cat, act=(float(p), None if out is None else ops._Into(out), None))
         return ops._structural_zeros(y)
 
 

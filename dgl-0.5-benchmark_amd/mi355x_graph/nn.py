@@ -114,7 +114,7 @@ class GATConv(nn.Module):
 
     def _aggregate_first(self, graph, feat, get_attention):
         """One-head layers that WIDEN (in < out, e.g. 16 hidden -> 41 classes): aggregate the input rows, project afterwards.
-        Taken when the fused block exists for the input width and it saves a 16-column gather pass; MGX_GAT_AGG_FIRST=0 never."""
+        Taken when the fused block exists for the input width and it saves a 16-column gather pass; config.GAT_AGG_FIRST = False: never."""
         if (self._num_heads != 1 or isinstance(feat, tuple) or get_attention or not hasattr(self, "fc") or not torch.is_tensor(feat)
                 or feat.dim() != 2 or not config.GAT_AGG_FIRST):
             return False

@@ -34,6 +34,8 @@ def _torch_ops():
     return torch_ops
 
 
+_STREAM_STEP = 0x9E3779B97F4A7C15  # 2^64 / golden ratio: what one call moves a counter-based dropout generator on by
+
 _NATIVE = None
 
 
@@ -382,7 +384,7 @@ class GATFused(torch.autograd.Function):
         el2, er2 = el.contiguous().view(el.shape[0], H), er.contiguous().view(er.shape[0], H)
         seed = 0
         if p > 0.0:
-            seed = ((torch.initial_seed() & (2 ** 64 - 1)) ^ ((GATFused._calls * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)))
+            seed = ((torch.initial_seed() & (2 ** 64 - 1)) ^ ((GATFused._calls * _STREAM_STEP) & (2 ** 64 - 1)))
             GATFused._calls += 1
         be = sparse.backend_for(feat)
         if p > 0.0 and be.name == "hip":  # training with attn_drop: the backward needs the out-CSR anyway; the forward's choice of kernel too
@@ -686,16 +688,14 @@ class ReluDropout(torch.autograd.Function):
         be = sparse.backend_for(x)
         if out is None or not be._row_strided(x):
             x = x.contiguous()
-        seed = torch.initial_seed() & (2 ** 64 - 1)
         if capture_path():
             # a HIP graph freezes launch arguments: the position in the random stream comes from a device counter that the
             # captured step itself advances, so every replay draws a new mask
             ctr = _capture_counter(x.device)
-            y, mask = be.relu_dropout_fwd(x, float(p), seed, 0, out=out, counter=ctr)
+            y, mask = be.relu_dropout_fwd(x, float(p), torch.initial_seed() & (2 ** 64 - 1), 0, out=out, counter=ctr)
             ctr.add_(1)
         else:
-            offset = (ReluDropout._calls * 0x9E3779B97F4A7C15) & (2 ** 63 - 1)
-            ReluDropout._calls += 1
+            seed, offset = _dropout_stream_position()
             y, mask = be.relu_dropout_fwd(x, float(p), seed, offset, out=out)
         ctx.save_for_backward(mask)
         ctx.p = float(p)
@@ -709,6 +709,14 @@ class ReluDropout(torch.autograd.Function):
         if not dy.is_contiguous() and not be._row_strided(dy):
             dy = dy.contiguous()
         return be.relu_dropout_bwd(dy, mask, ctx.p), None, None
+
+
+def _dropout_stream_position():
+    """(seed, offset) of the next relu + dropout mask in the counter-based generator's stream -- taken by every eager call that draws one,
+    ReluDropout and the layers with the activation in their GEMM's epilogue alike -- and the stream moved on by one call."""
+    offset = (ReluDropout._calls * _STREAM_STEP) & (2 ** 63 - 1)
+    ReluDropout._calls += 1
+    return torch.initial_seed() & (2 ** 64 - 1), offset
 
 
 _WARMING_UP_FOR_CAPTURE = 0
@@ -1059,6 +1067,25 @@ class CatBuffer(object):
         return (h.dim() == 2 and h.shape == (self.buf.shape[0], self.K) and h.data_ptr() == self.buf.data_ptr()
                 and h.stride(0) == self.buf.stride(0) and h.stride(1) == 1)
 
+    def is_resident(self, h):
+        """h is the SAME tensor object, unmodified (version counter), as the one the left half was last copied from.  The buffer keeps a
+        reference to that tensor: a per-step temporary at a recycled address is a different object."""
+        return self.static_key is not None and self.static_key[0] is h and self.static_key[1] == h._version
+
+    def take_input(self, h):
+        """Begin a forward pass over the layer input h: one that lives elsewhere -- the model's input features -- is copied into the
+        left half, unless it is the resident input (config.SAGE_STATIC_CAT; never one that takes a gradient); the pass is counted."""
+        if not self.holds(h) and (not self.is_resident(h) or h.requires_grad or not config.SAGE_STATIC_CAT):
+            self.left.copy_(h)
+            self.static_key = None if h.requires_grad else (h, h._version)
+        self.generation += 1
+
+    def check_generation(self, generation):
+        """A backward pass whose forward pass left the counter at `generation` may read the buffer only while it still stands there."""
+        if self.generation != generation:
+            raise DGLError("SAGEConv: a later forward pass overwrote the [h | neigh] buffer this backward pass needs (two forwards "
+                           "before one backward); set mi355x_graph.config.SAGE_CAT = False")
+
 
 # mgx_rows_gemm (csrc/rowsgemm.hip) for the projections of a layer over a CatBuffer: tall inputs only (the library GEMM wins below,
 # and the staging of B is per workgroup).  config.ROWS_GEMM = False: the library GEMM (+ the separate 1 / deg pass) everywhere.
@@ -1088,19 +1115,58 @@ def _rows_linear(be, x2d, weight, bias):
     return torch.nn.functional.linear(x2d, weight, bias)
 
 
+def _cat_project(be, cat, w_self, w_neigh, bias, act=None):
+    """(y, None) for y = [h | neigh] [W_self | W_neigh]^T + bias over every row of the CatBuffer, ONE GEMM; with act = (p, into, made):
+    (dropout(relu(y), p), its mask) from that GEMM's epilogue (mgx_rows_gemm_relu_dropout) -- the activation lands in `into` (the next
+    layer's buffer, or None: a new matrix), the N x out pre-activation is never stored, and the mask takes the position in the random
+    stream that ops.relu_dropout would take here.  made = [slots, overflow, written?] or None: the activation's rows as 128-byte
+    slots too.  No fused kernel for the operand after all: the composition it stands for, same seed and offset (same bits)."""
+    if act is None:
+        return _rows_linear(be, cat.buf, torch.cat([w_self, w_neigh], dim=1), bias), None
+    p, into, made = act
+    out = None if into is None else into.t
+    seed, offset = _dropout_stream_position()
+    wcat = torch.cat([w_self, w_neigh], dim=1)
+    fused = be.rows_gemm_relu_dropout(cat.buf, wcat, True, bias, float(p), seed, offset, out=out,
+                                      slots=None if made is None else made[0], overflow=None if made is None else made[1])
+    if fused is None:
+        return be.relu_dropout_fwd(_rows_linear(be, cat.buf, wcat, bias), float(p), seed, offset, out=out)
+    if made is not None:
+        made[2] = True
+    return fused
+
+
+def _split_cat_grad(dw, K):
+    """d[W_self | W_neigh] [out, 2K] -> (dW_self, dW_neigh)"""
+    return dw[:, :K].contiguous(), dw[:, K:].contiguous()
+
+
+def _cat_param_grads(be, dy, buf, K, need_w, need_b):
+    """(dW_self, dW_neigh, db) of a layer over a CatBuffer from dy [N, out] and buf = [h | neigh]: weight and bias from ONE pass over dy
+    where both are asked for (_weight_bias_grad), else the weight alone, else the column sums."""
+    if need_w and need_b:
+        dw, db = _weight_bias_grad(dy, buf)  # [out, 2K], [out]
+        return _split_cat_grad(dw, K) + (db,)
+    if need_w:
+        return _split_cat_grad(_weight_grad(dy, buf), K) + (None,)
+    return None, None, be.column_sum(dy if dy.is_contiguous() else dy.contiguous()) if need_b else None
+
+
+def _cat_param_grads_masked(be, dy, mask, p, buf, K, need_dh, need_w, need_b):
+    """_cat_param_grads(relu_dropout_bwd(dy, mask, p)) for a layer whose input takes no gradient (layer 1), or None: d z would be
+    written once and read twice by the weight gradient's two launches and for nothing else -- the mask is applied as that kernel loads
+    d y instead (mgx_xty_colsum_masked), same bits."""
+    if need_dh or not (need_w and need_b) or not _xty_masked_wanted(be, dy, buf):
+        return None
+    masked = be.xty_masked(dy, mask, p, buf)
+    return None if masked is None else _split_cat_grad(masked[0], K) + (masked[1],)
+
+
 def _cat_aggregate(be, gidx, cat, h):
     """The forward aggregation of a layer over a CatBuffer: h into the left half (unless it lives there or is the resident input), its
     mean over the in-edges into the right half, every row."""
     csc = gidx.csc()
-    if not cat.holds(h):
-        # a layer input that lives elsewhere -- the model's input features -- is copied into the left half; when it is the
-        # SAME tensor object, unmodified (version counter), as in the previous pass the copy is skipped.  The buffer keeps
-        # a reference to that tensor: a per-step temporary at a recycled address is a different object and is copied.
-        same = cat.static_key is not None and cat.static_key[0] is h and cat.static_key[1] == h._version
-        if not same or h.requires_grad or not config.SAGE_STATIC_CAT:
-            cat.left.copy_(h)
-            cat.static_key = None if h.requires_grad else (h, h._version)
-    cat.generation += 1
+    cat.take_input(h)
     tail_ops = _edge_tail_operands(be, csc, cat, h)
     if tail_ops is not None:
         # the constant 100-column input: columns 0 .. 95 as a compact block (three cache lines per row instead of four and an eighth),
@@ -1121,44 +1187,22 @@ class SageMeanCatFn(torch.autograd.Function):
         be = sparse.backend_for(h)
         _cat_aggregate(be, gidx, cat, h)
         ctx.gidx, ctx.cat, ctx.generation = gidx, cat, cat.generation
-        if act is not None:
-            # relu + dropout in the GEMM's epilogue (mgx_rows_gemm_relu_dropout): the activation lands in the next layer's buffer and
-            # the N x out pre-activation is never stored.  Same position in the random stream as ops.relu_dropout would take.
-            p, into = act[0], act[1]
-            made = act[2] if len(act) > 2 else None  # [slots, overflow, written?]: the activation's rows as 128-byte slots too
-            seed = torch.initial_seed() & (2 ** 64 - 1)
-            offset = (ReluDropout._calls * 0x9E3779B97F4A7C15) & (2 ** 63 - 1)
-            ReluDropout._calls += 1
-            wcat = torch.cat([w_self, w_neigh], dim=1)
-            fused = be.rows_gemm_relu_dropout(cat.buf, wcat, True, bias, float(p), seed, offset, out=None if into is None else into.t,
-                                              slots=None if made is None else made[0], overflow=None if made is None else made[1])
-            if fused is not None and made is not None:
-                made[2] = True
-            if fused is None:  # no fused kernel for this operand after all: the composition it stands for, same seed and offset (same bits)
-                y, mask = be.relu_dropout_fwd(_rows_linear(be, cat.buf, wcat, bias), float(p), seed, offset,
-                                              out=None if into is None else into.t)
-            else:
-                y, mask = fused
-            ctx.save_for_backward(w_self, w_neigh, mask)
-            ctx.p = float(p)
-            return y
-        ctx.save_for_backward(w_self, w_neigh)
-        ctx.p = None
-        return _rows_linear(be, cat.buf, torch.cat([w_self, w_neigh], dim=1), bias)
+        y, mask = _cat_project(be, cat, w_self, w_neigh, bias, act)
+        ctx.save_for_backward(*((w_self, w_neigh) if mask is None else (w_self, w_neigh, mask)))
+        ctx.p = None if act is None else float(act[0])
+        return y
 
     @staticmethod
     @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
     def backward(ctx, dy):
         cat = ctx.cat
-        if cat.generation != ctx.generation:
-            raise DGLError("SAGEConv: a later forward pass overwrote the [h | neigh] buffer this backward pass needs "
-                           "(two forwards before one backward); set MGX_SAGE_CAT=0")
+        cat.check_generation(ctx.generation)
         need = ctx.needs_input_grad
+        need_w = need[3] or need[4]
         be = sparse.backend_for(dy)
         K = cat.K
         dh = None
         aggregated_first = False
-        masked = None
         if ctx.p is not None:
             w_self, w_neigh, mask = ctx.saved_tensors
             if not dy.is_contiguous() and not be._row_strided(dy):
@@ -1186,17 +1230,12 @@ class SageMeanCatFn(torch.autograd.Function):
                     dh = dcat @ torch.cat([w_self, w_neigh], dim=0)
                 aggregated_first = True
             else:
-                if not need[2] and (need[3] or need[4]) and need[5] and _xty_masked_wanted(be, dy, cat.buf):
-                    # layer 1 (its input takes no gradient): d z = relu_dropout_bwd(d y) would be written once and read twice by the weight
-                    # gradient's two launches and for nothing else -- the mask is applied as that kernel loads d y instead, same bits
-                    masked = be.xty_masked(dy, mask, ctx.p, cat.buf)
-                if masked is None:
-                    dy = be.relu_dropout_bwd(dy, mask, ctx.p)  # the gradient of the pre-activation, as ReluDropout.backward forms it
+                grads = _cat_param_grads_masked(be, dy, mask, ctx.p, cat.buf, K, need[2], need_w, need[5])
+                if grads is not None:
+                    return (None, None, None) + grads + (None,)
+                dy = be.relu_dropout_bwd(dy, mask, ctx.p)  # the gradient of the pre-activation, as ReluDropout.backward forms it
         else:
             w_self, w_neigh = ctx.saved_tensors
-        if masked is not None:
-            dw, db = masked
-            return None, None, None, dw[:, :K].contiguous(), dw[:, K:].contiguous(), db, None
         if not aggregated_first:
             dy = dy.contiguous()
         if need[2] and not aggregated_first:
@@ -1204,72 +1243,65 @@ class SageMeanCatFn(torch.autograd.Function):
             # else the GEMM and a streaming pass over that half -- never a per-edge factor
             dh, dn = _rows_dgrad(be, dy, torch.cat([w_self, w_neigh], dim=1), ctx.gidx.csc().inv_degrees(), K)
             be.spmm_copy_u_strided(ctx.gidx.csr(), "sum", dn, dh, accumulate=True)
-        dws = dwn = db = None
-        if (need[3] or need[4]) and need[5]:
-            dw, db = _weight_bias_grad(dy, cat.buf)               # [out, 2K], [out]: one pass over dy
-            dws, dwn = dw[:, :K].contiguous(), dw[:, K:].contiguous()
-        elif need[3] or need[4]:
-            dw = _weight_grad(dy, cat.buf)                        # [out, 2K]
-            dws, dwn = dw[:, :K].contiguous(), dw[:, K:].contiguous()
-        elif need[5]:
-            db = be.column_sum(dy if dy.is_contiguous() else dy.contiguous())
+        dws, dwn, db = _cat_param_grads(be, dy, cat.buf, K, need_w, need[5])
         return None, None, dh, dws, dwn, db, None
 
 
-_ROW_BITS = {}  # (rows.data_ptr(), len, N) -> (rows, version, bitmap): the loss rows of a training run are one tensor, reused every step
-# (this and the two caches below hold what was derived from a row list: same tensor object AND same version counter, so a list written
-# in place is derived again; a write behind autograd's back -- `.data`, a raw kernel -- is not seen: do not change a row list that way)
+def _of_row_list(cache, rows, extra, ident, build, *args):
+    """What build(*args) derives from the row list `rows`, kept in `cache` under (address, length, extra) for as long as `rows` is the
+    same tensor object at the same version counter (and `ident`, a second operand or None, the same object): the loss rows of a training
+    run are one tensor, reused every step, and a list written in place is derived again.  A write behind autograd's back -- `.data`, a
+    raw kernel -- is not seen: do not change a row list that way.  A cache that has grown past 8 entries is emptied first."""
+    key = (rows.data_ptr(), int(rows.shape[0]), extra)
+    held = cache.get(key)
+    if held is None or held[0] is not rows or held[1] != rows._version or held[2] is not ident:
+        if len(cache) > 8:
+            cache.clear()
+        held = cache[key] = (rows, rows._version, ident, build(*args))
+    return held[3]
+
+
+_ROW_BITS = {}     # per (rows, N): the bitmap of the listed nodes
+_ROW_INV_DEG = {}  # per (rows, inv_deg): inv_deg[rows] -- one gather per row list, not per step
+_ROW_POS = {}      # per (rows, N): int64 [N], the place of a node in `rows`, -1 outside
+
+
+def _build_row_bits(rows, n, be):
+    flag = torch.zeros((n, 4), dtype=torch.float32, device=rows.device)
+    flag[rows] = 1.0
+    return be.row_nonzero_bits(flag)
+
+
+def _build_row_pos(rows, n):
+    pos = torch.full((n,), -1, dtype=torch.int64, device=rows.device)
+    pos[rows] = torch.arange(rows.shape[0], dtype=torch.int64, device=rows.device)
+    return pos
 
 
 def _row_bits(rows, n, be):
-    key = (rows.data_ptr(), int(rows.shape[0]), int(n))
-    held = _ROW_BITS.get(key)
-    if held is None or held[0] is not rows or held[1] != rows._version:
-        flag = torch.zeros((n, 4), dtype=torch.float32, device=rows.device)
-        flag[rows] = 1.0
-        if len(_ROW_BITS) > 8:
-            _ROW_BITS.clear()
-        held = _ROW_BITS[key] = (rows, rows._version, be.row_nonzero_bits(flag))
-    return held[2]
-
-
-_ROW_INV_DEG = {}  # (rows.data_ptr(), len, inv_deg.data_ptr()) -> (rows, inv_deg, inv_deg[rows]): one gather per row list, not per step
+    return _of_row_list(_ROW_BITS, rows, int(n), None, _build_row_bits, rows, n, be)
 
 
 def _row_inv_deg(rows, inv_deg):
-    key = (rows.data_ptr(), int(rows.shape[0]), inv_deg.data_ptr())
-    held = _ROW_INV_DEG.get(key)
-    if held is None or held[0] is not rows or held[1] is not inv_deg or held[3] != rows._version:
-        if len(_ROW_INV_DEG) > 8:
-            _ROW_INV_DEG.clear()
-        held = _ROW_INV_DEG[key] = (rows, inv_deg, inv_deg.index_select(0, rows), rows._version)
-    return held[2]
-
-
-_ROW_POS = {}  # (rows.data_ptr(), len, N) -> (rows, int64 [N]: the place of a node in `rows`, -1 outside)
+    return _of_row_list(_ROW_INV_DEG, rows, inv_deg.data_ptr(), inv_deg, inv_deg.index_select, 0, rows)
 
 
 def _row_pos(rows, n):
-    key = (rows.data_ptr(), int(rows.shape[0]), int(n))
-    held = _ROW_POS.get(key)
-    if held is None or held[0] is not rows or held[2] != rows._version:
-        pos = torch.full((n,), -1, dtype=torch.int64, device=rows.device)
-        pos[rows] = torch.arange(rows.shape[0], dtype=torch.int64, device=rows.device)
-        if len(_ROW_POS) > 8:
-            _ROW_POS.clear()
-        held = _ROW_POS[key] = (rows, pos, rows._version)
-    return held[1]
+    return _of_row_list(_ROW_POS, rows, int(n), None, _build_row_pos, rows, n)
 
 
-def _head_rows_forward(be, gidx, cat, h, w_self, w_neigh, bias, rows):
-    """[h | mean_agg(h)][rows] x [W_self | W_neigh]^T + bias -> [R, out]: every row aggregated (the right half of the buffer fully
-    written: the weight gradient and every later reader see what SageMeanCatFn leaves), the listed rows projected -- read in place by
-    mgx_rows_gemm_rows where it has the shape, else gathered for the library GEMM."""
+def _head_rows_forward(ctx, gidx, cat, h, w_self, w_neigh, bias, rows):
+    """The forward of SageMeanCatHeadFn and SageMeanCatRowsFn: [h | mean_agg(h)][rows] x [W_self | W_neigh]^T + bias -> [R, out]: every
+    row aggregated (the right half of the buffer fully written: the weight gradient and every later reader see what SageMeanCatFn
+    leaves), the listed rows projected -- read in place by mgx_rows_gemm_rows where it has the shape, else gathered for the library GEMM."""
+    be = sparse.backend_for(h)
     _cat_aggregate(be, gidx, cat, h)
     wcat = torch.cat([w_self, w_neigh], dim=1)
     y = be.rows_gemm(cat.buf, wcat, b_transposed=True, bias=bias, rows=rows) if config.ROWS_GEMM else None
     if y is None:
         y = torch.nn.functional.linear(cat.buf.index_select(0, rows), wcat, bias)
+    ctx.gidx, ctx.cat, ctx.generation, ctx.rows = gidx, cat, cat.generation, rows
+    ctx.save_for_backward(w_self, w_neigh)
     return y
 
 
@@ -1329,12 +1361,24 @@ def _head_rows_dense_backward(be, gidx, cat, w_self, w_neigh, dyr, rows, need_dh
         res = be.xty_pos(dyr, _row_pos(rows, n), cat.buf, colsum=need_b) if n >= be.XTY_MIN_ROWS and config.LINEAR_XTY and config.XTY_COLSUM else None
         if res is None:
             dy = torch.zeros((n, dyr.shape[1]), dtype=dyr.dtype, device=dyr.device).index_copy_(0, rows, dyr)
-            res = _weight_bias_grad(dy, cat.buf) if need_b else _weight_grad(dy, cat.buf)
-        dw, db = res if need_b else (res, None)
-        dws, dwn = dw[:, :K].contiguous(), dw[:, K:].contiguous()
+            dws, dwn, db = _cat_param_grads(be, dy, cat.buf, K, True, need_b)
+        else:
+            dw, db = res if need_b else (res, None)
+            dws, dwn = _split_cat_grad(dw, K)
     elif need_b:
         db = be.column_sum(dyr)
     return d_self, dn, dws, dwn, db
+
+
+def _head_rows_backward(ctx, dyr, zero_fill):
+    """What the backward passes of SageMeanCatHeadFn and SageMeanCatRowsFn begin with: (be, need d h?) + _head_rows_dense_backward's results."""
+    w_self, w_neigh = ctx.saved_tensors
+    ctx.cat.check_generation(ctx.generation)
+    dyr = dyr.contiguous()
+    need = ctx.needs_input_grad
+    be = sparse.backend_for(dyr)
+    return (be, need[2]) + _head_rows_dense_backward(be, ctx.gidx, ctx.cat, w_self, w_neigh, dyr, ctx.rows, need[2], need[3] or need[4],
+                                                     need[5], zero_fill)
 
 
 class SageMeanCatHeadFn(torch.autograd.Function):
@@ -1352,32 +1396,20 @@ class SageMeanCatHeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gidx, cat, h, w_self, w_neigh, bias, rows):
-        be = sparse.backend_for(h)
-        y = _head_rows_forward(be, gidx, cat, h, w_self, w_neigh, bias, rows)
-        ctx.gidx, ctx.cat, ctx.generation, ctx.rows = gidx, cat, cat.generation, rows
-        ctx.save_for_backward(w_self, w_neigh)
-        return y
+        return _head_rows_forward(ctx, gidx, cat, h, w_self, w_neigh, bias, rows)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dyr):
-        w_self, w_neigh = ctx.saved_tensors
-        cat, rows = ctx.cat, ctx.rows
-        if cat.generation != ctx.generation:
-            raise DGLError("SAGEConv: a later forward pass overwrote the [h | neigh] buffer this backward pass needs")
-        dyr = dyr.contiguous()
-        need = ctx.needs_input_grad
-        be = sparse.backend_for(dyr)
-        d_self, dn, dws, dwn, db = _head_rows_dense_backward(be, ctx.gidx, cat, w_self, w_neigh, dyr, rows, need[2], need[3] or need[4],
-                                                             need[5], True)
+        rows = ctx.rows
+        be, need_dh, d_self, dn, dws, dwn, db = _head_rows_backward(ctx, dyr, True)
         dh = None
-        if need[2]:
+        if need_dh:
             # d self on the rows of a zero matrix, the reversed aggregation accumulating into it: what the layer over all rows does,
             # bit for bit (its d self is zero outside the rows).  Aggregating into a new matrix and adding d self afterwards saves the
             # kernel's read of its output, but the kernel starts a row's sum from the value it accumulates into: other bits.
             # config.SAGE_HEAD_INIT: the same sums started from the compact d self through the position map
             # (mgx_spmm_copy_u_strided_init) -- no zero matrix, no copy into it, no read of it; the sequence below where it declines
-            dh = None
             if config.SAGE_HEAD_INIT and d_self.stride(1) == 1:
                 dh = be.spmm_copy_u_strided_init(ctx.gidx.csr(), "sum", dn, d_self, _row_pos(rows, dn.shape[0]), torch.empty_like(dn))
             if dh is None:
@@ -1393,27 +1425,16 @@ class SageMeanCatRowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gidx, cat, h, w_self, w_neigh, bias, rows):
-        be = sparse.backend_for(h)
-        y = _head_rows_forward(be, gidx, cat, h, w_self, w_neigh, bias, rows)
-        ctx.gidx, ctx.cat, ctx.generation, ctx.rows = gidx, cat, cat.generation, rows
-        ctx.save_for_backward(w_self, w_neigh)
-        return y
+        return _head_rows_forward(ctx, gidx, cat, h, w_self, w_neigh, bias, rows)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dyr):
-        w_self, w_neigh = ctx.saved_tensors
-        cat, rows = ctx.cat, ctx.rows
-        if cat.generation != ctx.generation:
-            raise DGLError("SAGEConv: a later forward pass overwrote the [h | neigh] buffer this backward pass needs")
-        dyr = dyr.contiguous()
-        need = ctx.needs_input_grad
-        be = sparse.backend_for(dyr)
-        d_self, dn, dws, dwn, db = _head_rows_dense_backward(be, ctx.gidx, cat, w_self, w_neigh, dyr, rows, need[2], need[3] or need[4],
-                                                             need[5], False)
+        rows = ctx.rows
+        be, need_dh, d_self, dn, dws, dwn, db = _head_rows_backward(ctx, dyr, False)
         dh = None
-        if need[2]:
-            dh = be.spmm_copy_u_masked(ctx.gidx.csr(), "sum", dn, _row_bits(rows, cat.buf.shape[0], be))
+        if need_dh:
+            dh = be.spmm_copy_u_masked(ctx.gidx.csr(), "sum", dn, _row_bits(rows, dn.shape[0], be))
             dh.index_add_(0, rows, d_self)
         return None, None, dh, dws, dwn, db, None
 
@@ -1500,8 +1521,7 @@ class SageMeanStaticInputProjectFn(torch.autograd.Function):
     def forward(ctx, gidx, cat, x, w_self, w_neigh, bias):
         be = sparse.backend_for(x)
         K = w_self.shape[0]
-        same = cat.static_key is not None and cat.static_key[0] is x and cat.static_key[1] == x._version
-        if not same or cat.static_agg is not cat.static_key:
+        if not cat.is_resident(x) or cat.static_agg is not cat.static_key:
             cat.left.copy_(x)
             cat.static_key = (x, x._version)
             be.spmm_copy_u_strided(gidx.csc(), "mean", cat.left, cat.right)      # A_mean x: once per (tensor, version)
@@ -1519,8 +1539,7 @@ class SageMeanStaticInputProjectFn(torch.autograd.Function):
     @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
     def backward(ctx, dy):
         cat = ctx.cat
-        if cat.generation != ctx.generation:
-            raise DGLError("SAGEConv: the cached [x | mean_agg(x)] buffer was rewritten before this backward pass")
+        cat.check_generation(ctx.generation)
         need = ctx.needs_input_grad
         be = sparse.backend_for(dy)
         if dy.stride(1) != 1:
@@ -1537,12 +1556,9 @@ class SageMeanStaticInputProjectFn(torch.autograd.Function):
 def sage_static_input_project(g, x, w_self, w_neigh, bias, cat):
     """SageMeanStaticInputProjectFn when it applies (opt-in switch, constant input, out_feats < in_feats), else None."""
     K, D = w_self.shape
-    if (os.environ.get("MGX_SAGE_L1_PROJECT_FIRST", "0") != "1" or cat is None or x.requires_grad or type(g) is not DGLGraph
-            or g.is_block or x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or x.device.type not in sparse._BACKENDS
-            or not torch.is_grad_enabled() or g.idtype != torch.int32 or cat.K != D or cat.buf.shape[0] != x.shape[0]
-            or g.number_of_src_nodes() != g.number_of_dst_nodes() or x.shape[0] != g.number_of_src_nodes()
-            or K % 4 or D % 4 or K >= D or _torch_ops() is not None or not _cat_eligible(g, x, cat)
-            or (bias is not None and K > sparse.backend_for(x).COLUMN_SUM_MAX) or x.shape[0] * 2 * K * 4 >= (1 << 32)):
+    if (os.environ.get("MGX_SAGE_L1_PROJECT_FIRST", "0") != "1" or cat is None or x.requires_grad
+            or not _fused_layer_operands(g, x, w_self, bias) or cat.K != D or cat.buf.shape[0] != x.shape[0]
+            or K % 4 or D % 4 or K >= D or not _cat_eligible(g, x, cat) or x.shape[0] * 2 * K * 4 >= (1 << 32)):
         return None
     return SageMeanStaticInputProjectFn.apply(g._index, cat, x, w_self, w_neigh, bias)
 
@@ -1554,11 +1570,7 @@ def sage_project_first(g, h, w_self, w_neigh, bias=None):
     K, D = w_self.shape
     if hasattr(g, "sage_project_first"):  # dist.DistGraph: the same form with the halo exchange at the output width
         return g.sage_project_first(h, w_self, w_neigh, bias)
-    if (type(g) is not DGLGraph or g.is_block or h.dim() != 2 or h.dtype != torch.float32 or not h.is_cuda
-            or h.device.type not in sparse._BACKENDS or not torch.is_grad_enabled() or g.idtype != torch.int32
-            or g.number_of_src_nodes() != g.number_of_dst_nodes() or h.shape[0] != g.number_of_src_nodes()
-            or K % 4 or K > 128 or _torch_ops() is not None or not config.SAGE_PROJECT_FIRST
-            or (bias is not None and K > sparse.backend_for(h).COLUMN_SUM_MAX)
+    if (not _fused_layer_operands(g, h, w_self, bias) or K % 4 or K > 128 or not config.SAGE_PROJECT_FIRST
             or g.number_of_src_nodes() * 2 * K * 4 >= (1 << 32)):
         return None
     aggs_now = 2 if h.requires_grad else 1
@@ -1572,12 +1584,7 @@ def sage_mean_layer(g, h, w_self, w_neigh, bias=None, cat=None):
     not apply (the caller then composes update_all + linear_sum)."""
     if hasattr(g, "sage_mean_layer"):  # dist.DistGraph: the same one-GEMM layer with the halo exchange inside
         return g.sage_mean_layer(h, w_self, w_neigh, bias, cat)
-    if (type(g) is not DGLGraph or g.is_block or h.dim() != 2 or h.dtype != torch.float32
-            or not h.is_cuda or h.device.type not in sparse._BACKENDS or not torch.is_grad_enabled()
-            or g.number_of_src_nodes() != g.number_of_dst_nodes() or h.shape[0] != g.number_of_src_nodes()
-            or g.idtype != torch.int32  # the accumulating aggregation is exercised on the int32 kernels only
-            or (bias is not None and w_self.shape[0] > sparse.backend_for(h).COLUMN_SUM_MAX)
-            or _torch_ops() is not None or not config.SAGE_FUSED_LAYER):
+    if not _fused_layer_operands(g, h, w_self, bias) or not config.SAGE_FUSED_LAYER:
         return None
     if cat is not None and _cat_eligible(g, h, cat):
         return SageMeanCatFn.apply(g._index, cat, h, w_self, w_neigh, bias)
@@ -1590,12 +1597,9 @@ def sage_mean_layer_act(g, h, w_self, w_neigh, bias, cat, p, out):
     over the N x out pre-activation less each way.  None when that form does not apply (the caller composes the two)."""
     if hasattr(g, "sage_mean_layer_act"):  # dist.DistGraph: the same fused layer with the halo exchange inside
         return g.sage_mean_layer_act(h, w_self, w_neigh, bias, cat, p, out)
-    if (not config.SAGE_FUSED_ACT or not config.ROWS_GEMM or type(g) is not DGLGraph or cat is None or capture_path()
-            or not (0.0 < p < 1.0) or h.dim() != 2 or h.dtype != torch.float32 or not h.is_cuda or h.device.type not in sparse._BACKENDS
-            or not torch.is_grad_enabled() or g.is_block or g.number_of_src_nodes() != g.number_of_dst_nodes()
-            or h.shape[0] != g.number_of_src_nodes() or h.shape[0] < _ROWS_GEMM_MIN or g.idtype != torch.int32
-            or _torch_ops() is not None or not config.SAGE_FUSED_LAYER or not _cat_eligible(g, h, cat)
-            or (bias is not None and w_self.shape[0] > sparse.backend_for(h).COLUMN_SUM_MAX) or w_self.shape[0] % 4
+    if (not config.SAGE_FUSED_ACT or not config.ROWS_GEMM or cat is None or capture_path() or not (0.0 < p < 1.0)
+            or not _fused_layer_operands(g, h, w_self, bias) or h.shape[0] < _ROWS_GEMM_MIN
+            or not config.SAGE_FUSED_LAYER or not _cat_eligible(g, h, cat) or w_self.shape[0] % 4
             or not sparse.backend_for(h).rows_gemm_supported(2 * cat.K, w_self.shape[0], cat.buf.stride(0))
             or (out is not None and (out.shape != (h.shape[0], w_self.shape[0]) or out.stride(1) != 1 or out.stride(0) % 4
                                      or out.data_ptr() % 16 or out.requires_grad))):
@@ -1617,6 +1621,16 @@ def sage_mean_layer_act(g, h, w_self, w_neigh, bias, cat, p, out):
     if made is not None and made[2]:
         y._mgx_slots = (made[0], made[1], int(y._version))
     return y
+
+
+def _fused_layer_operands(g, h, w_self, bias):
+    """What every fused SAGE layer form asks of its operands: a plain square int32 DGLGraph (the accumulating aggregation is exercised on
+    the int32 kernels only), 2-D float32 HIP features with one row per node, gradients enabled, the dispatcher ops (MGX_TORCH_OPS) off,
+    and a bias narrow enough for mgx_column_sum to form its gradient."""
+    return (type(g) is DGLGraph and not g.is_block and h.dim() == 2 and h.dtype == torch.float32 and h.is_cuda
+            and h.device.type in sparse._BACKENDS and torch.is_grad_enabled() and g.idtype == torch.int32
+            and g.number_of_src_nodes() == g.number_of_dst_nodes() and h.shape[0] == g.number_of_src_nodes()
+            and _torch_ops() is None and (bias is None or w_self.shape[0] <= sparse.backend_for(h).COLUMN_SUM_MAX))
 
 
 def _cat_eligible(g, h, cat):

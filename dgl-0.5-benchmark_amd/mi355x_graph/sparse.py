@@ -20,7 +20,7 @@ from . import config
 
 
 # Every tile plan is bounds-checked once when it is built (the kernels follow its tables blindly: a wrong entry would be an
-# out-of-bounds access on the device).  A dozen reductions with host syncs per plan; MGX_TILE_VALIDATE=0 skips them.
+# out-of-bounds access on the device).  A dozen reductions with host syncs per plan; config.TILE_VALIDATE = False skips them.
 PROFILE = None  # set to a list by bench.py to collect per-launch HIP-event timings of mgx_spmm_csr
 
 
