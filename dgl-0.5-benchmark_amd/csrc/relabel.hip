@@ -14,6 +14,10 @@
 //                       width, and the in-CSR row pointer by boundary detection when the edges arrive grouped by destination)
 //   mgx_node_subgraph_* scatter, then a wave per selected row of the parent's in-CSR: count the in-edges whose source is selected too,
 //                       and -- after the caller's cumsum -- write them in CSR order (ballot + prefix popcount, no atomics)
+//   mgx_frontier_exclude_*  the same count / cumsum / fill protocol over a sampled frontier (edges grouped by seed): drop the edges whose
+//                       id is in a short ascending list -- the seed edges of a link-prediction batch and their reverses
+//   mgx_compact_nodes   mark (every id sets its bit) -> rank -> emit -> apply: the distinct ids ascending and each entry's position among
+//                       them, what sort + unique + inverse give (dgl.compact_graphs, g.edge_subgraph, the pair graphs of an edge batch)
 //
 // Every phase is its own launch on the caller's stream: what one phase wrote is read by the next only across a kernel boundary, never
 // through a hand-off between workgroups of one launch.  The scan over the bitmap words is ONE workgroup of 1024 threads striding over
@@ -199,6 +203,84 @@ __global__ __launch_bounds__(kBlock) void subgraph_fill_kernel(const Idx* indptr
   }
 }
 
+// ---- seed-edge exclusion: one wave per seed of a sampled frontier ------------------------------------------------------------
+// x in the ascending list a[0..n)?  At most 64 halvings; the list (the edge ids of one batch and their reverses, a few thousand) stays
+// in cache, where a bitmap over all E edges would have to be cleared for every batch.
+__device__ __forceinline__ bool in_sorted_list(const int64_t* a, int64_t n, int64_t x) {
+  int64_t lo = 0, hi = n;
+  for (int it = 0; it < 64 && lo < hi; ++it) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (a[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return lo < n && a[lo] == x;
+}
+
+template <typename Idx>
+__global__ __launch_bounds__(kBlock) void frontier_exclude_count_kernel(int64_t num_seeds, const int64_t* offsets, const Idx* eid,
+                                                                        int64_t num_excl, const int64_t* excl, int64_t* counts) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t i = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  if (i >= num_seeds) return;
+  const int64_t beg = offsets[i], end = offsets[i + 1];
+  int64_t cnt = 0;
+  for (int64_t c = beg; c < end; c += kWave) {
+    const int64_t p = c + lane;
+    const bool keep = p < end && !in_sorted_list(excl, num_excl, (int64_t)eid[p]);
+    cnt += __popcll(__ballot(keep));
+  }
+  if (lane == 0) counts[i] = cnt;
+}
+
+// the kept edges of seed i, in their order, at [new_offsets[i], new_offsets[i + 1]) -- never past it
+template <typename Idx>
+__global__ __launch_bounds__(kBlock) void frontier_exclude_fill_kernel(int64_t num_seeds, const int64_t* offsets, const Idx* eid,
+                                                                       int64_t num_excl, const int64_t* excl, const Idx* src,
+                                                                       const int64_t* new_offsets, Idx* out_src, Idx* out_eid) {
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t i = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+  if (i >= num_seeds) return;
+  const int64_t beg = offsets[i], end = offsets[i + 1];
+  int64_t o = new_offsets[i];
+  const int64_t stop = new_offsets[i + 1];
+  for (int64_t c = beg; c < end; c += kWave) {
+    const int64_t p = c + lane;
+    Idx id = 0;
+    bool keep = false;
+    if (p < end) {
+      id = eid[p];
+      keep = !in_sorted_list(excl, num_excl, (int64_t)id);
+    }
+    const uint64_t mask = __ballot(keep);
+    const int64_t at = o + __popcll(mask & ((1ull << lane) - 1ull));
+    if (keep && at < stop) {
+      out_src[at] = src[p];
+      out_eid[at] = id;
+    }
+    o += __popcll(mask);
+  }
+}
+
+// ---- compaction: the distinct ids of a list in ascending order, and where each entry of the list went --------------------------
+__global__ __launch_bounds__(kBlock) void compact_mark_kernel(const int64_t* ids, int64_t n, int64_t num_nodes, unsigned long long* bits,
+                                                              int64_t* flags) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const int64_t v = ids[i];
+    if (!in_range(v, num_nodes)) { flag_error(flags, kErrRange); continue; }
+    const unsigned long long m = 1ull << (v & 63);
+    if (!(bits[v >> 6] & m)) atomicOr(&bits[v >> 6], m);  // a stale plain read only costs the atomic it was meant to save
+  }
+}
+
+// lut is read only at marked nodes, and block_emit_kernel has written every one of them
+template <typename Out>
+__global__ __launch_bounds__(kBlock) void compact_apply_kernel(const int64_t* ids, int64_t n, int64_t num_nodes, const int32_t* lut,
+                                                               Out* local) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const int64_t v = ids[i];
+    local[i] = in_range(v, num_nodes) ? (Out)lut[v] : (Out)0;  // out of range: reported by the mark phase
+  }
+}
+
 // workspace of mgx_to_block: lut int32[num_nodes] | bits uint64[words] | word_rank int32[words]
 static inline int64_t bitmap_words(int64_t num_nodes) { return (num_nodes + 63) / 64; }
 static inline int64_t lut_bytes(int64_t num_nodes) { return round_up(num_nodes * 4, 16); }
@@ -336,6 +418,93 @@ extern "C" int32_t mgx_node_subgraph_fill(const mgx_csr* csr, int64_t num_sel, c
     launch_subgraph_fill<int32_t>(csr, num_sel, sel_nodes, (const int32_t*)workspace, offsets, out_bits, l_src, l_dst, parent_eid, s);
   else
     launch_subgraph_fill<int64_t>(csr, num_sel, sel_nodes, (const int32_t*)workspace, offsets, out_bits, l_src, l_dst, parent_eid, s);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+namespace mgx {
+static int32_t check_frontier_args(const char* who, int64_t num_seeds, const int64_t* offsets, const void* eid, int32_t idx_bits,
+                                   int64_t num_excl, const int64_t* excl_sorted) {
+  MGX_CHECK_ARG(num_seeds >= 0 && num_excl >= 0, "%s: negative size", who);
+  MGX_CHECK_ARG(idx_bits == 32 || idx_bits == 64, "%s: idx_bits must be 32 or 64, got %d", who, idx_bits);
+  MGX_CHECK_ARG(num_seeds < (int64_t(1) << 31), "%s: num_seeds must be below 2^31", who);
+  MGX_CHECK_ARG(num_seeds == 0 || (offsets && eid), "%s: NULL pointer (offsets, eid)", who);
+  MGX_CHECK_ARG(num_excl == 0 || excl_sorted, "%s: excl_sorted is NULL", who);
+  return MGX_OK;
+}
+}  // namespace mgx
+
+extern "C" int32_t mgx_frontier_exclude_count(int64_t num_seeds, const int64_t* offsets, const void* eid, int32_t idx_bits,
+                                              int64_t num_excl, const int64_t* excl_sorted, int64_t* counts, void* stream) {
+  using namespace mgx;
+  MGX_ENTER();
+  if (int32_t st = check_frontier_args("mgx_frontier_exclude_count", num_seeds, offsets, eid, idx_bits, num_excl, excl_sorted)) return st;
+  MGX_CHECK_ARG(num_seeds == 0 || counts, "mgx_frontier_exclude_count: counts is NULL");
+  if (num_seeds == 0) return MGX_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (idx_bits == 32)
+    hipLaunchKernelGGL((frontier_exclude_count_kernel<int32_t>), row_wave_grid(num_seeds), dim3(kBlock), 0, s, num_seeds, offsets,
+                       (const int32_t*)eid, num_excl, excl_sorted, counts);
+  else
+    hipLaunchKernelGGL((frontier_exclude_count_kernel<int64_t>), row_wave_grid(num_seeds), dim3(kBlock), 0, s, num_seeds, offsets,
+                       (const int64_t*)eid, num_excl, excl_sorted, counts);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int32_t mgx_frontier_exclude_fill(int64_t num_seeds, const int64_t* offsets, const void* eid, int32_t idx_bits,
+                                             int64_t num_excl, const int64_t* excl_sorted, const void* src, const int64_t* new_offsets,
+                                             void* out_src, void* out_eid, void* stream) {
+  using namespace mgx;
+  MGX_ENTER();
+  if (int32_t st = check_frontier_args("mgx_frontier_exclude_fill", num_seeds, offsets, eid, idx_bits, num_excl, excl_sorted)) return st;
+  MGX_CHECK_ARG(num_seeds == 0 || (src && new_offsets && out_src && out_eid),
+                "mgx_frontier_exclude_fill: NULL pointer (src, new_offsets, out_src, out_eid)");
+  if (num_seeds == 0) return MGX_OK;
+  hipStream_t s = (hipStream_t)stream;
+  if (idx_bits == 32)
+    hipLaunchKernelGGL((frontier_exclude_fill_kernel<int32_t>), row_wave_grid(num_seeds), dim3(kBlock), 0, s, num_seeds, offsets,
+                       (const int32_t*)eid, num_excl, excl_sorted, (const int32_t*)src, new_offsets, (int32_t*)out_src,
+                       (int32_t*)out_eid);
+  else
+    hipLaunchKernelGGL((frontier_exclude_fill_kernel<int64_t>), row_wave_grid(num_seeds), dim3(kBlock), 0, s, num_seeds, offsets,
+                       (const int64_t*)eid, num_excl, excl_sorted, (const int64_t*)src, new_offsets, (int64_t*)out_src,
+                       (int64_t*)out_eid);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int64_t mgx_compact_nodes_workspace(int64_t num_nodes, int64_t n) { return mgx_to_block_workspace(num_nodes, n); }
+
+extern "C" int32_t mgx_compact_nodes(int64_t num_nodes, int64_t n, const int64_t* ids, int32_t out_bits, void* workspace, int64_t* nodes,
+                                     void* local, int64_t* result, void* stream) {
+  using namespace mgx;
+  MGX_ENTER();
+  MGX_CHECK_ARG(num_nodes >= 0 && n >= 0, "mgx_compact_nodes: negative size");
+  MGX_CHECK_ARG(out_bits == 32 || out_bits == 64, "mgx_compact_nodes: out_bits must be 32 or 64, got %d", out_bits);
+  MGX_CHECK_ARG(n < (int64_t(1) << 31), "mgx_compact_nodes: n must be below 2^31");
+  MGX_CHECK_ARG(result != nullptr, "mgx_compact_nodes: result is NULL");
+  MGX_CHECK_ARG(num_nodes == 0 || workspace, "mgx_compact_nodes: workspace is NULL");
+  MGX_CHECK_ARG(n == 0 || (ids && local), "mgx_compact_nodes: NULL pointer (ids, local)");
+  MGX_CHECK_ARG(n == 0 || num_nodes == 0 || nodes, "mgx_compact_nodes: nodes is NULL");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t words = bitmap_words(num_nodes);
+  int32_t* lut = (int32_t*)workspace;
+  unsigned long long* bits = (unsigned long long*)((char*)workspace + lut_bytes(num_nodes));
+  int32_t* word_rank = (int32_t*)((char*)bits + words * 8);
+  int64_t* flags = result + 1;
+  MGX_CHECK_HIP(hipMemsetAsync(result, 0, 2 * sizeof(int64_t), s));
+  if (n == 0) return MGX_OK;
+  if (words > 0) MGX_CHECK_HIP(hipMemsetAsync(bits, 0, (size_t)words * 8, s));
+  hipLaunchKernelGGL(compact_mark_kernel, stride_grid(n), dim3(kBlock), 0, s, ids, n, num_nodes, bits, flags);
+  hipLaunchKernelGGL(block_rank_kernel, dim3(1), dim3(kRankBlock), 0, s, bits, words, word_rank, (int64_t)0, result);
+  if (words > 0)
+    hipLaunchKernelGGL(block_emit_kernel, stride_grid(words), dim3(kBlock), 0, s, bits, words, word_rank, (int64_t)0,
+                       n < num_nodes ? n : num_nodes, lut, nodes);
+  if (out_bits == 32)
+    hipLaunchKernelGGL((compact_apply_kernel<int32_t>), stride_grid(n), dim3(kBlock), 0, s, ids, n, num_nodes, lut, (int32_t*)local);
+  else
+    hipLaunchKernelGGL((compact_apply_kernel<int64_t>), stride_grid(n), dim3(kBlock), 0, s, ids, n, num_nodes, lut, (int64_t*)local);
   MGX_CHECK_LAUNCH();
   return MGX_OK;
 }

@@ -17,17 +17,11 @@
 //                                   a running sum in row order, fp32 inside a chunk of 64 and fp64 across chunks
 // Every random number is a function of (rng_seed, seed slot, draw or CSR position), never of the launch geometry.
 #include "common.h"
+#include "counter_rng.h"  // mix64
 
 namespace mgx {
 
 constexpr int kMaxFanout = 64;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
 template <typename Idx>
 __global__ __launch_bounds__(kBlock) void sample_neighbors_kernel(const Idx* indptr, const Idx* indices, const Idx* eids,

@@ -11,6 +11,7 @@ from mi355x_graph.readout import (readout_nodes, sum_nodes, mean_nodes, max_node
                                   readout_edges, sum_edges, mean_edges, max_edges, softmax_edges, broadcast_edges)
 from . import nn, data, dataloading, utils, sampling, transform, backend  # noqa: F401
 from mi355x_graph.sampling import to_block, in_subgraph, NID, EID  # noqa: F401
+from mi355x_graph.linkpred import compact_graphs  # noqa: F401
 from mi355x_graph.ops import edge_softmax  # noqa: F401
 
 __version__ = "0.6.1+mi355x"

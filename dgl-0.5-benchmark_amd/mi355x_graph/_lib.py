@@ -140,6 +140,12 @@ SIGNATURES = {
     "mgx_node_subgraph_workspace": (_i64, [_i64]),
     "mgx_node_subgraph_count": (_i32, [_csr_p, _i64, _vp, _vp, _vp, _vp, _vp]),
     "mgx_node_subgraph_fill": (_i32, [_csr_p, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "mgx_edge_lookup": (_i32, [_csr_p, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mgx_negative_sample": (_i32, [_csr_p, _i32, _i64, _vp, _i32, _i64, _i32, _i32, ctypes.c_uint64, _vp, _vp, _vp]),
+    "mgx_frontier_exclude_count": (_i32, [_i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp]),
+    "mgx_frontier_exclude_fill": (_i32, [_i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mgx_compact_nodes_workspace": (_i64, [_i64, _i64]),
+    "mgx_compact_nodes": (_i32, [_i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "mgx_gather_rows": (_i32, [_i64, _vp, _i32, _i64, _fp, _fp, _vp]),
     "mgx_gather_rows_strided": (_i32, [_i64, _vp, _i32, _i64, _fp, _i64, _fp, _i64, _vp]),
     "mgx_scatter_add_rows": (_i32, [_i64, _vp, _i32, _i64, _fp, _fp, _vp]),

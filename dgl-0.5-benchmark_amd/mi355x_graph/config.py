@@ -44,6 +44,10 @@ SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: seg
 DEVICE_BLOCKS = True    # the relabelling kernels of csrc/relabel.hip; False: look-up table -> unique -> gathers -> bincount + cumsum in torch ops
 DEVICE_SUBGRAPH = True  # a wave per selected row of a materialised in-CSR (csrc/relabel.hip); False: the look-up table gathered at both ends of every parent edge
 
+# ---- link-prediction minibatches (linkpred.py, sampling.exclude_frontier_edges, DGLGraph.has_edges_between)
+DEVICE_LINKPRED = True  # edge lookup, negative sampling (csrc/edgefind.hip), seed-edge exclusion and compaction (csrc/relabel.hip); False: the
+                        # torch compositions of the same semantics -- the same result bit for bit, the negatives' random stream included
+
 # ---- schedules (schedule.py, tileplan.py)
 PLAN_BUILDER = "device"    # "device" (mgx_spmm_plan_count / _fill) | "torch" | "host": the same tables three ways (tests compare them)
 HUB_SPLIT = 256            # rows longer than this become several work items (256 measured best on MI355X; 1024: +5..10 %)

@@ -27,6 +27,7 @@ SHAPES = {
     "reddit-small": dict(n=232965, m=5803459, symmetric=True, feat=602, classes=41, max_deg=21657, seed=3),
     "products": dict(n=2449029, m=61859140, symmetric=True, feat=100, classes=47, max_deg=17481, seed=4),
     "proteins": dict(n=132534, m=39561252, symmetric=True, feat=8, classes=112, max_deg=7750, seed=8),
+    "citation": dict(n=2927963, m=30561187, symmetric=False, feat=128, classes=2, max_deg=10000, seed=9),  # ogbl-citation: directed citations
 }
 
 

@@ -491,7 +491,17 @@ class DGLGraph(object):
         return src[e], dst[e]
 
     def has_edges_between(self, u, v):
+        """Bool tensor: is there an edge u[i] -> v[i].  On a device graph with config.DEVICE_LINKPRED the row of v[i] in the in-CSR is
+        scanned (mgx_edge_lookup); the composition below sorts one key per edge of the graph on every call."""
+        from . import config
+        if self.device.type == "cuda" and config.DEVICE_LINKPRED:
+            from .linkpred import edge_lookup
+            return edge_lookup(self, u, v, "has_edges_between") >= 0
         src, dst = self._index.coo()
+        for ids, n in ((u, self._index.num_src), (v, self._index.num_dst)):
+            ids = torch.as_tensor(ids, device=src.device).long()
+            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= n):
+                raise DGLError("has_edges_between: a node id is out of range")
         n = max(self._index.num_dst, 1)
         key = torch.sort(src.long() * n + dst.long())[0]
         q = torch.as_tensor(u, device=src.device).long() * n + torch.as_tensor(v, device=src.device).long()
@@ -501,6 +511,14 @@ class DGLGraph(object):
     def subgraph(self, nodes, **kwargs):
         from .sampling import node_subgraph
         return node_subgraph(self, nodes)
+
+    def edge_ids(self, u, v, return_uv=False, etype=None):
+        from .linkpred import edge_ids
+        return edge_ids(self, u, v, return_uv=return_uv)
+
+    def edge_subgraph(self, edges, preserve_nodes=False, **kwargs):
+        from .linkpred import edge_subgraph
+        return edge_subgraph(self, edges, preserve_nodes=preserve_nodes)
 
     def add_self_loop(self, etype=None):
         from .transform import add_self_loop

@@ -149,8 +149,9 @@ def _view(idx, edge_dir, what):
     return idx.csc() if edge_dir == "in" else idx.csr()
 
 
-def _sample_modes(g, idx, nodes, fanout, edge_dir, prob, replace, generator):
-    """Every mode but the uniform in-edge one without replacement: prob=, replace=True, edge_dir='out'."""
+def _sample_modes(g, idx, nodes, fanout, edge_dir, prob, replace, generator, want_counts=False):
+    """Every mode but the uniform in-edge one without replacement: prob=, replace=True, edge_dir='out'.  Returns (src, dst, eid) and the
+    edges per seed (None unless `want_counts`)."""
     view = _view(idx, edge_dir, "sample_neighbors")
     dev = view.device
     nodes = torch.as_tensor(nodes, device=dev).long()
@@ -164,9 +165,9 @@ def _sample_modes(g, idx, nodes, fanout, edge_dir, prob, replace, generator):
         else:
             picked, eid, counts = backend.sample_neighbors_modes(view, seeds, fanout, w, replace, _rng_seed(generator))
         seeds = torch.repeat_interleave(nodes, counts, output_size=picked.shape[0])
-        return (picked.long(), seeds, eid.long()) if edge_dir == "in" else (seeds, picked.long(), eid.long())
+        return ((picked.long(), seeds, eid.long()) if edge_dir == "in" else (seeds, picked.long(), eid.long())), counts
     pos, seg = _sample_torch(view, nodes, fanout, w, replace, generator)
-    return _triple(view, nodes, pos, seg, edge_dir)
+    return _triple(view, nodes, pos, seg, edge_dir), (torch.bincount(seg, minlength=nodes.shape[0]) if want_counts else None)
 
 
 def select_topk(g, k, weight, nodes=None, edge_dir="in", ascending=False):
@@ -200,9 +201,15 @@ def in_subgraph(g, nodes):
 def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, generator=None):
     """Returns (src, dst, eid) of the sampled in-edges (edge_dir="out": out-edges) of `nodes` in GLOBAL ids.
     prob: the name of an edge feature or one non-negative weight per edge id; replace: draw with replacement."""
+    return _sample_frontier(g, nodes, fanout, edge_dir, prob, replace, generator)[0]
+
+
+def _sample_frontier(g, nodes, fanout, edge_dir="in", prob=None, replace=False, generator=None, want_counts=False):
+    """sample_neighbors, and with it the edges per seed (int64 [len(nodes)]; None unless `want_counts`): the frontier as the rows of a
+    CSR over the seeds, which is what the seed-edge exclusion of a link-prediction batch walks."""
     idx = g._index if isinstance(g, DGLGraph) else g
     if edge_dir != "in" or prob is not None or replace:
-        return _sample_modes(g, idx, nodes, fanout, edge_dir, prob, replace, generator)
+        return _sample_modes(g, idx, nodes, fanout, edge_dir, prob, replace, generator, want_counts)
     csc = idx.csc()
     dev = csc.device
     nodes = torch.as_tensor(nodes, device=dev).long()
@@ -214,14 +221,14 @@ def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, 
             else int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item())
         src, eid, counts = sparse.backend_for(csc.indptr).sample_neighbors(csc, nodes.to(csc.indptr.dtype), fanout, rng_seed)
         dst = torch.repeat_interleave(nodes, counts)
-        return src.long(), dst, eid.long()
+        return (src.long(), dst, eid.long()), counts
     indptr = csc.indptr.long()
     beg = indptr[nodes]
     deg = indptr[nodes + 1] - beg
     total = int(deg.sum().item())
     if total == 0:
         z = torch.zeros(0, dtype=torch.int64, device=dev)
-        return z, z, z
+        return (z, z, z), deg
     seg = torch.repeat_interleave(torch.arange(nodes.shape[0], device=dev), deg)
     first = torch.cumsum(deg, 0) - deg
     pos = torch.arange(total, device=dev) - first[seg] + beg[seg]  # CSR positions of every candidate edge
@@ -235,7 +242,26 @@ def sample_neighbors(g, nodes, fanout, edge_dir="in", prob=None, replace=False, 
     src = csc.indices[pos].long()
     dst = nodes[seg]
     eid = pos if csc.eids is None else csc.eids[pos].long()
-    return src, dst, eid
+    return (src, dst, eid), (torch.bincount(seg, minlength=nodes.shape[0]) if want_counts else None)
+
+
+def exclude_frontier_edges(frontier, counts, seeds, excl):
+    """(src, dst, eid) of a frontier -- edges grouped by seed, counts[i] of them for seeds[i] -- without the edges whose id is in
+    `excl` (int64 on the frontier's device, ASCENDING).  DGL's semantics: sample first, then remove (a seed may end with fewer than `fanout` edges).  Kept edges keep their
+    order, so the result is again grouped by seed in seed order.  On the device with config.DEVICE_LINKPRED the count / cumsum / fill
+    kernels of csrc/relabel.hip (a bisection per edge in the sorted list), else the same in torch ops."""
+    src, dst, eid = frontier
+    if src.is_cuda and config.DEVICE_LINKPRED:
+        from . import sparse
+        backend = sparse.backend_for(src)
+        offsets = backend._sample_offsets(counts.long())
+        src, eid, kept = backend.frontier_exclude(offsets, src.contiguous(), eid.contiguous(), excl.contiguous())
+        return src, torch.repeat_interleave(seeds, kept, output_size=src.shape[0]), eid
+    if excl.numel() == 0 or eid.numel() == 0:
+        return src, dst, eid
+    pos = torch.searchsorted(excl, eid).clamp(max=excl.shape[0] - 1)
+    keep = excl[pos] != eid
+    return src[keep], dst[keep], eid[keep]
 
 
 def to_block(g_or_edges, dst_nodes, num_nodes=None, idtype=torch.int64, dst_sorted=False, max_in_degree=None):
@@ -295,13 +321,21 @@ class MultiLayerNeighborSampler(object):
         self.fanouts = list(fanouts)
         self.replace, self.prob = bool(replace), prob
 
-    def sample_blocks(self, g, seed_nodes, generator=None):
+    def sample_blocks(self, g, seed_nodes, exclude_eids=None, generator=None):
+        """exclude_eids: edge ids taken out of every layer's frontier before the block is built (the seed edges of a link-prediction
+        batch and their reverses: sampling them back in would leak the label)."""
         blocks = []
         seeds = torch.as_tensor(seed_nodes, device=g.device).long()
         n = g.number_of_nodes()
+        if exclude_eids is not None:
+            exclude_eids = torch.sort(torch.as_tensor(exclude_eids, device=g.device).long().reshape(-1))[0]
         for fanout in reversed(self.fanouts):
-            frontier = sample_neighbors(g, seeds, fanout, prob=self.prob, replace=self.replace, generator=generator)
-            # sample_neighbors returns edges grouped by seed in seed order (CSR positions sorted inside a seed)
+            frontier, counts = _sample_frontier(g, seeds, fanout, prob=self.prob, replace=self.replace, generator=generator,
+                                                want_counts=exclude_eids is not None)
+            # sample_neighbors returns edges grouped by seed in seed order (CSR positions sorted inside a seed); dropping edges keeps
+            # that, so the dst-sorted in-CSR below comes from the counts after the exclusion
+            if exclude_eids is not None:
+                frontier = exclude_frontier_edges(frontier, counts, seeds, exclude_eids)
             block = to_block(frontier, seeds, num_nodes=n, idtype=g.idtype, dst_sorted=True,
                              max_in_degree=fanout if (fanout is not None and fanout >= 0) else None)
             seeds = block.srcdata[NID]

@@ -1609,6 +1609,74 @@ class HipBackend(object):
                                                     _ptr(parent_eid), _stream(dev)))
         return l_src, l_dst, parent_eid, offsets, not (err & 16)
 
+    # ---- link-prediction minibatches (csrc/edgefind.hip, csrc/relabel.hip)
+    def edge_lookup(self, csr, row_ids, col_ids):
+        """row_ids, col_ids: contiguous int64 on the CSR's device.  Returns (eid int64 [n], error bits): the lowest edge id of every
+        (row, col) pair, -1 without an edge.  The caller reads the bits (4: an id out of range) with whatever else it reads."""
+        dev = self._check_dev(csr.indptr, row_ids, col_ids)
+        n = int(row_ids.shape[0])
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+        result = torch.empty(1, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mgx_edge_lookup(ctypes.byref(csr.c_struct()), n, _ptr(row_ids), _ptr(col_ids), _ptr(out), _ptr(result),
+                                                  _stream(dev)))
+        return out, result
+
+    def negative_sample(self, csr, rows_are_sources, pos_src, k, num_dst_nodes, flags, max_tries, rng_seed):
+        """pos_src: contiguous int64 on the device; csr: the CSR of the existence checks, None exactly when flags has no bit 1.
+        Returns (dst int64 [n * k], -1 where every try was rejected; result int64 [2] = {failed draws, error bits})."""
+        dev = self._check_dev(pos_src, None if csr is None else csr.indptr)
+        n = int(pos_src.shape[0])
+        out = torch.empty(n * int(k), dtype=torch.int64, device=dev)
+        result = torch.empty(2, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mgx_negative_sample(None if csr is None else ctypes.byref(csr.c_struct()), 1 if rows_are_sources else 0, n,
+                                                      _ptr(pos_src), int(k), int(num_dst_nodes), int(flags), int(max_tries),
+                                                      ctypes.c_uint64(rng_seed & (2 ** 64 - 1)), _ptr(out), _ptr(result), _stream(dev)))
+        return out, result
+
+    def frontier_exclude(self, offsets, src, eid, excl_sorted):
+        """A frontier (offsets int64 [n + 1]; src, eid of one integer type, grouped by seed) without the edges whose id is in the
+        ascending int64 list `excl_sorted`.  Returns (src, eid, counts int64 [n]); one host read: the new size."""
+        dev = self._check_dev(offsets, src, eid, excl_sorted)
+        L = _lib.lib()
+        n = int(offsets.shape[0]) - 1
+        bits = 32 if eid.dtype == torch.int32 else 64
+        counts = torch.empty(n, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(L.mgx_frontier_exclude_count(n, _ptr(offsets), _ptr(eid), bits, int(excl_sorted.shape[0]), _ptr(excl_sorted),
+                                                    _ptr(counts), _stream(dev)))
+        new_offsets = self._sample_offsets(counts)
+        total = int(new_offsets[-1].item())
+        out_src = torch.empty(total, dtype=src.dtype, device=dev)
+        out_eid = torch.empty(total, dtype=eid.dtype, device=dev)
+        if total:
+            with torch.cuda.device(dev):
+                _lib.check(L.mgx_frontier_exclude_fill(n, _ptr(offsets), _ptr(eid), bits, int(excl_sorted.shape[0]), _ptr(excl_sorted),
+                                                       _ptr(src), _ptr(new_offsets), _ptr(out_src), _ptr(out_eid), _stream(dev)))
+        return out_src, out_eid, counts
+
+    def compact_nodes(self, num_nodes, ids, idtype):
+        """ids: contiguous int64 on the device.  Returns (nodes int64: the distinct ids ascending, local in `idtype`: the position of
+        every entry of `ids` among them).  One host read: the number of distinct ids and the error bits."""
+        dev = self._check_dev(ids)
+        L = _lib.lib()
+        n = int(ids.shape[0])
+        nodes = torch.empty(min(n, num_nodes), dtype=torch.int64, device=dev)
+        local = torch.empty(n, dtype=idtype, device=dev)
+        with torch.cuda.device(dev):
+            ws_bytes = L.mgx_compact_nodes_workspace(num_nodes, n)
+            if ws_bytes < 0:
+                raise DGLError("compact_nodes: negative num_nodes")
+            ws = torch.empty(ws_bytes // 8 + 2, dtype=torch.int64, device=dev)  # the last two words: {count, error bits}
+            result = ws[-2:]
+            _lib.check(L.mgx_compact_nodes(num_nodes, n, _ptr(ids), 32 if idtype == torch.int32 else 64, _ptr(ws), _ptr(nodes), _ptr(local),
+                                           _ptr(result), _stream(dev)))
+        count, err = result.tolist()
+        if err & 4:
+            raise DGLError("compact_nodes: a node id is outside [0, %d)" % num_nodes)
+        return nodes[:count], local
+
     # ---- halo rows as bitmaps + packed values (csrc/rowpack.hip; dist.SparseHalo)
     ROWPACK_MAX_D = 256
 

@@ -837,6 +837,55 @@ int32_t mgx_node_subgraph_count(const mgx_csr* csr, int64_t num_sel, const int64
 int32_t mgx_node_subgraph_fill(const mgx_csr* csr, int64_t num_sel, const int64_t* sel_nodes, const void* workspace,
                                const int64_t* offsets, int32_t out_bits, void* l_src, void* l_dst, int64_t* parent_eid, void* stream);
 
+/* ------------------------------------------------------------------ link-prediction minibatches (csrc/edgefind.hip, csrc/relabel.hip)
+ * What turns a batch of EDGES into a training step (dgl.dataloading.EdgeDataLoader, dgl.dataloading.negative_sampler,
+ * end_to_end/sampling/link-prediction/): which edge joins a pair of nodes, k negative destinations per positive edge, the batch's own
+ * edges (and their reverses) taken out of the sampled neighbourhoods, and the compaction of the batch's endpoints.  Integer kernels;
+ * every id read from a caller's array is checked before it indexes anything.  Purely additive: mgx_abi_version() stays 35.
+ *
+ * mgx_edge_lookup: `csr` is the in-CSR (rows = destinations, indices = sources) or the out-CSR, the caller passing row_ids / col_ids
+ *   (int64, [num_q]) in the matching order.  out_eid[q] = the LOWEST edge id among the positions p of row row_ids[q] with
+ *   indices[p] == col_ids[q] -- eids[p], or p when csr->eids is NULL -- and -1 when there is none.  A minimum over all matches: nothing
+ *   is assumed about the order inside a row (rows are in edge-id order, not column order, so a lookup is a scan of one row: 16 lanes
+ *   per query, coalesced loads, a shuffle reduction, no atomics -- deterministic).  result: device int64[1] of error bits; 4 = a row id
+ *   outside [0, num_rows) or a column id outside [0, num_cols): that query gets -1.  num_q < 2^34. */
+int32_t mgx_edge_lookup(const mgx_csr* csr, int64_t num_q, const int64_t* row_ids, const int64_t* col_ids,
+                        int64_t* out_eid /* [num_q] */, int64_t* result /* [1] error bits */, void* stream);
+/* mgx_negative_sample: draw (e, j), e < num_pos, j < k, belongs to positive edge e with source u = pos_src[e] and proposes a
+ *   destination uniform on [0, num_dst_nodes), num_dst_nodes < 2^31.  flags: bit 1 (exclude_existing) rejects v' when (u, v') is an edge
+ *   of the graph, bit 2 (exclude_self_loops) rejects v' == u.  Try t of the draw uses
+ *       r = mix64(rng_seed ^ mix64((e * k + j) * 64 + t)),   v' = ((r >> 32) * num_dst_nodes) >> 32
+ *   (mix64: the splitmix64 finaliser; csrc/counter_rng.h), a function of (rng_seed, e, j, t) alone -- never of the launch geometry, the
+ *   index width or the form of the CSR.  out_dst[e * k + j] = the first accepted of at most max_tries tries, -1 when all were rejected;
+ *   max_tries in [1, 64]: there is no unbounded rejection loop, a source adjacent to every node fails its draws and ends.
+ *   csr: NULL exactly when exclude_existing is off.  rows_are_sources != 0: the out-CSR, all k * max_tries checks of one positive edge
+ *   scan the row of u; else the in-CSR, scanned at row v'.  Both give the same output.
+ *   result: device int64[2] = {failed draws, error bits}; 4 = a source outside the graph (its slots get -1 and are not counted). */
+int32_t mgx_negative_sample(const mgx_csr* csr /* NULL iff no exclude_existing */, int32_t rows_are_sources, int64_t num_pos,
+                            const int64_t* pos_src, int32_t k, int64_t num_dst_nodes, int32_t flags, int32_t max_tries, uint64_t rng_seed,
+                            int64_t* out_dst /* [num_pos * k] */, int64_t* result /* [2] */, void* stream);
+/* Seed-edge exclusion.  A frontier is what the samplers return: edges grouped by seed, seed s owning [offsets[s], offsets[s + 1])
+ * ([num_seeds + 1] int64) of `src` / `eid` (idx_bits wide).  An edge is dropped when its edge id occurs in excl_sorted[num_excl]
+ * (int64, ASCENDING; a few thousand ids, searched by bisection -- no bitmap over all edges to clear per batch).  DGL's semantics:
+ * sample first, then remove, so a seed may end with fewer than `fanout` edges.
+ *   _count  counts[s] (int64) = the kept edges of seed s.  The caller takes new_offsets = exclusive cumsum ([num_seeds + 1]), reads
+ *           new_offsets[num_seeds] once, allocates out_src / out_eid (idx_bits wide) and calls
+ *   _fill   with the same arguments: the kept edges of seed s in their order at [new_offsets[s], new_offsets[s + 1]), never past it.
+ * Ballot + prefix popcount inside a seed, no atomics: deterministic. */
+int32_t mgx_frontier_exclude_count(int64_t num_seeds, const int64_t* offsets, const void* eid, int32_t idx_bits, int64_t num_excl,
+                                   const int64_t* excl_sorted, int64_t* counts /* [num_seeds] */, void* stream);
+int32_t mgx_frontier_exclude_fill(int64_t num_seeds, const int64_t* offsets, const void* eid, int32_t idx_bits, int64_t num_excl,
+                                  const int64_t* excl_sorted, const void* src, const int64_t* new_offsets, void* out_src, void* out_eid,
+                                  void* stream);
+/* mgx_compact_nodes: ids[n] (int64, values in [0, num_nodes), repeats allowed, n < 2^31) -> nodes = the distinct ids in ASCENDING order
+ *   (int64, capacity min(n, num_nodes)) and local[i] = the position of ids[i] in nodes (out_bits wide): what sort + unique + inverse
+ *   give, from the node bitmap of mgx_to_block walked word by word -- no sort.  result: device int64[2] = {number of distinct ids,
+ *   error bits}; 4 = an id out of range (skipped; its local entry is 0).  workspace: mgx_compact_nodes_workspace(num_nodes, n) bytes
+ *   (-1: bad arguments). */
+int64_t mgx_compact_nodes_workspace(int64_t num_nodes, int64_t n);
+int32_t mgx_compact_nodes(int64_t num_nodes, int64_t n, const int64_t* ids, int32_t out_bits, void* workspace,
+                          int64_t* nodes /* capacity min(n, num_nodes) */, void* local /* [n] */, int64_t* result /* [2] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
