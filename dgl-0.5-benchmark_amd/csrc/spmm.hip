@@ -1396,6 +1396,51 @@ extern "C" int32_t mgx_spmm_copy_u_slots(const mgx_csr* csr, const mgx_spmm_plan
                             out_stride, slots);
 }
 
+extern "C" int32_t mgx_rows_slots_pack_rows(int64_t n, int64_t D, const float* x, int64_t x_stride, const int64_t* rows, int64_t num_listed,
+                                            void* slots, void* stream) {
+  using namespace mgx;
+  MGX_ENTER();
+  MGX_CHECK_ARG(n >= 0 && num_listed >= 0 && x_stride >= D, "mgx_rows_slots_pack_rows: negative size or stride below D");
+  if (D != 64 || x_stride % 4 != 0 || (uintptr_t)x % 16 != 0 || (uintptr_t)slots % 16 != 0)
+    MGX_UNSUPPORTED("mgx_rows_slots_pack_rows: rows of exactly 64 columns, stride a multiple of 4, 16-byte aligned pointers");
+  if (n == 0 || num_listed == 0) return MGX_OK;
+  MGX_CHECK_ARG(x && slots && rows, "mgx_rows_slots_pack_rows: NULL pointer");
+  int64_t blocks = (num_listed + 4 * kWavesPerBlock - 1) / (4 * kWavesPerBlock);
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(rows_slots_pack_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, n, num_listed, rows, x, x_stride,
+                     (uint32_t*)slots);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}
+
+extern "C" int32_t mgx_spmm_copy_u_slots_init(const mgx_csr* csr, const mgx_spmm_plan* plan, int32_t reduce, const float* ufeat, int64_t D,
+                                              int64_t u_stride, const void* slots, const float* dst_scale, const float* init, int64_t init_rows,
+                                              int64_t init_stride, const int64_t* init_pos, float* out, int64_t out_stride, float* partial_ws,
+                                              int32_t flags, void* stream) {
+  using namespace mgx;
+  MGX_ENTER();
+  MGX_CHECK_ARG(csr != nullptr, "mgx_spmm_copy_u_slots_init: csr is NULL");
+  MGX_CHECK_ARG(csr->num_rows >= 0 && csr->nnz >= 0, "mgx_spmm_copy_u_slots_init: negative sizes");
+  MGX_CHECK_ARG(csr->num_rows == 0 || csr->indptr != nullptr, "mgx_spmm_copy_u_slots_init: indptr is NULL");
+  MGX_CHECK_ARG(csr->nnz == 0 || csr->indices != nullptr, "mgx_spmm_copy_u_slots_init: indices is NULL");
+  MGX_CHECK_ARG(reduce == MGX_REDUCE_SUM || reduce == MGX_REDUCE_MEAN, "mgx_spmm_copy_u_slots_init: SUM or MEAN only, got %d", reduce);
+  MGX_CHECK_ARG(D >= 0 && u_stride >= D && out_stride >= D && init_stride >= D && init_rows >= 0,
+                "mgx_spmm_copy_u_slots_init: strides must be >= D, init_rows >= 0");
+  MGX_CHECK_ARG((ufeat != nullptr && slots != nullptr) || csr->num_cols == 0, "mgx_spmm_copy_u_slots_init: ufeat / slots is NULL");
+  MGX_CHECK_ARG(out != nullptr || csr->num_rows == 0, "mgx_spmm_copy_u_slots_init: out is NULL");
+  MGX_CHECK_ARG(init_pos != nullptr || csr->num_rows == 0, "mgx_spmm_copy_u_slots_init: init_pos is NULL");
+  MGX_CHECK_ARG(init != nullptr || init_rows == 0, "mgx_spmm_copy_u_slots_init: init is NULL");
+  if (csr->idx_bits != 32 || reduce != MGX_REDUCE_SUM || dst_scale != nullptr || D != 64 || u_stride % 4 != 0 || out_stride % 4 != 0 ||
+      init_stride % 4 != 0 || (uintptr_t)ufeat % 16 != 0 || (uintptr_t)out % 16 != 0 || (uintptr_t)init % 16 != 0 || (uintptr_t)slots % 16 != 0 ||
+      csr->num_cols * (int64_t)128 >= (int64_t(1) << 32) || csr->num_cols * u_stride * 4 >= (int64_t(1) << 32) ||
+      init_rows * init_stride * 4 >= (int64_t(1) << 32))
+    MGX_UNSUPPORTED("mgx_spmm_copy_u_slots_init: plain sums (no mean, no dst_scale) on int32 graphs, 64 columns, the three strides multiples "
+                    "of 4, 16-byte aligned operands, gathered, slot and initial matrix under 4 GiB");
+  return spmm_impl<int32_t>(csr, plan, partial_ws, MGX_SPMM_ACCUMULATE | (flags & MGX_SPMM_SHORT_ROWS), MGX_OP_COPY_LHS, reduce, ufeat, nullptr,
+                            D, 0, D, nullptr, nullptr, nullptr, nullptr, out, nullptr, nullptr, (hipStream_t)stream, nullptr, u_stride, out_stride,
+                            slots, nullptr, init, init_pos, init_stride);
+}
+
 extern "C" int32_t mgx_spmm_csr(const mgx_csr* csr, const mgx_spmm_plan* plan, int32_t op, int32_t reduce,
                                 const float* ufeat, const float* efeat, int64_t u_len, int64_t e_len,
                                 int64_t out_len, const int64_t* u_off, const int64_t* e_off, const float* src_scale,

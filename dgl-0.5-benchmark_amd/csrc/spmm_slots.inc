@@ -159,6 +159,155 @@ __global__ __launch_bounds__(kBlock) void spmm_slots_kernel(const SpmmFastArgs<i
   }
 }
 
+// mgx_spmm_copy_u_slots_init: the INIT launch of spmm_rowwave32_kernel<4, 16, ...> (plain copy_u sum whose initial value comes from a compact
+// matrix, `out` write-only) over slots -- for a gathered matrix most of whose ROWS are zero (d neigh / deg of a loss taken on 8 % of the
+// nodes): an empty slot is one line per edge instead of the dense row's two and adds nothing.
+//
+// The sum has the dense INIT launch's bits, which fixes the order of additions: that kernel keeps four accumulators, edge e of an item
+// (counted from the item's first edge) is added to accumulator e % 4 in increasing e, accumulator 0 starts from the initial value, and
+// the result is (A0 + A1) + (A2 + A3).  Here the four accumulators are four LDS rows of the wave.  Lane group g of a step holds edge
+// k + 8 u + g (k a multiple of 16), so groups g and g + 4 feed accumulator g & 3: the lower half of the wave adds first, then the upper
+// half (a wave's LDS operations execute in order), u ascending.  An empty slot adds nothing -- eight empty slots skip the whole path,
+// tested wave-uniformly --; a slot with values adds them at their columns by read - add - write; a flagged slot (more than 24
+// non-zeros) adds the dense row.  A skipped addend is an exact +0.0f, so the result is the dense launch's bit for bit wherever no
+// element of the operands is -0.0f, and equal as a number otherwise (only the sign of an exactly-zero result can differ).
+//
+// Schedule: spmm_slots_kernel's (two steps of 16 slots in ping-pong); the dense rows of a step's flagged slots are read where they are
+// added, both halves' at once.  (Requesting them one step ahead -- a third stage, 108 - 138 VGPRs at U = 2, 70 at U = 1 -- was
+// measured on the products graph with 8 % dense rows and lost to this form and to the dense launch: docs/LOG_head_slots.md.)
+template <int U>
+__global__ __launch_bounds__(kBlock) void spmm_slots_init_kernel(const SpmmFastArgs<int32_t> a, const char* __restrict__ slots) {
+  __shared__ __attribute__((aligned(16))) float acc_all[kWavesPerBlock][4][kSlotAccStride];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int grp = lane >> 3, gi = lane & 7;
+  float* accw = &acc_all[wave][0][0];
+  float* accg = accw + (grp & 3) * kSlotAccStride;
+  for (int i = lane; i < 4 * kSlotAccStride; i += kWave) accw[i] = 0.f;
+  int64_t item_base, item_stop;
+  xcd_stretch(a.xcd, item_base, item_stop);
+  item_base += (int64_t)(blockIdx.x / kXcds) * a.rpb;
+  int r = wave;
+  if (r >= a.rpb || item_base + r >= item_stop) return;
+  const uint32_t laneoff = (uint32_t)gi * 16u;
+  const char* __restrict__ srcb = reinterpret_cast<const char*>(a.src);
+  const uint32_t rowbytes = (uint32_t)a.lds * 4u;
+
+  auto load_meta = [&](int64_t item, int64_t& row, int32_t& beg, int32_t& end, int32_t& ipos) {
+    if (a.item_row) {
+      row = (int64_t)a.item_row[item];
+      beg = a.item_beg[item];
+      end = a.item_end[item];
+    } else {
+      row = item;
+      beg = a.indptr[item];
+      end = a.indptr[item + 1];
+    }
+    ipos = row >= 0 ? (int32_t)a.init_pos[row] : -1;  // (a chunk of a split row starts from zero: its row's value enters in the fix-up)
+  };
+  auto load_ids = [&](int32_t base, int32_t end) -> uint32_t {
+    const int32_t q = base + lane;
+    return q < end ? (uint32_t)__builtin_nontemporal_load(&a.indices[q]) * (uint32_t)kSlotBytes : 0u;
+  };
+  // the gathers of one step: 8 U edges from edge k of the current 64-edge chunk on, one 16-byte piece of a slot per lane
+  auto issue = [&](int k, int cnt, uint32_t goff, v4f (&val)[U], uint32_t (&roff)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = k + u * 8 + grp;
+      roff[u] = (uint32_t)__builtin_amdgcn_ds_bpermute((e < cnt ? e : 0) * 4, (int)goff);
+      val[u] = *reinterpret_cast<const v4f*>(slots + roff[u] + laneoff);
+    }
+  };
+  auto consume = [&](int k, int cnt, const v4f (&val)[U], const uint32_t (&roff)[U]) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool live = k + u * 8 + grp < cnt;
+      const uint32_t meta = (uint32_t)__float_as_int(val[u].x);
+      const uint32_t c0 = meta & 0xffu, c1 = (meta >> 8) & 0xffu, c2 = (meta >> 16) & 0xffu;
+      const bool dense = live && (meta >> 24) == 255u;
+      const bool valued = live && !dense && c0 < 64u;  // (a lane's values fill c0 first)
+      const uint64_t busy = __ballot(dense || valued);
+      if (busy == 0) continue;  // eight empty slots: nothing to add
+      v4f d0 = (v4f)(0.f), d1 = (v4f)(0.f);
+      if (dense) {  // more than 24 non-zeros: the dense row, 8 columns per lane
+        const char* dr = srcb + ((roff[u] / (uint32_t)kSlotBytes) * rowbytes + (uint32_t)gi * 32u);
+        d0 = *reinterpret_cast<const v4f*>(dr);
+        d1 = *reinterpret_cast<const v4f*>(dr + 16);
+      }
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {  // groups g before groups g + 4: the order of the additions to accumulator g & 3
+        if (((busy >> (32 * half)) & 0xffffffffull) == 0) continue;
+        if ((grp >> 2) == half) {
+          if (valued) {
+            const float a0 = accg[c0], a1 = accg[c1], a2 = accg[c2];  // (column 64 = the padding element of the accumulator row)
+            accg[c0] = a0 + val[u].y;
+            if (c1 < 64u) accg[c1] = a1 + val[u].z;
+            if (c2 < 64u) accg[c2] = a2 + val[u].w;
+          } else if (dense) {
+            v4f* ar = reinterpret_cast<v4f*>(accg + gi * 8);
+            ar[0] += d0;
+            ar[1] += d1;
+          }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+  };
+
+  int64_t row;
+  int32_t beg, end, ipos;
+  load_meta(item_base + r, row, beg, end, ipos);
+  uint32_t goff = load_ids(beg, end);
+  for (;;) {
+    // the initial value is requested before anything else of the item and enters accumulator 0 behind the first step's gathers
+    float iv = 0.f;
+    if (ipos >= 0) iv = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.init) + ((uint32_t)ipos * ((uint32_t)a.ldi * 4u) + (uint32_t)lane * 4u));
+    const int rn = r + kWavesPerBlock;
+    const bool has_next = rn < a.rpb && item_base + rn < item_stop;
+    int64_t nrow = 0;
+    int32_t nbeg = 0, nend = 0, nipos = -1;
+    uint32_t ngoff = 0;
+    if (has_next) {
+      load_meta(item_base + rn, nrow, nbeg, nend, nipos);
+      ngoff = load_ids(nbeg, nend);
+    }
+    for (int32_t cbase = beg; cbase < end; cbase += kWave) {
+      if (cbase != beg) goff = load_ids(cbase, end);
+      const int cnt = (end - cbase) < kWave ? (end - cbase) : kWave;
+      v4f va[U], vb[U];
+      uint32_t ra[U], rb[U];
+      issue(0, cnt, goff, va, ra);
+      if (cbase == beg) accw[lane] = iv;
+      int k = 0;
+      for (;;) {
+        if (k + 8 * U >= cnt) { consume(k, cnt, va, ra); break; }
+        issue(k + 8 * U, cnt, goff, vb, rb);
+        consume(k, cnt, va, ra);
+        k += 8 * U;
+        if (k + 8 * U >= cnt) { consume(k, cnt, vb, rb); break; }
+        issue(k + 8 * U, cnt, goff, va, ra);
+        consume(k, cnt, vb, rb);
+        k += 8 * U;
+      }
+    }
+    float A[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      A[j] = accw[j * kSlotAccStride + lane];
+      accw[j * kSlotAccStride + lane] = 0.f;
+    }
+    if (end <= beg) A[0] = iv;  // no edge: the initial value never reached the accumulator
+    const float res = (A[0] + A[1]) + (A[2] + A[3]);
+    if (row >= 0) __builtin_nontemporal_store(res, a.out + row * (int64_t)a.ldo + lane);
+    else a.partial[(-(row + 1)) * (int64_t)64 + lane] = res;
+    if (!has_next) break;
+    r = rn;
+    row = nrow; beg = nbeg; end = nend; ipos = nipos;
+    goff = ngoff;
+  }
+}
+
 // SHORT work items (the head of a two-part plan: direct rows of at most 32 edges): one item per LANE GROUP of 8 lanes, 8 items per wave at
 // a time (spmm_rowgroup32_kernel's reason: a wave per 3-edge row is one dependent chain per row).  The group's 8 lanes fetch the 8 pieces
 // of one slot per edge, U edges in flight, and add into the group's own accumulator row, which IS the item's result: no cross-group sum.
@@ -327,6 +476,25 @@ __global__ __launch_bounds__(kBlock) void rows_slots_pack_kernel(int64_t n, cons
   if (overflow && lane == 0 && over_rows) atomicAdd(overflow, over_rows);
 }
 
+// the slots of the listed rows only (mgx_rows_slots_pack_rows): what rows_slots_pack_kernel writes for them, byte for byte; four listed rows
+// per wave-instruction, a row id outside [0, n) is skipped
+__global__ __launch_bounds__(kBlock) void rows_slots_pack_rows_kernel(int64_t n, int64_t nrows, const int64_t* __restrict__ rows, const float* __restrict__ x,
+                                                                      int64_t ld, uint32_t* __restrict__ slots) {
+  __shared__ uint32_t stage_all[kWavesPerBlock][4 * 32];
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+  const int sub = lane >> 4, l = lane & 15;
+  const int64_t rows_per_pass = (int64_t)gridDim.x * kWavesPerBlock * 4;
+  for (int64_t base = ((int64_t)blockIdx.x * kWavesPerBlock + wave) * 4; base < nrows; base += rows_per_pass) {
+    int64_t r = -1;
+    if (base + sub < nrows) r = rows[base + sub];
+    const bool ok = r >= 0 && r < n;
+    v4f v = (v4f)(0.f);
+    if (ok) v = *reinterpret_cast<const v4f*>(x + r * ld + l * 4);
+    slot_pack_rows4(v, sub, l, stage_all[wave], ok ? slots + r * 32 : nullptr);
+  }
+}
+
 static bool spmm_slots_eligible(const SpmmFastArgs<int32_t>& a) {
   return a.D == 64 && a.lds % 4 == 0 && a.ldo >= 64 && !a.src_bits && !a.ragged &&
          a.src_rows * (int64_t)kSlotBytes < (int64_t(1) << 32) && a.src_rows * (int64_t)a.lds * 4 < (int64_t(1) << 32) &&
@@ -336,6 +504,13 @@ static bool spmm_slots_eligible(const SpmmFastArgs<int32_t>& a) {
 // the items of `a` on the slot kernels: a whole schedule or the `rest` part of a two-part plan (a wave per item), or its head of short
 // items (a.short_rows: a lane group per item)
 static void launch_spmm_slots(SpmmFastArgs<int32_t> a, const void* slots, hipStream_t s) {
+  if (a.init_pos) {  // mgx_spmm_copy_u_slots_init (its entry point checked; short items never come here: they carry no src_scale)
+    a.rpb = kItemsPerBlock;
+    const dim3 grid((unsigned)xcd_ranges(a.plan, a.n_items, a.rpb, a.xcd));
+    note_spmm_kernel("slots");
+    hipLaunchKernelGGL((spmm_slots_init_kernel<2>), grid, dim3(kBlock), 0, s, a, (const char*)slots);
+    return;
+  }
   if (a.short_rows) {
     a.rpb = 2 * kWavesPerBlock * 8;  // two batches per wave: the second's ids travel under the first's gathers
     const dim3 grid((unsigned)xcd_ranges(a.plan, a.n_items, a.rpb, a.xcd));

@@ -55,6 +55,8 @@ SIGNATURES = {
     "mgx_spmm_copy_u_edge_tail": (_i32, [_csr_p, _vp, _i32, _fp, _fp, _fp, _fp, _i64, _fp, _i32, _vp]),
     "mgx_rows_slots_pack": (_i32, [_i64, _i64, _fp, _i64, _fp, _vp, _vp, _vp]),
     "mgx_spmm_copy_u_slots": (_i32, [_csr_p, _vp, _i32, _fp, _i64, _i64, _vp, _fp, _fp, _fp, _i64, _fp, _i32, _vp]),
+    "mgx_rows_slots_pack_rows": (_i32, [_i64, _i64, _fp, _i64, _vp, _i64, _vp, _vp]),
+    "mgx_spmm_copy_u_slots_init": (_i32, [_csr_p, _vp, _i32, _fp, _i64, _i64, _vp, _fp, _fp, _i64, _i64, _vp, _fp, _i64, _fp, _i32, _vp]),
     "mgx_spmm_tile_copy_u": (_i32, [_csr_p, _vp, _vp, _i32, _fp, _i64, _i64, _fp, _fp, _i64, _fp, _i32, _vp]),
     "mgx_spmm_rel": (_i32, [_csr_p, _vp, _i32, _i64, _i64, _fp, _fp, _i64, _fp, _fp, _fp, _fp, _vp]),
     "mgx_spmm_rel_grad": (_i32, [_csr_p, _vp, _i64, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _vp]),

@@ -2,7 +2,7 @@
 
 USER switches are environment variables, read where they are used; the complete list is the table in README.md ("Switches"):
     MGX_LIB_PATH  MGX_DATA_ROOT  MGX_CACHE_DIR  MGX_SCHEDULE  MGX_TILE  MGX_GAT_TILE  MGX_GAT_FUSED  MGX_TORCH_OPS  MGX_SDDMM_WALK
-    MGX_SPARSE_HALO  MGX_ACCELERATE_LINEAR  MGX_SAGE_SPARSE_LAST  MGX_SAGE_HEAD_ROWS  MGX_XTY_MASKED  MGX_SAGE_L1_PROJECT_FIRST  MGX_PLAIN_MODEL  MGX_HOST_THREADS
+    MGX_SPARSE_HALO  MGX_ACCELERATE_LINEAR  MGX_SAGE_SPARSE_LAST  MGX_SAGE_HEAD_ROWS  MGX_SAGE_HEAD_SLOTS  MGX_XTY_MASKED  MGX_SAGE_L1_PROJECT_FIRST  MGX_PLAIN_MODEL  MGX_HOST_THREADS
 (+ the bench / test hooks MGX_DIST_BACKEND, MGX_BENCH_SHARE_GPU, MGX_BENCH_TUNABLEOP, MGX_BENCH_STEP_TIMES, MGX_DATASET_SCALE).
 
 Everything below is NOT a user switch: module attributes with fixed defaults that choose between a fused form and the composition it
@@ -22,6 +22,8 @@ SAGE_PROJECT_FIRST = True  # project before aggregating when that moves fewer co
 SAGE_HEAD_ROWS = True      # the last layer's dense work on the loss rows only (ops.SageMeanCatHeadFn; MGX_SAGE_HEAD_ROWS=0 turns it off)
 SAGE_HEAD_INIT = True      # ... its reversed aggregation started from the compact d self (mgx_spmm_copy_u_strided_init), d neigh / deg scattered into
                            # one [N, K] matrix kept zero elsewhere between steps (ops._head_dn): no zero fill, no copy of d self into one
+SAGE_HEAD_SLOTS = True     # ... and, on a graph of PACKED_GATHER_MIN_NNZ edges with K = 64, gathering that matrix as 128-byte slots kept beside it: an
+                           # empty slot per zero row, the dense row on a flag (mgx_spmm_copy_u_slots_init, same bits; MGX_SAGE_HEAD_SLOTS=0 turns it off)
 ROWS_GEMM = True           # mgx_rows_gemm for the projections of a layer over >= 65 536 rows (else the library GEMM)
 LINEAR_XTY = True          # tall-skinny weight gradients by mgx_xty (else the library GEMM)
 XTY_COLSUM = True          # ... with the bias gradient from the same pass (mgx_xty_colsum)

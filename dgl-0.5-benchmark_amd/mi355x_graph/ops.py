@@ -1305,7 +1305,7 @@ def _head_rows_forward(ctx, gidx, cat, h, w_self, w_neigh, bias, rows):
     return y
 
 
-def _head_dn(csr, K, rows, n, like):
+def _head_dn(csr, K, rows, n, like, be):
     """The [N, K] matrix SageMeanCatHeadFn's backward scatters d neigh / deg into, zero outside `rows`: ONE matrix, kept between steps
     instead of a zero fill per step (config.SAGE_HEAD_INIT) -- on the CSR the reversed aggregation gathers it over, which lives as long
     as the graph (the CatBuffer of a hidden layer's output is a new one every forward pass; steps over one graph run one after the
@@ -1314,22 +1314,48 @@ def _head_dn(csr, K, rows, n, like):
     clearing; with another list the rows of the previous one are cleared first (the whole matrix when that list was written to since).
     Internal to the node: the aggregation reads it, autograd never sees it.  Inside a HIP-graph capture the step gets a zero matrix
     of its own, filled in the captured step: a replay runs none of this bookkeeping, and eager steps with other lists in between
-    must not leave their rows in what it reads."""
+    must not leave their rows in what it reads.
+    config.SAGE_HEAD_SLOTS (_head_slots_wanted): the matrix's 128-byte slots are kept beside it, for the aggregation to gather instead of
+    the dense rows (mgx_spmm_copy_u_slots_init) -- all of them packed when the matrix is created or cleared as a whole, the slots of a
+    previous list's rows packed again (empty) when those rows are cleared; the step's rows are packed by the caller once the scatter has
+    written them (_head_dn_slots).  A captured step has no slots."""
     if torch.cuda.is_current_stream_capturing():
         return torch.zeros((n, K), dtype=like.dtype, device=like.device)
     held = csr._head_dn
+    slots, stale = None, True  # stale: every slot has to be written again
     if held is None or held[0].shape != (n, K) or held[0].dtype != like.dtype or held[0].device != like.device:
         buf = torch.zeros((n, K), dtype=like.dtype, device=like.device)
     else:
-        buf, prev, version = held
+        buf, prev, version, slots = held
+        stale = slots is None
         if prev is rows and version == rows._version:
             pass
         elif prev._version == version:
             buf.index_fill_(0, prev, 0.0)
+            if slots is not None:
+                be.rows_slots_pack_rows(buf, prev, slots)  # the cleared rows' slots are empty again
         else:
             buf.zero_()
-    csr._head_dn = (buf, rows, rows._version)
+            stale = True
+    if _head_slots_wanted(csr, K, be) and be.rows_slots_supported(buf, csr):
+        if stale:
+            slots = be.rows_slots_pack(buf)[0]  # (a kept list's rows included: the step's scatter and its pack follow)
+    else:
+        slots = None
+    csr._head_dn = (buf, rows, rows._version, slots)
     return buf
+
+
+def _head_slots_wanted(csr, K, be):
+    """Does the reversed aggregation of SageMeanCatHeadFn gather d neigh / deg over `csr` as 128-byte slots (config.SAGE_HEAD_SLOTS)?"""
+    return (config.SAGE_HEAD_SLOTS and config.SAGE_HEAD_INIT and os.environ.get("MGX_SAGE_HEAD_SLOTS", "1") != "0" and K == 64
+            and csr.nnz >= config.PACKED_GATHER_MIN_NNZ and hasattr(be, "spmm_copy_u_slots_init") and hasattr(be, "rows_slots_pack_rows"))
+
+
+def _head_dn_slots(csr, dn):
+    """The slots kept beside `dn` when it is the matrix _head_dn keeps on `csr` (None: a captured step, the switch off, another matrix)."""
+    held = csr._head_dn
+    return held[3] if held is not None and held[0] is dn else None
 
 
 def _head_rows_dense_backward(be, gidx, cat, w_self, w_neigh, dyr, rows, need_dh, need_w, need_b, zero_fill):
@@ -1341,7 +1367,7 @@ def _head_rows_dense_backward(be, gidx, cat, w_self, w_neigh, dyr, rows, need_dh
     if need_dh:
         wcat = torch.cat([w_self, w_neigh], dim=1)  # [out, 2K]
         if zero_fill and config.SAGE_HEAD_INIT:
-            dn = _head_dn(gidx.csr(), K, rows, n, dyr)
+            dn = _head_dn(gidx.csr(), K, rows, n, dyr, be)
         else:
             dn = (torch.zeros if zero_fill else torch.empty)((n, K), dtype=dyr.dtype, device=dyr.device)
         inv_r = _row_inv_deg(rows, gidx.csc().inv_degrees())
@@ -1354,6 +1380,9 @@ def _head_rows_dense_backward(be, gidx, cat, w_self, w_neigh, dyr, rows, need_dh
             d_self = dcat[:, :K]
         else:
             d_self = pair[0]
+        slots = _head_dn_slots(gidx.csr(), dn) if zero_fill and config.SAGE_HEAD_INIT else None
+        if slots is not None:
+            be.rows_slots_pack_rows(dn, rows, slots)  # the listed rows hold this step's values now
     if need_w:
         # over the listed rows, but summed as the layer over all rows sums them (mgx_xty_colsum_pos): a training run then stays on the
         # bits of that layer -- sums of the listed rows alone in their own order (mgx_xty_rows) differ in the last place, and Adam on
@@ -1388,9 +1417,10 @@ class SageMeanCatHeadFn(torch.autograd.Function):
     operands of mgx_rows_gemm_rows and the position map of mgx_xty_colsum_pos instead of over all N rows, of which the loss reads 8 % on ogbn-products.
     Both aggregations are untouched: every row is aggregated forward, and the reversed one gathers every source row over every edge
     from d neigh / deg, which is zero outside the rows: an [N, K] matrix the GEMM scatters into, kept zero elsewhere from step to step
-    (_head_dn).  Its sums start from d self, which stays the compact [R, K] matrix the GEMM wrote: the aggregation takes it through
-    the position map (mgx_spmm_copy_u_strided_init) and writes every row of d h once.  config.SAGE_HEAD_INIT = False, or operands
-    that entry point declines: a zero-filled [N, K] per step, d self copied into a second one, the accumulating aggregation.
+    (_head_dn) -- as 128-byte slots kept beside it on a big graph with K = 64 (config.SAGE_HEAD_SLOTS, mgx_spmm_copy_u_slots_init: the
+    slot of a zero row is empty, a dense row is read on its slot's flag), else as the dense rows.  Its sums start from d self, which
+    stays the compact [R, K] matrix the GEMM wrote: the aggregation takes it through the position map
+    (mgx_spmm_copy_u_strided_init) and writes every row of d h once.  config.SAGE_HEAD_INIT = False, or operands that entry point declines: a zero-filled [N, K] per step, d self copied into a second one, the accumulating aggregation.
     Every sum is formed in the order the layer over all rows forms it, so the gradients are that layer's bit for bit.  No atomics,
     no host synchronisation."""
 
@@ -1411,6 +1441,12 @@ class SageMeanCatHeadFn(torch.autograd.Function):
             # config.SAGE_HEAD_INIT: the same sums started from the compact d self through the position map
             # (mgx_spmm_copy_u_strided_init) -- no zero matrix, no copy into it, no read of it; the sequence below where it declines
             if config.SAGE_HEAD_INIT and d_self.stride(1) == 1:
+                # config.SAGE_HEAD_SLOTS: ... gathering the slots kept beside d neigh / deg -- one line per edge, nothing to add for the
+                # 92 % of the source rows that are zero, the dense row on a slot's flag (mgx_spmm_copy_u_slots_init); the same bits
+                slots = _head_dn_slots(ctx.gidx.csr(), dn)
+                if slots is not None:
+                    dh = be.spmm_copy_u_slots_init(ctx.gidx.csr(), "sum", dn, slots, d_self, _row_pos(rows, dn.shape[0]), torch.empty_like(dn))
+            if dh is None and config.SAGE_HEAD_INIT and d_self.stride(1) == 1:
                 dh = be.spmm_copy_u_strided_init(ctx.gidx.csr(), "sum", dn, d_self, _row_pos(rows, dn.shape[0]), torch.empty_like(dn))
             if dh is None:
                 dh = torch.zeros_like(dn).index_copy_(0, rows, d_self)

@@ -83,7 +83,7 @@ class CsrView(object):
         self._row_order = (None, None)  # (row order, kind) computed with the first plan
         self._rows = None  # row id of every stored position (the expanded indptr), built on first use by the permuted g-SDDMM walk
         self._gate = None  # ops._SlotGate of untagged 64-column operands aggregated over this CSR (ops._gspmm_over_slots)
-        self._head_dn = None  # (matrix, row list, its version): the [N, K] operand ops.SageMeanCatHeadFn's backward gathers over this CSR, kept
+        self._head_dn = None  # (matrix, row list, its version, its slots or None): the [N, K] operand ops.SageMeanCatHeadFn's backward gathers over this CSR, kept
                               # zero outside the list between steps (ops._head_dn)
         self.dst_is_src_prefix = False  # block graphs whose destination nodes are the first source nodes
 
@@ -621,6 +621,61 @@ class HipBackend(object):
                 ctypes.byref(csr.c_struct()), None if plan is None else ctypes.byref(plan.c_struct()), REDUCE[reduce], _ptr(U2d), D,
                 int(U2d.stride(0)), _ptr(dst_scale), _ptr(init2d) if init2d.shape[0] else None, int(init2d.shape[0]),
                 max(int(init2d.stride(0)), D) if init2d.shape[0] else D, _ptr(init_pos), _ptr(out2d), int(out2d.stride(0)), _ptr(partial), 2 if short else 0, _stream(dev))
+            if st == _lib.ERR_UNSUPPORTED:
+                return None
+            _lib.check(st)
+            if rec is not None:
+                rec["end"].record(torch.cuda.current_stream(dev))
+                PROFILE.append(rec)
+        return out2d
+
+    def rows_slots_pack_rows(self, x2d, rows, slots):
+        """slots[rows[i]] = the 128-byte slot of row rows[i] of x2d [n, 64], for the listed rows only (int64, distinct): byte for byte what
+        rows_slots_pack writes for them; every other slot stays as it is (mgx_rows_slots_pack_rows).  Returns slots."""
+        dev = self._check_dev(x2d, rows, slots)
+        n = int(x2d.shape[0])
+        if (x2d.dim() != 2 or x2d.stride(1) != 1 or rows.dtype != torch.int64 or rows.dim() != 1 or not rows.is_contiguous()
+                or slots.shape != (n, 32) or slots.dtype != torch.int32 or not slots.is_contiguous()):
+            raise DGLError("rows_slots_pack_rows: expected a row-strided [n, 64] matrix, an int64 row list and the [n, 32] int32 slots of rows_slots_pack")
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().mgx_rows_slots_pack_rows(n, int(x2d.shape[1]), _ptr(x2d), int(x2d.stride(0)), _ptr(rows), int(rows.shape[0]),
+                                                           _ptr(slots), _stream(dev)))
+        return slots
+
+    def spmm_copy_u_slots_init(self, csr, reduce, U2d, slots, init2d, init_pos, out2d, dst_scale=None):
+        """spmm_copy_u_strided_init with `slots` = rows_slots_pack(U2d)[0] beside U2d: the wave-per-item work items gather one 128-byte slot
+        per edge, add nothing for an empty one and read the dense row of a flagged one -- for a U2d most of whose rows are zero
+        (mgx_spmm_copy_u_slots_init).  The bits of spmm_copy_u_strided_init wherever no element of U2d / init2d is -0.0.  Returns out2d,
+        or None when the library has no kernel for these operands (what spmm_copy_u_strided_init declines, and D != 64)."""
+        dev = self._check_dev(csr.indptr, U2d, slots, init2d, init_pos, out2d, dst_scale)
+        D = int(U2d.shape[1])
+        if (U2d.dim() != 2 or out2d.dim() != 2 or init2d.dim() != 2 or U2d.stride(1) != 1 or out2d.stride(1) != 1 or out2d.shape[1] != D
+                or init2d.shape[1] != D or (init2d.stride(1) != 1 and init2d.shape[0] > 0) or U2d.shape[0] != csr.num_cols
+                or out2d.shape[0] != csr.num_rows or init_pos.dtype != torch.int64 or init_pos.shape != (csr.num_rows,)
+                or not init_pos.is_contiguous()):
+            raise DGLError("spmm_copy_u_slots_init: expected row-strided [num_cols, D] -> [num_rows, D] views, a row-strided [R, D] "
+                           "initial matrix and an int64 [num_rows] position map")
+        if slots.shape != (U2d.shape[0], 32) or slots.dtype != torch.int32 or not slots.is_contiguous():
+            raise DGLError("spmm_copy_u_slots_init: slots must be the [num_cols, 32] int32 result of rows_slots_pack")
+        if D >= config.TILE_MIN_WIDTH and D % 4 == 0 and csr.idx_bits == 32 and csr.tile_plan(D) is not None:  # (the tile kernel has no such operand)
+            return None
+        plan, short = csr.spmm_plan_for(D)
+        partial = torch.empty((plan.total_slots, D), dtype=torch.float32, device=dev) if plan is not None and plan.total_slots else None
+        with torch.cuda.device(dev):
+            rec = None
+            if PROFILE is not None:
+                rec = {"op": "copy_lhs", "reduce": reduce, "out_len": D, "n_rows": csr.num_rows, "n_cols": csr.num_cols,
+                       "nnz": csr.nnz, "accumulate": True, "strides": (int(U2d.stride(0)), int(out2d.stride(0))),
+                       "start": torch.cuda.Event(enable_timing=True), "end": torch.cuda.Event(enable_timing=True)}
+                if short:
+                    rec["variant"] = _short_variant(plan)
+                rec["variant"] = (rec.get("variant", "") + "+slots").lstrip("+")
+                rec["start"].record(torch.cuda.current_stream(dev))
+            st = _lib.lib().mgx_spmm_copy_u_slots_init(
+                ctypes.byref(csr.c_struct()), None if plan is None else ctypes.byref(plan.c_struct()), REDUCE[reduce], _ptr(U2d), D,
+                int(U2d.stride(0)), _ptr(slots), _ptr(dst_scale), _ptr(init2d) if init2d.shape[0] else None, int(init2d.shape[0]),
+                max(int(init2d.stride(0)), D) if init2d.shape[0] else D, _ptr(init_pos), _ptr(out2d), int(out2d.stride(0)), _ptr(partial),
+                2 if short else 0, _stream(dev))
             if st == _lib.ERR_UNSUPPORTED:
                 return None
             _lib.check(st)

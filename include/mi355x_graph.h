@@ -261,6 +261,29 @@ int32_t mgx_spmm_copy_u_slots(const mgx_csr* csr, const mgx_spmm_plan* plan /* m
                               const float* dst_scale /* may be NULL */, float* out, int64_t out_stride, float* partial_ws, int32_t flags,
                               void* stream);
 
+/* mgx_spmm_copy_u_slots_init is mgx_spmm_copy_u_strided_init with the slots beside the dense matrix (slots = pack(ufeat), no factor),
+ * for a gathered matrix most of whose ROWS are zero -- d neigh / deg of a loss taken on 8 % of the nodes:
+ *     out[v] = (init[init_pos[v]] where init_pos[v] >= 0, else +0.0f) + SUM_{u -> v} ufeat[u, :]          (`out` is write-only)
+ * A wave-per-item work item gathers one 128-byte slot per edge; an empty slot adds nothing, a slot with values adds them at their
+ * columns, a flagged slot adds the dense row of `ufeat`.  The additions per output element are made in the order of the dense call --
+ * four accumulators, edge e of an item to accumulator e % 4, the initial value first in accumulator 0, (A0 + A1) + (A2 + A3) -- and a
+ * skipped addend is an exact +0.0f, so the result is that of mgx_spmm_copy_u_strided_init on the same graph and plan
+ *     bit for bit wherever no element of `ufeat` and `init` is -0.0f;
+ *     equal as numbers otherwise (mgx_rows_slots_pack drops a -0.0f, and a skipped +0.0f would have turned a running sum of -0.0f into
+ *     +0.0f): only the sign of an exactly-zero result can differ.
+ * The short items of a two-part plan (MGX_SPMM_SHORT_ROWS) read the dense rows, as in mgx_spmm_copy_u_slots without a factor.
+ * reduce = MGX_REDUCE_SUM, dst_scale = NULL, int32 graph, D = 64, fewer than 2^25 source rows, and the alignment / stride / size
+ * conditions of the two entries it combines; anything else returns MGX_ERR_UNSUPPORTED before a launch.
+ * mgx_rows_slots_pack_rows writes the slots of the listed rows only -- rows int64 [num_listed], distinct, in [0, n) (an id outside is
+ * skipped) -- byte for byte what mgx_rows_slots_pack writes for them; every other slot is left as it is.
+ * Deterministic: no atomics.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_rows_slots_pack_rows(int64_t n, int64_t D /* 64 */, const float* x, int64_t x_stride, const int64_t* rows, int64_t num_listed,
+                                 void* slots /* [n, 128 bytes] */, void* stream);
+int32_t mgx_spmm_copy_u_slots_init(const mgx_csr* csr, const mgx_spmm_plan* plan /* may be NULL */, int32_t reduce, const float* ufeat,
+                                   int64_t D /* 64 */, int64_t u_stride, const void* slots, const float* dst_scale /* must be NULL */,
+                                   const float* init, int64_t init_rows /* R */, int64_t init_stride, const int64_t* init_pos, float* out,
+                                   int64_t out_stride, float* partial_ws, int32_t flags, void* stream);
+
 /* LDS-staged copy_u / sum | mean for DENSE neighbourhoods (round 3; csrc/spmm_tile.hip).  On graphs with hundreds of in-edges
  * per node (reddit, proteins: kernel/dgl-new.py:61; main_dgl_reddit_sage.py:73-80) destination rows scheduled next to each other
  * share most of their sources; a TILE of consumers * nacc * 4 work items of the schedule is aggregated by one workgroup of
