@@ -18,6 +18,7 @@
 // Every random number is a function of (rng_seed, seed slot, draw or CSR position), never of the launch geometry.
 #include "common.h"
 #include "counter_rng.h"  // mix64
+#include "wave_select.h"
 
 namespace mgx {
 
@@ -62,38 +63,7 @@ __global__ __launch_bounds__(kBlock) void sample_neighbors_kernel(const Idx* ind
 
 
 // ---- one wave per seed: weighted / with-replacement sampling, top-k ----------------------------------------------------------
-// A candidate edge is ONE 64-bit number: the key as order-preserving bits above the position inside the row, so that pairs compare
-// as (key, position) -- equal keys fall to the lower CSR position -- and all-ones (kNoPair) sorts after every real pair, +inf keys
-// included.  (Rows are taken to be shorter than 2^32 - 1 edges.)
-constexpr uint64_t kNoPair = ~0ull;
-
-__device__ __forceinline__ uint64_t pack_pair(float key, uint64_t rel_pos) {
-  const uint32_t b = __float_as_uint(key);
-  return ((uint64_t)(b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u)) << 32) | (rel_pos & 0xFFFFFFFFull);
-}
-
-// v of the 64 lanes in ascending lane order (bitonic network, 21 compare-exchanges over ds_bpermute)
-__device__ __forceinline__ uint64_t wave_sort(uint64_t v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= kWave; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint64_t o = __shfl_xor(v, j, kWave);
-      const bool keep_min = ((lane & j) == 0) == ((lane & k) == 0);
-      v = keep_min ? (o < v ? o : v) : (o > v ? o : v);
-    }
-  }
-  return v;
-}
-// the last 6 steps alone: sorts a bitonic sequence
-__device__ __forceinline__ uint64_t wave_bitonic_merge(uint64_t v, int lane) {
-#pragma unroll
-  for (int j = kWave >> 1; j > 0; j >>= 1) {
-    const uint64_t o = __shfl_xor(v, j, kWave);
-    v = ((lane & j) == 0) ? (o < v ? o : v) : (o > v ? o : v);
-  }
-  return v;
-}
+// (key, position) pairs, kNoPair, wave_sort and wave_bitonic_merge: wave_select.h, shared with segtopk.hip.
 
 // Inclusive scan of w over the lanes IN LANE ORDER, fl(fl(w0 + w1) + w2) ...: a lane of weight 0 repeats its predecessor's sum bit for
 // bit and the sums never decrease, which a tree-shaped scan does not promise under rounding -- the inverse CDF below depends on both

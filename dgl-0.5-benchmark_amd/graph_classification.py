@@ -77,28 +77,32 @@ class GCNConv(nn.Module):
         return {"m": norm * F.relu(edges.src["x"] + edges.data["w"])}
 
 
-def make_readout(kind, emb_dim):
+def make_readout(kind, emb_dim, sortpool_k=30):
     """(readout module, width of its output) for --readout: `mean` is the reference's AvgPooling (main_dgl_molhiv_gcn.py:75); `attention`
     is dgl.nn.GlobalAttentionPooling with a Linear(emb_dim, 1) gate; `set2set` is dgl.nn.Set2Set(emb_dim, 3 iterations, 1 LSTM layer),
-    whose output is twice as wide.  Both attention readouts run ops.segment_attention (csrc/segattn.hip): one launch each way."""
+    whose output is twice as wide.  Both attention readouts run ops.segment_attention (csrc/segattn.hip): one launch each way.
+    `sortpool` is dgl.nn.SortPooling(sortpool_k): the k nodes with the largest last (sorted) feature, flattened to k * emb_dim columns
+    (ops.segment_topk, csrc/segtopk.hip); its output shape is static, so the padded batches of --hipgraph capture it as it is."""
     if kind == "mean":
         return dgl.nn.AvgPooling(), emb_dim
     if kind == "attention":
         return dgl.nn.GlobalAttentionPooling(nn.Linear(emb_dim, 1)), emb_dim
     if kind == "set2set":
         return dgl.nn.Set2Set(emb_dim, n_iters=3, n_layers=1), 2 * emb_dim
+    if kind == "sortpool":
+        return dgl.nn.SortPooling(sortpool_k), sortpool_k * emb_dim
     raise ValueError("unknown readout %r" % (kind,))
 
 
 class GCN(nn.Module):
-    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, bond_columns=3, readout="mean", fused=False):
+    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, bond_columns=3, readout="mean", fused=False, sortpool_k=30):
         super(GCN, self).__init__()
         self.fused = fused
         self.atom_encoder = CategoricalEncoder(emb_dim, atom_columns)
         self.layers = nn.ModuleList([GCNConv(emb_dim, emb_dim, bond_columns, fused=fused) for _ in range(num_layers)])
         self.bns = nn.ModuleList([nn.BatchNorm1d(emb_dim) for _ in range(num_layers - 1)])
         self.dropout = nn.Dropout(p=dropout)
-        self.readout, width = make_readout(readout, emb_dim)
+        self.readout, width = make_readout(readout, emb_dim, sortpool_k)
         self.graph_pred_fc = nn.Linear(width, num_classes, bias=False)
 
     def edge_norm(self, g):
@@ -121,7 +125,7 @@ class GIN(nn.Module):
     copy_u/sum g-SpMM per layer on the batched graph; atom encoder, BatchNorm / relu / dropout and the mean readout as in
     the GCN above.  Bond features are not used (plain GIN)."""
 
-    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, readout="mean"):
+    def __init__(self, emb_dim, num_classes, num_layers, dropout, atom_columns=9, readout="mean", sortpool_k=30):
         super(GIN, self).__init__()
         from dgl.nn.pytorch import GINConv
         self.atom_encoder = CategoricalEncoder(emb_dim, atom_columns)
@@ -130,7 +134,7 @@ class GIN(nn.Module):
         self.layers = nn.ModuleList([GINConv(mlp(), "sum", learn_eps=True) for _ in range(num_layers)])
         self.bns = nn.ModuleList([nn.BatchNorm1d(emb_dim) for _ in range(num_layers - 1)])
         self.dropout = nn.Dropout(p=dropout)
-        self.readout, width = make_readout(readout, emb_dim)
+        self.readout, width = make_readout(readout, emb_dim, sortpool_k)
         self.graph_pred_fc = nn.Linear(width, num_classes, bias=False)
 
     def forward(self, g, atom, bond=None):
@@ -407,8 +411,10 @@ def make_parser():
     p.add_argument("--dropout", type=float, default=0.5)
     p.add_argument("--model", default="gcn", choices=["gcn", "gin"],
                    help="gcn: the reference's main_dgl_molhiv_gcn.py model; gin: BASELINE.json's wording of config 5")
-    p.add_argument("--readout", default="mean", choices=["mean", "attention", "set2set"],
-                   help="mean: the reference's AvgPooling; attention: GlobalAttentionPooling; set2set: Set2Set (3 iterations)")
+    p.add_argument("--readout", default="mean", choices=["mean", "attention", "set2set", "sortpool"],
+                   help="mean: the reference's AvgPooling; attention: GlobalAttentionPooling; set2set: Set2Set (3 iterations); "
+                        "sortpool: SortPooling (--sortpool-k nodes per graph)")
+    p.add_argument("--sortpool-k", type=int, default=30, help="--readout sortpool: nodes kept per graph")
     p.add_argument("--fused-message", action="store_true",
                    help="gcn: run every layer's norm * relu(x_u + w_e) message and its sum as ONE operator (dgl.ops.gine_sum) instead "
                         "of the UDF's gathers, add / relu / mul and copy_e/sum g-SpMM")
@@ -426,7 +432,8 @@ def main():
     loader = GraphDataLoader(data, batch_size=args.batch_size, shuffle=True, num_workers=args.num_workers)
     torch.manual_seed(0)
     extra = {"fused": True} if args.fused_message and args.model == "gcn" else {}
-    model = (GCN if args.model == "gcn" else GIN)(args.emb_dim, 1, args.num_layers, args.dropout, readout=args.readout, **extra).to(device)
+    model = (GCN if args.model == "gcn" else GIN)(args.emb_dim, 1, args.num_layers, args.dropout, readout=args.readout, sortpool_k=args.sortpool_k,
+                                                    **extra).to(device)
     loss_fn = nn.BCEWithLogitsLoss()
     trainer = None
     if args.hipgraph:

@@ -10,7 +10,7 @@ from .graph import DGLGraph, GraphIndex, graph, create_block, ALL  # noqa: F401
 from .heterograph import DGLHeteroGraph, heterograph, bipartite, hetero_from_relations  # noqa: F401
 from . import readout  # noqa: F401
 from .readout import (readout_nodes, sum_nodes, mean_nodes, max_nodes, softmax_nodes, broadcast_nodes,  # noqa: F401
-                      readout_edges, sum_edges, mean_edges, max_edges, softmax_edges, broadcast_edges)
+                      readout_edges, sum_edges, mean_edges, max_edges, softmax_edges, broadcast_edges, topk_nodes, topk_edges)
 
 __version__ = "0.1.0"
 

@@ -42,6 +42,9 @@ GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> r
 # ---- graph readout (ops.segment_attention, nn.GlobalAttentionPooling, nn.Set2Set)
 SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: segment max -> gather -> exp -> segment sum -> gather -> multiply -> segment sum
 
+# ---- segment top-k (ops.segment_topk, readout.topk_nodes / topk_edges, nn.SortPooling)
+SEGMENT_TOPK_FUSED = True  # csrc/segtopk.hip, one launch each way; False: two stable sorts and gathers in torch operators
+
 # ---- sampled blocks and induced subgraphs (sampling.to_block, sampling.node_subgraph)
 DEVICE_BLOCKS = True    # the relabelling kernels of csrc/relabel.hip; False: look-up table -> unique -> gathers -> bincount + cumsum in torch ops
 DEVICE_SUBGRAPH = True  # a wave per selected row of a materialised in-CSR (csrc/relabel.hip); False: the look-up table gathered at both ends of every parent edge

@@ -6,6 +6,7 @@
   GraphConv  main_dgl_enzymes_gcn_nn.py:12,29-36
   AvgPooling / SumPooling / MaxPooling   main_dgl_molhiv_gcn.py:75,93
   GlobalAttentionPooling / Set2Set / WeightAndSum   dgl.nn.pytorch.glob (attention readouts, fused: ops.segment_attention)
+  SortPooling   dgl.nn.pytorch.glob (the DGCNN readout: ops.segment_topk)
 Parameter names, shapes and initialisation follow DGL v0.6.x so state_dicts and the scripts'
 reset_parameters() calls (main_dgl_reddit_gat.py:57-59) line up.
 """
@@ -637,6 +638,25 @@ class Set2Set(nn.Module):
 
     def extra_repr(self):
         return "n_iters={n_iters}".format(**self.__dict__)
+
+
+class SortPooling(nn.Module):
+    """dgl.nn.SortPooling (Zhang et al., An End-to-End Deep Learning Architecture for Graph Classification): every node's features sorted
+    ascending, the k nodes of every graph with the largest last feature in descending order, flattened -> [B, k * D]; graphs with fewer
+    than k nodes are padded with zeros.  The selection is ONE ops.segment_topk call (csrc/segtopk.hip, sortby = -1); the per-node
+    feature sort stays a torch operator (feat.sort(dim=-1))."""
+
+    def __init__(self, k):
+        super(SortPooling, self).__init__()
+        self.k = k
+
+    def forward(self, graph, feat):
+        feat, _ = feat.sort(dim=-1)
+        values, _ = ops.segment_topk(graph.batch_num_nodes(), feat, self.k, sortby=-1, descending=True, total=graph.number_of_nodes())
+        return values.view(values.shape[0], -1)
+
+    def extra_repr(self):
+        return "k={k}".format(**self.__dict__)
 
 
 class WeightAndSum(nn.Module):

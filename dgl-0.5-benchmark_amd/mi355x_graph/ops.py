@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -1894,6 +1894,108 @@ def segment_attention(seglen, feat, logits=None, query=None, scale=1.0, total=No
     if feat.shape[0] == 0 or seglen.shape[0] == 0:
         return feat.new_zeros((seglen.shape[0],) + tuple(feat.shape[1:]))
     return _segment_attention_composed(offsets, feat, logits, query, scale, n)
+
+
+# ----------------------------------------------------------------------------- graph readout: segment top-k
+class SegmentTopk(torch.autograd.Function):
+    """(values, index) of the k first rows (sortby = a column) or elements of every column (sortby = None) of every segment in the order
+    of a stable sort: ONE launch of csrc/segtopk.hip, which also writes the inverse map the backward -- one gather -- reads."""
+
+    @staticmethod
+    def forward(ctx, feat, offsets, k, sortby, descending):
+        values, index, slot = sparse.backend_for(feat).segment_topk_fwd(offsets, feat, k, sortby, descending)
+        ctx.mark_non_differentiable(index)
+        ctx.save_for_backward(slot)
+        ctx.D = int(feat.shape[1])
+        return values, index
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_values, _d_index):
+        slot, = ctx.saved_tensors
+        return sparse.backend_for(slot).segment_topk_bwd(slot, d_values, ctx.D), None, None, None, None
+
+
+def _segment_topk_composed(offsets, feat, k, sortby, descending, n):
+    """ops.segment_topk through torch operators, in the same order: a stable sort by key, then a stable sort by segment id, leaves every
+    segment's rows in place as a block, ordered; rank j of segment s is position offsets[s] + j.  Zero padding and index -1 past a
+    segment's end.  The form for CPU tensors, for k > 1024, under MGX_TORCH_OPS=1 and with config.SEGMENT_TOPK_FUSED off."""
+    S, D = offsets.shape[0] - 1, int(feat.shape[1])
+    columns = sortby is None
+    if n == 0 or S == 0:
+        return feat.new_zeros((S, k, D)), torch.full((S, k, D) if columns else (S, k), -1, dtype=torch.int64, device=feat.device)
+    with torch.no_grad():
+        key = feat if columns else feat[:, sortby:sortby + 1]
+        key = torch.where(key != key, key.new_full((), float("nan")), key + 0.0)  # one NaN, one zero: a sort by key bits orders the same
+        seg = _segment_ids(offsets, n)
+        by_key = torch.sort(key, dim=0, stable=True, descending=bool(descending)).indices        # [n, D | 1]
+        by_seg = torch.sort(seg[by_key], dim=0, stable=True).indices
+        perm = by_key.gather(0, by_seg)                                                          # position -> row
+        rank = torch.arange(k, device=feat.device)
+        valid = rank.unsqueeze(0) < (offsets[1:] - offsets[:-1]).unsqueeze(1)                    # [S, k]
+        pos = (offsets[:-1].unsqueeze(1) + rank.unsqueeze(0)).clamp(max=n - 1)                   # [S, k]
+        row = perm[pos.view(-1)]                                                                 # [S * k, D | 1]
+        index = torch.where(valid.view(-1, 1), row - offsets[:-1].repeat_interleave(k).unsqueeze(1), row.new_full((), -1))
+    if columns:
+        values = feat.gather(0, row)
+    else:
+        values = feat[row.view(-1)]
+    values = torch.where(valid.view(-1, 1), values, values.new_zeros(()))
+    return values.view(S, k, D), index.view((S, k, D) if columns else (S, k))
+
+
+def _segment_topk_args(seglen, feat, k, sortby, total):
+    if not torch.is_tensor(feat) or feat.dim() not in (1, 2):
+        raise DGLError("segment_topk: expected feat [N] or [N, D], got %s" % (tuple(feat.shape) if torch.is_tensor(feat) else type(feat).__name__,))
+    if feat.dtype != torch.float32:
+        raise DGLError("segment_topk expects float32 input, got %s" % (feat.dtype,))
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise DGLError("segment_topk: k must be an integer >= 1, got %r" % (k,))
+    if torch.is_tensor(seglen) and seglen.device != feat.device and seglen.device.type != "cpu":  # host lengths go with any feat
+        raise DGLError("segment_topk: operands on different devices: %s vs %s" % (feat.device, seglen.device))
+    feat2d = feat if feat.dim() == 2 else feat.unsqueeze(1)
+    D = int(feat2d.shape[1])
+    if D < 1:
+        raise DGLError("segment_topk: feat has no columns")
+    if sortby is not None:
+        if isinstance(sortby, bool) or not isinstance(sortby, int) or not -D <= sortby < D:
+            raise DGLError("segment_topk: sortby must be None or a column in [%d, %d), got %r" % (-D, D, sortby))
+        sortby = sortby % D
+    offsets, n = _segment_offsets(seglen, feat2d, total, "segment_topk")
+    return offsets, n, feat2d, sortby
+
+
+def segment_topk_fused(seglen, feat, k, sortby=None, descending=True, total=None):
+    """True when segment_topk(...) with these operands runs csrc/segtopk.hip (else the composition of sorts and gathers)."""
+    if (not torch.is_tensor(feat) or feat.dim() not in (1, 2) or feat.dtype != torch.float32 or not torch.is_tensor(seglen)
+            or (seglen.device != feat.device and seglen.device.type != "cpu") or isinstance(k, bool) or not isinstance(k, int) or k < 1
+            or not config.SEGMENT_TOPK_FUSED or feat.device.type not in sparse._BACKENDS or not _readout_kernels(feat)
+            or not hasattr(sparse.backend_for(feat), "segment_topk_fwd")):
+        return False
+    D = 1 if feat.dim() == 1 else int(feat.shape[1])
+    return (feat.shape[0] > 0 and seglen.shape[0] > 0 and D >= 1 and feat.shape[0] < 2 ** 31 and seglen.shape[0] * k < 2 ** 31
+            and (sortby is not None or seglen.shape[0] * D < 2 ** 31) and sparse.backend_for(feat).segment_topk_supported(k, D, sortby is None))
+
+
+def segment_topk(seglen, feat, k, sortby=None, descending=True, total=None):
+    """The k first rows of every consecutive row segment in sorted order (dgl.topk_nodes / topk_edges): (values, index).
+
+    feat [N, D] (fp32; [N] is taken as D = 1; may be a row-strided column block), seglen [S] segment lengths.
+      sortby = c (negative c counts from the last column): rows ordered by column c; values [S, k, D] are whole rows, index [S, k] int64
+               the row's number inside its segment
+      sortby = None: every column ordered on its own; values [S, k, D], index [S, k, D]
+    The order is torch.sort(key, stable=True, descending=descending) per segment: NaN is the greatest key, -0.0 == +0.0, equal keys keep
+    the lower row first in both directions; values are copies of the input bits.  A segment shorter than k is padded with zero values
+    and index -1 (DGL leaves those indices unspecified; -1 is this package's choice).  Gradients flow to `feat` through `values` (each
+    selected row or element receives its rank's gradient, everything else zero); `index` is not differentiable.
+    `total`: the row count when the caller knows it (no read-back of device lengths).  Device operands with k <= 1024 run
+    csrc/segtopk.hip, one launch each way (segment_topk_fused); everything else -- CPU tensors under a registered CPU backend, larger k,
+    config.SEGMENT_TOPK_FUSED = False -- is two stable sorts and gathers in torch operators."""
+    offsets, n, feat2d, sortby = _segment_topk_args(seglen, feat, k, sortby, total)
+    if segment_topk_fused(seglen, feat, k, sortby, descending, n):
+        return SegmentTopk.apply(feat2d, offsets, k, sortby, bool(descending))
+    sparse.backend_for(feat)  # no CPU backend: DGLError
+    return _segment_topk_composed(offsets, feat2d, k, sortby, descending, n)
 
 
 def segment_broadcast(seglen, value, total):

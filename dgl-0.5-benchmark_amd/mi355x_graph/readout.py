@@ -2,12 +2,13 @@
 broadcast for nodes and for edges.  A graph of the batch is a contiguous slice of rows (batch_num_nodes() / batch_num_edges()), so every
 function is one segment operator of ops.py: segment_reduce (csrc/segment.hip), segment_softmax (csrc/segattn.hip) or a row gather.  An
 unbatched graph is one segment.  The layers built on them are in nn.py (GlobalAttentionPooling, Set2Set, WeightAndSum); the fused
-attention readout those layers use is ops.segment_attention."""
+attention readout those layers use is ops.segment_attention.  topk_nodes / topk_edges select rows: ops.segment_topk (csrc/segtopk.hip),
+which nn.SortPooling is built on."""
 from ._lib import DGLError
 from . import ops
 
-__all__ = ["readout_nodes", "sum_nodes", "mean_nodes", "max_nodes", "softmax_nodes", "broadcast_nodes",
-           "readout_edges", "sum_edges", "mean_edges", "max_edges", "softmax_edges", "broadcast_edges"]
+__all__ = ["readout_nodes", "sum_nodes", "mean_nodes", "max_nodes", "softmax_nodes", "broadcast_nodes", "topk_nodes",
+           "readout_edges", "sum_edges", "mean_edges", "max_edges", "softmax_edges", "broadcast_edges", "topk_edges"]
 
 _READOUT_OPS = ("sum", "mean", "max", "min")
 
@@ -45,6 +46,11 @@ def _broadcast(graph, kind, graph_feat, type_):
     return ops.segment_broadcast(seglen, graph_feat, total)
 
 
+def _topk(graph, kind, feat, k, descending, sortby, type_):
+    seglen, frame, total = _rows(graph, kind, type_)
+    return ops.segment_topk(seglen, frame[feat], k, sortby=sortby, descending=descending, total=total)
+
+
 # ---- nodes
 def readout_nodes(graph, feat, weight=None, *, op="sum", ntype=None):
     """Per-graph `op` (sum, mean, max, min) of the node feature `feat`, multiplied by the node feature `weight` first: [B, ...]."""
@@ -73,6 +79,14 @@ def broadcast_nodes(graph, graph_feat, *, ntype=None):
     return _broadcast(graph, "nodes", graph_feat, ntype)
 
 
+def topk_nodes(graph, feat, k, *, descending=True, sortby=None, ntype=None):
+    """The k first nodes of every graph by the node feature `feat` [N, D] (dgl.topk_nodes): (values [B, k, D], index).  With `sortby` (a
+    column; negative counts from the last) whole rows are ordered by that column and index is [B, k]; without, every column is ordered on
+    its own and index is [B, k, D].  The order is a stable sort's (ties keep the lower node first, NaN is the greatest value); a graph
+    with fewer than k nodes is padded with zero rows, whose index is -1 (DGL leaves it unspecified)."""
+    return _topk(graph, "nodes", feat, k, descending, sortby, ntype)
+
+
 # ---- edges
 def readout_edges(graph, feat, weight=None, *, op="sum", etype=None):
     """Per-graph `op` (sum, mean, max, min) of the edge feature `feat`, multiplied by the edge feature `weight` first: [B, ...]."""
@@ -99,3 +113,8 @@ def softmax_edges(graph, feat, *, etype=None):
 def broadcast_edges(graph, graph_feat, *, etype=None):
     """Row g of `graph_feat` [B, ...] repeated for every edge of graph g: [E, ...]."""
     return _broadcast(graph, "edges", graph_feat, etype)
+
+
+def topk_edges(graph, feat, k, *, descending=True, sortby=None, etype=None):
+    """topk_nodes over the edges of every graph by the edge feature `feat` (dgl.topk_edges)."""
+    return _topk(graph, "edges", feat, k, descending, sortby, etype)

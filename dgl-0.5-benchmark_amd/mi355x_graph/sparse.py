@@ -1194,6 +1194,42 @@ class HipBackend(object):
                                                             _ptr(d_logits), _ptr(d_query), _stream(dev)))
         return d_feat, d_logits, d_query
 
+    # ---- segment top-k (csrc/segtopk.hip): nothing here reads `offsets` on the host either
+    @classmethod
+    def segment_topk_supported(cls, k, D, columns):
+        """Shapes mgx_segment_topk_* takes: 1 <= k <= 1024, any D >= 1."""
+        return bool(_lib.lib().mgx_segment_topk_supported(int(k), int(D), 1 if columns else 0))
+
+    def segment_topk_fwd(self, offsets, feat2d, k, sortby, descending):
+        """feat2d [N, D] (a column block of a wider matrix is taken as it is), sortby a column in [0, D) or None (every column on its
+        own) -> (values [S, k, D], index int64 [S, k] | [S, k, D], slot int32 [N] | [N, D])."""
+        dev = self._check_dev(offsets, feat2d)
+        S, N, D = offsets.shape[0] - 1, int(feat2d.shape[0]), int(feat2d.shape[1])
+        columns = sortby is None
+        if not (feat2d.stride(1) == 1 and feat2d.stride(0) >= D) and N > 0:  # a stride the kernel cannot take becomes a dense copy
+            feat2d = feat2d.contiguous()
+        ld = int(feat2d.stride(0)) if N > 0 else D
+        values = torch.empty((S, k, D), dtype=torch.float32, device=dev)
+        index = torch.empty((S, k, D) if columns else (S, k), dtype=torch.int64, device=dev)
+        slot = torch.empty((N, D) if columns else (N,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="seg_topk_fwd", k=int(k), D=D, segments=int(S), rows=N,
+                                                mode="columns" if columns else "rows"):
+            _lib.check(_lib.lib().mgx_segment_topk_fwd(S, _ptr(offsets), N, D, ld, _ptr(feat2d), int(k), 1 if columns else 0,
+                                                       0 if columns else int(sortby), 1 if descending else 0, _ptr(values), _ptr(index),
+                                                       _ptr(slot), _stream(dev)))
+        return values, index, slot
+
+    def segment_topk_bwd(self, slot, d_values, D):
+        """slot int32 [N] | [N, D], d_values [S, k, D] -> d_feat [N, D]: a gather, every element written once."""
+        dev = self._check_dev(slot, d_values)
+        N = int(slot.shape[0])
+        d_values = d_values.contiguous()
+        d_feat = torch.empty((N, D), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="seg_topk_bwd", D=int(D), rows=N, mode="columns" if slot.dim() == 2 else "rows"):
+            _lib.check(_lib.lib().mgx_segment_topk_bwd(N, int(D), 1 if slot.dim() == 2 else 0, _ptr(slot), _ptr(d_values), _ptr(d_feat),
+                                                       _stream(dev)))
+        return d_feat
+
     @staticmethod
     def _row_strided(t):
         return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 4 == 0 and t.shape[1] % 4 == 0

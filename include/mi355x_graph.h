@@ -710,6 +710,35 @@ int32_t mgx_segment_attention_bwd(int64_t num_segments, const int64_t* offsets, 
                                   const float* d_out, const float* stat, float* d_feat, float* d_logits, float* d_query,
                                   void* stream);
 
+/* ------------------------------------------------------------------ graph readout: segment top-k (csrc/segtopk.hip)
+ * dgl.topk_nodes / topk_edges and the selection of dgl.nn.SortPooling over the segments described above (offsets int64
+ * [num_segments+1] on the device; segment s = rows offsets[s] .. offsets[s+1]).  feat [N, ld] fp32, the first D floats of a row are the
+ * operand (ld >= D, no alignment asked).  Everything is a copy: outputs hold input BITS.
+ *
+ * Order inside a segment = torch.sort(key, stable=True, descending=...) on the CPU: NaN is the greatest key (first when descending,
+ * last when ascending; a NaN with the sign bit set is a NaN too), -0.0 == +0.0, equal keys keep the lower row first in both
+ * directions.
+ *   mode 0 (rows):    key = column `sortby` in [0, D);  values[s, j, :] = the whole row of rank j,  index[s, j] = its row number
+ *                     INSIDE the segment (int64);  values [S, k, D], index [S, k], slot [N]
+ *   mode 1 (columns): every column ranked on its own (`sortby` ignored);  values[s, j, c], index[s, j, c];
+ *                     values [S, k, D], index [S, k, D], slot [N, D]
+ * A segment shorter than k: ranks j >= len hold zero values and index -1.
+ * slot (int32) is the inverse map: the flat output rank s*k + j of a selected row (mode 0) or element (mode 1), -1 for one not
+ * selected.  The forward writes every output element and all of slot: no memset is needed.
+ *   bwd: d_feat[i, c] = slot >= 0 ? d_values[slot, c] : 0 with slot = slot[i] (mode 0) or slot[i, c] (mode 1); d_values [S*k, D] and
+ *        d_feat [N, D] dense.  A pure gather that writes every element of d_feat once, one launch.
+ * Supported (mgx_segment_topk_supported(k, D, mode); everything else is MGX_ERR_UNSUPPORTED and the caller composes sorts and
+ * gathers): 1 <= k <= 1024, any D >= 1, segments shorter than 2^32 - 1, N < 2^31, num_segments * k < 2^31 (mode 1: num_segments * D
+ * < 2^31).  k <= 64: one wave per segment (mode 1: per segment and column); larger k: one 256-thread workgroup with 16 KB of LDS.
+ * One wave / workgroup walks a segment whatever its length.  Nothing is read back to the host: capture-safe.
+ * Deterministic: no atomics.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_segment_topk_supported(int64_t k, int64_t D, int32_t mode);
+int32_t mgx_segment_topk_fwd(int64_t num_segments, const int64_t* offsets, int64_t N, int64_t D, int64_t ld, const float* feat, int64_t k,
+                             int32_t mode, int64_t sortby, int32_t descending, float* values, int64_t* index, int32_t* slot,
+                             void* stream);
+int32_t mgx_segment_topk_bwd(int64_t N, int64_t D, int32_t mode, const int32_t* slot, const float* d_values, float* d_feat,
+                             void* stream);
+
 /* ------------------------------------------------------------------ formats (integer, bit-exact)
  * Replace the lazy COO->CSR/CSC construction behind g.formats(...)/first kernel call
  * (main_dgl_product_sage.py:158, kernel/dgl-new.py:63) and g.in_degrees()
