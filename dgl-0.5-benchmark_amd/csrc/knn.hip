@@ -1,0 +1,185 @@
+// knn.hip -- k nearest neighbours inside the contiguous row segments of a batch of point clouds (gfx950 / MI355X): dgl.knn_graph /
+// segmented_knn_graph and the graph dgl.nn.EdgeConv models rebuild before every layer.  Distances and selection in ONE walk: no
+// [n, n] distance matrix is written.
+//
+//   distance   d(i, j) = sum_c (x[i,c] - x[j,c])^2 over c ascending, one fp32 fma per term: the DIRECT difference form (the expansion
+//              |x_i|^2 + |x_j|^2 - 2 x_i.x_j cancels for clouds far from the origin).  Every j of i's segment, i itself included.
+//   order      (d, j) ascending: equal distances keep the lower row first, a NaN distance is the greatest key (one canonical NaN, so
+//              NaNs tie).  The pair is pack_pair(d, j - offsets[s]) of wave_select.h, compared as one 64-bit integer.
+//   outputs    index int64 [N, k]: global row numbers; dist fp32 [N, k] (optional).  A segment shorter than k: ranks >= len hold index
+//              -1 and dist +inf.  Every element is written: no memset.
+//
+// One 256-thread workgroup takes 16 consecutive query rows, four per wave.  The candidates of the union of their segments (a contiguous
+// row range: segments are consecutive) stream through LDS 64 rows at a time and 32 columns per pass, stored column-major with a row of
+// 65 floats: the transposing stores are at most 2-way conflicted, lane j then reads candidate j at consecutive addresses and that ONE LDS
+// read feeds four queries.  The query's own coordinates come from wave-uniform addresses (scalar loads).  A candidate outside a query's
+// own segment is kNoPair.  Each query keeps its 64 best pairs one per lane, ascending; a chunk in which no lane beats the current k-th is
+// skipped on a ballot; up to 8 lanes that do (the common case past a segment's first chunks: about k / i candidates of chunk i) are inserted
+// one at a time -- a ballot against the sorted best gives the place, the lanes above it shift up by one -- else wave_sort +
+// wave_bitonic_merge as in the wave form of segtopk.hip.  Only ranks below k are exact in either path: a skipped chunk may have held ranks
+// k .. 63.  A wave whose four segments do not meet the chunk skips the arithmetic (never the barriers).
+// Nothing is read on the host and the launch depends on N only: capture-safe.  No atomics: reruns are bitwise equal.
+#include "wave_select.h"
+
+namespace mgx {
+
+constexpr int kKnnMaxK = kWave;  // one rank per lane
+constexpr int kKnnMaxD = 256;
+constexpr int kKnnQueries = 16;  // query rows per workgroup
+constexpr int kKnnPerWave = kKnnQueries / kWavesPerBlock;
+constexpr int kKnnCols = 32;     // columns staged per pass
+constexpr int kKnnTileLd = kWave + 1;
+constexpr int kKnnInsertMax = 8;  // candidates of a chunk under the current k-th that are inserted one by one; more: sort and merge
+
+__global__ __launch_bounds__(kBlock) void segment_knn_kernel(int64_t S, const int64_t* __restrict__ offsets, int64_t N, int D, int64_t ld,
+                                                             const float* __restrict__ x, int k, int64_t* __restrict__ index,
+                                                             float* __restrict__ dist) {
+  __shared__ float tile[kKnnCols * kKnnTileLd];
+  __shared__ int64_t sbeg[kKnnQueries], send[kKnnQueries];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1);
+  const int w = __builtin_amdgcn_readfirstlane(tid / kWave);
+  const int64_t q0 = (int64_t)blockIdx.x * kKnnQueries;
+  if (tid < kKnnQueries) {  // the segment of query row q0 + tid: the last s with offsets[s] <= row, clamped to the N rows there are
+    const int64_t row = q0 + tid;
+    int64_t beg = 0, end = 0;
+    if (row < N) {
+      int64_t lo = 0, hi = S + 1;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (offsets[mid] > row) hi = mid; else lo = mid + 1;
+      }
+      if (lo >= 1 && lo <= S) {
+        beg = offsets[lo - 1];
+        end = offsets[lo];
+      }
+      end = end < N ? end : N;
+      beg = beg < 0 ? 0 : beg;
+      if (!(beg <= row && row < end)) beg = end = 0;  // a row no segment holds: k ranks of padding
+    }
+    sbeg[tid] = beg;
+    send[tid] = end;
+  }
+  __syncthreads();
+  int64_t lo = N, hi = 0;  // the rows the workgroup streams
+#pragma unroll
+  for (int q = 0; q < kKnnQueries; ++q) {
+    const int64_t b = sbeg[q], e = send[q];
+    if (b < e) {
+      lo = b < lo ? b : lo;
+      hi = e > hi ? e : hi;
+    }
+  }
+  int64_t qbeg[kKnnPerWave], qend[kKnnPerWave], wlo = N, whi = 0;  // ... and the rows this wave has a use for
+  const float* xq[kKnnPerWave];
+  uint64_t best[kKnnPerWave];
+#pragma unroll
+  for (int q = 0; q < kKnnPerWave; ++q) {
+    qbeg[q] = sbeg[w * kKnnPerWave + q];
+    qend[q] = send[w * kKnnPerWave + q];
+    if (qbeg[q] < qend[q]) {
+      wlo = qbeg[q] < wlo ? qbeg[q] : wlo;
+      whi = qend[q] > whi ? qend[q] : whi;
+    }
+    const int64_t row = q0 + w * kKnnPerWave + q;
+    xq[q] = x + (row < N ? row : N - 1) * ld;
+    best[q] = kNoPair;
+  }
+  for (int64_t c0 = lo; c0 < hi; c0 += kWave) {
+    const int rows = hi - c0 < kWave ? (int)(hi - c0) : kWave;
+    const bool mine = c0 < whi && c0 + kWave > wlo;  // wave-uniform
+    float acc[kKnnPerWave];
+#pragma unroll
+    for (int q = 0; q < kKnnPerWave; ++q) acc[q] = 0.f;
+    for (int d0 = 0; d0 < D; d0 += kKnnCols) {
+      const int dc = D - d0 < kKnnCols ? D - d0 : kKnnCols;
+      __syncthreads();  // the previous tile has been read
+      if (dc == kKnnCols) {
+        const int c = tid & (kKnnCols - 1);
+#pragma unroll
+        for (int r = tid / kKnnCols; r < kWave; r += kBlock / kKnnCols)
+          tile[c * kKnnTileLd + r] = r < rows ? x[(c0 + r) * ld + d0 + c] : 0.f;
+      } else {
+        for (int e = tid; e < kWave * dc; e += kBlock) {
+          const int r = e / dc, c = e - r * dc;
+          tile[c * kKnnTileLd + r] = r < rows ? x[(c0 + r) * ld + d0 + c] : 0.f;
+        }
+      }
+      __syncthreads();
+      if (!mine) continue;
+#pragma unroll 8
+      for (int c = 0; c < dc; ++c) {
+        const float v = tile[c * kKnnTileLd + lane];
+#pragma unroll
+        for (int q = 0; q < kKnnPerWave; ++q) {
+          const float diff = xq[q][d0 + c] - v;
+          acc[q] = __builtin_fmaf(diff, diff, acc[q]);
+        }
+      }
+    }
+    if (!mine) continue;
+    const int64_t g = c0 + lane;
+#pragma unroll
+    for (int q = 0; q < kKnnPerWave; ++q) {
+      float d = acc[q];
+      if (d != d) d = __uint_as_float(0x7FC00000u);  // every NaN is the one positive NaN: above +inf, ties by row
+      const uint64_t cand = (g >= qbeg[q] && g < qend[q]) ? pack_pair(d, (uint64_t)(g - qbeg[q])) : kNoPair;
+      const uint64_t kth = __shfl(best[q], k - 1, kWave);
+      uint64_t pass = __ballot(cand < kth);
+      if (pass == 0) continue;  // nothing in this chunk beats the current k-th
+      if (__popcll(pass) <= kKnnInsertMax) {  // a few: each goes to its place among the sorted best, the lanes above move up by one
+        do {
+          const int l = __builtin_ctzll(pass);  // wave-uniform
+          const uint64_t v = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(cand >> 32), l) << 32) |
+                             (uint32_t)__builtin_amdgcn_readlane((int)(cand & 0xFFFFFFFFull), l);
+          const int pos = __popcll(__ballot(best[q] < v));  // pairs are distinct; best is ascending: lanes 0 .. pos-1 stay
+          const uint64_t up = __shfl_up(best[q], 1, kWave);
+          best[q] = lane < pos ? best[q] : (lane == pos ? v : up);
+          pass &= pass - 1;
+        } while (pass);
+        continue;
+      }
+      const uint64_t sorted = wave_sort(cand, lane);
+      const uint64_t rev = __shfl(sorted, kWave - 1 - lane, kWave);
+      best[q] = wave_bitonic_merge(rev < best[q] ? rev : best[q], lane);  // the 64 smallest of both, as a bitonic sequence, sorted
+    }
+  }
+  if (lane < k) {
+#pragma unroll
+    for (int q = 0; q < kKnnPerWave; ++q) {
+      const int64_t row = q0 + w * kKnnPerWave + q;
+      if (row >= N) continue;
+      const uint64_t p = best[q];
+      const uint32_t b = (uint32_t)(p >> 32);
+      index[row * k + lane] = p == kNoPair ? (int64_t)-1 : qbeg[q] + (int64_t)(p & 0xFFFFFFFFull);
+      if (dist) dist[row * k + lane] = p == kNoPair ? __uint_as_float(0x7F800000u) : __uint_as_float((b >> 31) ? b ^ 0x80000000u : ~b);
+    }
+  }
+}
+
+static bool knn_shape_ok(int64_t k, int64_t D) { return k >= 1 && k <= kKnnMaxK && D >= 1 && D <= kKnnMaxD; }
+
+}  // namespace mgx
+
+extern "C" int32_t mgx_segment_knn_supported(int64_t k, int64_t D) { return mgx::knn_shape_ok(k, D); }
+
+extern "C" int32_t mgx_segment_knn(int64_t num_segments, const int64_t* offsets, int64_t N, int64_t D, int64_t ld, const float* x, int64_t k,
+                                   int64_t* index, float* dist, void* stream) {
+  using namespace mgx;
+  MGX_ENTER();
+  const char* who = "mgx_segment_knn";
+  MGX_CHECK_ARG(num_segments >= 0 && N >= 0, "%s: negative num_segments or N", who);
+  MGX_CHECK_ARG(D >= 1 && ld >= D, "%s: needs D >= 1 and a row stride of at least D (got D = %lld, ld = %lld)", who, (long long)D, (long long)ld);
+  MGX_CHECK_ARG(k >= 1, "%s: k must be at least 1, got %lld", who, (long long)k);
+  if (!knn_shape_ok(k, D)) MGX_UNSUPPORTED("%s: k = %lld beyond %d or D = %lld beyond %d", who, (long long)k, kKnnMaxK, (long long)D, kKnnMaxD);
+  const int64_t lim = int64_t(1) << 31;
+  if (N >= lim || num_segments >= lim || ld >= lim || N * ld >= lim / 2)
+    MGX_UNSUPPORTED("%s: needs N and num_segments below 2^31 and x below 4 GiB (got N = %lld, num_segments = %lld, ld = %lld)", who,
+                    (long long)N, (long long)num_segments, (long long)ld);
+  if (N == 0) return MGX_OK;
+  MGX_CHECK_ARG(offsets && x && index, "%s: offsets / x / index is NULL", who);
+  const dim3 grid((unsigned)((N + kKnnQueries - 1) / kKnnQueries));
+  hipLaunchKernelGGL(segment_knn_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, num_segments, offsets, N, (int)D, ld, x, (int)k, index,
+                     dist);
+  MGX_CHECK_LAUNCH();
+  return MGX_OK;
+}

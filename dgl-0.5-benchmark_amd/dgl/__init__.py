@@ -5,7 +5,7 @@ Put the directory that contains this package on PYTHONPATH to use it."""
 from mi355x_graph import DGLError, DGLGraph, DGLHeteroGraph, graph, create_block, ALL  # noqa: F401
 from mi355x_graph import heterograph, bipartite, hetero_from_relations  # noqa: F401
 from mi355x_graph.transform import (to_bidirected, add_self_loop, remove_self_loop, add_reverse_edges,  # noqa: F401
-                                    reverse, from_networkx, from_scipy, batch, unbatch)
+                                    reverse, from_networkx, from_scipy, batch, unbatch, knn_graph, segmented_knn_graph)
 from mi355x_graph import function, ops, readout  # noqa: F401
 from mi355x_graph.readout import (readout_nodes, sum_nodes, mean_nodes, max_nodes, softmax_nodes, broadcast_nodes,  # noqa: F401
                                   readout_edges, sum_edges, mean_edges, max_edges, softmax_edges, broadcast_edges, topk_nodes, topk_edges)

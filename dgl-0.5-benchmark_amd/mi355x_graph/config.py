@@ -45,6 +45,11 @@ SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: seg
 # ---- segment top-k (ops.segment_topk, readout.topk_nodes / topk_edges, nn.SortPooling)
 SEGMENT_TOPK_FUSED = True  # csrc/segtopk.hip, one launch each way; False: two stable sorts and gathers in torch operators
 
+# ---- point clouds (ops.segment_knn, transform.knn_graph / segmented_knn_graph, nn.EdgeConv)
+KNN_FUSED = True       # csrc/knn.hip: distances and selection in one launch; False: a stable sort of direct-form distances per segment in torch operators
+EDGECONV_FUSED = True  # EdgeConv without batch norm as theta GEMM over nodes -> copy_u / max -> + x (phi - theta)^T: no E-sized tensor; False:
+                       # u_sub_v -> the two Linears over edges -> copy_e / max
+
 # ---- sampled blocks and induced subgraphs (sampling.to_block, sampling.node_subgraph)
 DEVICE_BLOCKS = True    # the relabelling kernels of csrc/relabel.hip; False: look-up table -> unique -> gathers -> bincount + cumsum in torch ops
 DEVICE_SUBGRAPH = True  # a wave per selected row of a materialised in-CSR (csrc/relabel.hip); False: the look-up table gathered at both ends of every parent edge

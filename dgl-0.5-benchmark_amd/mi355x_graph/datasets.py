@@ -256,3 +256,50 @@ class Subset(object):
 
     def __len__(self):
         return len(self.indices)
+
+
+POINT_SHAPES = ("sphere", "cube", "cylinder", "torus", "cone", "plane", "helix", "saddle")
+
+
+def shapes_like(num_clouds=2048, points=1024, seed=11, noise=0.02):
+    """Point-cloud classification stand-in (the role of ModelNet40 in the DGCNN example): every cloud is `points` samples of one of
+    eight parametric surfaces / curves (POINT_SHAPES), randomly scaled per axis, rotated about z and perturbed by Gaussian noise.
+    Returns (xyz float32 [num_clouds, points, 3], label int64 [num_clouds]); seeded, generated on the host."""
+    rng = np.random.default_rng(seed)
+    label = rng.integers(0, len(POINT_SHAPES), num_clouds)
+    u = rng.random((num_clouds, points)) * 2 * np.pi
+    v = rng.random((num_clouds, points)) * 2 - 1
+    w = rng.random((num_clouds, points)) * 2 - 1
+    xyz = np.zeros((num_clouds, points, 3))
+    for c, name in enumerate(POINT_SHAPES):
+        m = label == c
+        a, b, t = u[m], v[m], w[m]
+        if name == "sphere":
+            r = np.sqrt(1 - b * b)
+            p = (r * np.cos(a), r * np.sin(a), b)
+        elif name == "cube":
+            face = (np.abs(t) * 3).astype(np.int64) % 3
+            side = np.sign(t) + (t == 0)
+            q = np.stack([np.cos(a), b, side], -1)
+            p = tuple(np.take_along_axis(q, ((face + i) % 3)[..., None], -1)[..., 0] for i in range(3))
+        elif name == "cylinder":
+            p = (0.6 * np.cos(a), 0.6 * np.sin(a), b)
+        elif name == "torus":
+            p = ((0.7 + 0.3 * np.cos(np.pi * b)) * np.cos(a), (0.7 + 0.3 * np.cos(np.pi * b)) * np.sin(a), 0.3 * np.sin(np.pi * b))
+        elif name == "cone":
+            h = (b + 1) / 2
+            p = (h * np.cos(a), h * np.sin(a), 1 - 2 * h)
+        elif name == "plane":
+            p = (b, t, 0 * b)
+        elif name == "helix":
+            p = (0.7 * np.cos(2 * a), 0.7 * np.sin(2 * a), a / np.pi - 1)
+        else:  # saddle
+            p = (b, t, b * b - t * t)
+        xyz[m] = np.stack(p, -1)
+    turn = rng.random(num_clouds) * 2 * np.pi
+    cs, sn = np.cos(turn)[:, None], np.sin(turn)[:, None]
+    x, y = xyz[..., 0] * cs - xyz[..., 1] * sn, xyz[..., 0] * sn + xyz[..., 1] * cs
+    xyz[..., 0], xyz[..., 1] = x, y
+    xyz *= rng.uniform(0.8, 1.25, (num_clouds, 1, 3))
+    xyz += rng.normal(0, noise, xyz.shape)
+    return torch.from_numpy(xyz.astype(np.float32)), torch.from_numpy(label.astype(np.int64))

@@ -7,6 +7,7 @@
   AvgPooling / SumPooling / MaxPooling   main_dgl_molhiv_gcn.py:75,93
   GlobalAttentionPooling / Set2Set / WeightAndSum   dgl.nn.pytorch.glob (attention readouts, fused: ops.segment_attention)
   SortPooling   dgl.nn.pytorch.glob (the DGCNN readout: ops.segment_topk)
+  KNNGraph / SegmentedKNNGraph   dgl.nn.pytorch.factory (ops.segment_knn);  EdgeConv   dgl.nn.pytorch.conv (point clouds)
 Parameter names, shapes and initialisation follow DGL v0.6.x so state_dicts and the scripts'
 reset_parameters() calls (main_dgl_reddit_gat.py:57-59) line up.
 """
@@ -657,6 +658,87 @@ class SortPooling(nn.Module):
 
     def extra_repr(self):
         return "k={k}".format(**self.__dict__)
+
+
+class KNNGraph(nn.Module):
+    """dgl.nn.KNNGraph: points [N, D] (one set) or [B, n, D] (B sets, node b * n + i) -> the graph in which every node's predecessors
+    are its k nearest points (transform.knn_graph: ops.segment_knn, whose index is the in-CSR).  No parameters."""
+
+    def __init__(self, k):
+        super(KNNGraph, self).__init__()
+        self.k = k
+
+    def forward(self, x):
+        from .transform import knn_graph
+        return knn_graph(x, self.k)
+
+    def extra_repr(self):
+        return "k={k}".format(**self.__dict__)
+
+
+class SegmentedKNNGraph(nn.Module):
+    """dgl.nn.SegmentedKNNGraph: points [N, D] in consecutive sets of segs[0], segs[1], ... points (transform.segmented_knn_graph)."""
+
+    def __init__(self, k):
+        super(SegmentedKNNGraph, self).__init__()
+        self.k = k
+
+    def forward(self, x, segs):
+        from .transform import segmented_knn_graph
+        return segmented_knn_graph(x, self.k, segs)
+
+    def extra_repr(self):
+        return "k={k}".format(**self.__dict__)
+
+
+class EdgeConv(nn.Module):
+    """dgl.nn.EdgeConv (Wang et al., Dynamic Graph CNN for Learning on Point Clouds), by upstream's documented formula:
+        out_i = max_{j -> i} [ theta(x_j - x_i) + phi(x_i) ]     per column; 0 for a node without in-edges
+    with theta, phi = Linear(in_feat, out_feat).  Without batch norm (config.EDGECONV_FUSED) the bracket is
+    x_j Theta^T + [x_i (Phi - Theta)^T + b_theta + b_phi], whose second part does not depend on j: a GEMM over the NODES, the
+    copy_u / max g-SpMM (gradient through its arg) and a second node GEMM -- no tensor of E rows exists in either direction.  With
+    batch_norm=True, or with the switch off, the literal composition: u_sub_v g-SDDMM, the two Linears, BatchNorm1d over the edges,
+    copy_e / max."""
+
+    def __init__(self, in_feat, out_feat, batch_norm=False, allow_zero_in_degree=False):
+        super(EdgeConv, self).__init__()
+        self.batch_norm = batch_norm
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.theta = Linear(in_feat, out_feat)
+        self.phi = Linear(in_feat, out_feat)
+        if batch_norm:
+            self.bn = BatchNorm1d(out_feat)
+
+    def set_allow_zero_in_degree(self, set_value):
+        self._allow_zero_in_degree = set_value
+
+    def forward(self, g, feat):
+        with g.local_scope():
+            zero_deg = _has_zero_in_degree(g)
+            if zero_deg and not self._allow_zero_in_degree:
+                raise DGLError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid. "
+                               "Adding self-loop on the input graph by calling `g = dgl.add_self_loop(g)` will "
+                               "resolve the issue. Setting ``allow_zero_in_degree`` to be `True` when constructing "
+                               "this module will suppress the check and let the code run.")
+            h_src, h_dst = expand_as_pair(feat, g)
+            if not self.batch_norm and config.EDGECONV_FUSED:
+                g.srcdata["y"] = F.linear(h_src, self.theta.weight)
+                g.update_all(fn.copy_u("y", "m"), fn.max("m", "m"))
+                rst = g.dstdata["m"] + ops.linear(h_dst, self.phi.weight - self.theta.weight, self.theta.bias + self.phi.bias)
+            else:
+                g.srcdata["x"], g.dstdata["x"] = h_src, h_dst
+                g.apply_edges(fn.u_sub_v("x", "x", "theta"))
+                g.edata["theta"] = self.theta(g.edata["theta"])
+                g.dstdata["phi"] = self.phi(h_dst)
+                g.apply_edges(fn.e_add_v("theta", "phi", "e"))
+                e = g.edata["e"]
+                g.edata["e"] = self.bn(e) if self.batch_norm else e
+                g.update_all(fn.copy_e("e", "m"), fn.max("m", "x"))
+                rst = g.dstdata["x"]
+            if zero_deg:
+                has = (g.in_degrees() > 0).view((-1,) + (1,) * (rst.dim() - 1))
+                rst = torch.where(has, rst, rst.new_zeros(()))
+            return rst
 
 
 class WeightAndSum(nn.Module):

@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -1996,6 +1996,87 @@ def segment_topk(seglen, feat, k, sortby=None, descending=True, total=None):
         return SegmentTopk.apply(feat2d, offsets, k, sortby, bool(descending))
     sparse.backend_for(feat)  # no CPU backend: DGLError
     return _segment_topk_composed(offsets, feat2d, k, sortby, descending, n)
+
+
+# ----------------------------------------------------------------------------- point clouds: segment k nearest neighbours
+_KNN_COMPOSED_ELEMS = 1 << 24  # the composition's [queries, len, D] difference tensor is built this many elements at a time
+
+
+def _segment_knn_composed(offsets, x, k, return_dist):
+    """ops.segment_knn through torch operators, by the same definition: per segment the direct-form distances sum_c (x_i - x_j)^2 and a
+    stable sort of every query's row of them (NaN greatest, equal distances keep the lower row); index -1 and dist +inf past a
+    segment's end.  One read-back of the offsets, a loop over segments.  The form for CPU tensors, for k > 64 or D > 256, under
+    MGX_TORCH_OPS=1 and with config.KNN_FUSED off."""
+    N, D = int(x.shape[0]), int(x.shape[1])
+    index = torch.full((N, k), -1, dtype=torch.int64, device=x.device)
+    dist = torch.full((N, k), float("inf"), dtype=torch.float32, device=x.device) if return_dist else None
+    with torch.no_grad():
+        ends = offsets.tolist()
+        for beg, end in zip(ends[:-1], ends[1:]):
+            n = end - beg
+            if n <= 0:
+                continue
+            seg, m = x[beg:end], min(k, n)
+            step = max(1, _KNN_COMPOSED_ELEMS // (n * D))
+            for q in range(0, n, step):
+                diff = seg[q:q + step].unsqueeze(1) - seg.unsqueeze(0)                          # [queries, n, D]
+                d = (diff * diff).sum(-1)
+                d = torch.where(d != d, d.new_full((), float("nan")), d)
+                order = torch.sort(d, dim=1, stable=True)
+                rows = slice(beg + q, beg + min(q + step, n))
+                index[rows, :m] = order.indices[:, :m] + beg
+                if return_dist:
+                    dist[rows, :m] = order.values[:, :m]
+    return index, dist
+
+
+def _segment_knn_args(seglen, x, k, total):
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise DGLError("segment_knn: expected x [N, D], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    if x.dtype != torch.float32:
+        raise DGLError("segment_knn expects float32 input, got %s" % (x.dtype,))
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise DGLError("segment_knn: k must be an integer >= 1, got %r" % (k,))
+    if torch.is_tensor(seglen) and seglen.device != x.device and seglen.device.type != "cpu":  # host lengths go with any x
+        raise DGLError("segment_knn: operands on different devices: %s vs %s" % (x.device, seglen.device))
+    if x.shape[1] < 1:
+        raise DGLError("segment_knn: x has no columns")
+    return _segment_offsets(seglen, x, total, "segment_knn")
+
+
+def segment_knn_fused(seglen, x, k, total=None, return_dist=False):
+    """True when segment_knn(...) with these operands runs csrc/knn.hip (else the composition of distances and a stable sort)."""
+    if (not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not torch.is_tensor(seglen)
+            or (seglen.device != x.device and seglen.device.type != "cpu") or isinstance(k, bool) or not isinstance(k, int) or k < 1
+            or not config.KNN_FUSED or x.device.type not in sparse._BACKENDS or not _readout_kernels(x)
+            or not hasattr(sparse.backend_for(x), "segment_knn")):
+        return False
+    N, D = int(x.shape[0]), int(x.shape[1])
+    ld = int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= D else D
+    return (N > 0 and D >= 1 and N < 2 ** 31 and seglen.shape[0] < 2 ** 31 and N * ld < 2 ** 30
+            and sparse.backend_for(x).segment_knn_supported(k, D))
+
+
+def segment_knn(seglen, x, k, total=None, return_dist=False):
+    """The k nearest rows of every row inside its own consecutive row segment (dgl.knn_graph / segmented_knn_graph): index int64 [N, k],
+    or (index, dist [N, k]) with return_dist.
+
+    x [N, D] (fp32; may be a row-strided column block), seglen [S] segment lengths.  d(i, j) = sum_c (x[i,c] - x[j,c])^2 in fp32, the
+    direct difference form, over every j of i's segment, i included; neighbours are ordered by (d, j) ascending, so equal distances
+    keep the lower row first and rank 0 of a finite point is itself or a lower-numbered duplicate; a NaN distance is the greatest
+    key.  index holds global row numbers of x.  A segment shorter than k is padded with index -1 and dist +inf.  Neither output is
+    differentiable: `index` is a selection, and `dist` is returned detached (no gradient flows to x through it).
+    `total`: the row count when the caller knows it (no read-back of device lengths).  Device operands with k <= 64 and D <= 256 run
+    csrc/knn.hip in one launch that writes no [n, n] matrix (segment_knn_fused); everything else -- CPU tensors under a registered CPU
+    backend, larger k or D, config.KNN_FUSED = False -- is a stable sort of the distances per segment in torch operators."""
+    offsets, n = _segment_knn_args(seglen, x, k, total)
+    if segment_knn_fused(seglen, x, k, n, return_dist):
+        with torch.no_grad():
+            index, dist = sparse.backend_for(x).segment_knn(offsets, x.detach(), k, return_dist)
+    else:
+        sparse.backend_for(x)  # no CPU backend: DGLError
+        index, dist = _segment_knn_composed(offsets, x.detach(), k, return_dist)
+    return (index, dist) if return_dist else index
 
 
 def segment_broadcast(seglen, value, total):

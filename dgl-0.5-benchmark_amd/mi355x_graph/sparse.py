@@ -1230,6 +1230,25 @@ class HipBackend(object):
                                                        _stream(dev)))
         return d_feat
 
+    # ---- segment k nearest neighbours (csrc/knn.hip)
+    @classmethod
+    def segment_knn_supported(cls, k, D):
+        """Shapes mgx_segment_knn takes: 1 <= k <= 64, 1 <= D <= 256."""
+        return bool(_lib.lib().mgx_segment_knn_supported(int(k), int(D)))
+
+    def segment_knn(self, offsets, x2d, k, return_dist):
+        """x2d [N, D] (a column block of a wider matrix is taken as it is) -> (index int64 [N, k], dist [N, k] | None)."""
+        dev = self._check_dev(offsets, x2d)
+        S, N, D = offsets.shape[0] - 1, int(x2d.shape[0]), int(x2d.shape[1])
+        if not (x2d.stride(1) == 1 and x2d.stride(0) >= D) and N > 0:  # a stride the kernel cannot take becomes a dense copy
+            x2d = x2d.contiguous()
+        ld = int(x2d.stride(0)) if N > 0 else D
+        index = torch.empty((N, k), dtype=torch.int64, device=dev)
+        dist = torch.empty((N, k), dtype=torch.float32, device=dev) if return_dist else None
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_knn", k=int(k), D=D, segments=int(S), rows=N):
+            _lib.check(_lib.lib().mgx_segment_knn(S, _ptr(offsets), N, D, ld, _ptr(x2d), int(k), _ptr(index), _ptr(dist), _stream(dev)))
+        return index, dist
+
     @staticmethod
     def _row_strided(t):
         return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 4 == 0 and t.shape[1] % 4 == 0

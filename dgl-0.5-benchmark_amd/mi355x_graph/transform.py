@@ -264,6 +264,59 @@ def unbatch(g):
     return out
 
 
+def _knn_graph_of(x2d, k, lens, who):
+    """The graph of N nodes and N * k edges whose edge i * k + j runs from the j-th nearest neighbour of row i (inside i's segment,
+    i itself first) to i: ops.segment_knn's index IS the in-CSR (indptr = arange(N + 1) * k, no edge-id permutation), so no sort or
+    COO -> CSR pass runs.  `lens`: the segment lengths, known on the host."""
+    from . import ops
+    from .sparse import CsrView
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise DGLError("%s: k must be an integer >= 1, got %r" % (who, k))
+    if not torch.is_tensor(x2d) or not x2d.dtype.is_floating_point:
+        raise DGLError("%s expects a floating-point tensor of points" % who)
+    lens = [int(n) for n in lens]
+    N = int(x2d.shape[0])
+    if any(n < 0 for n in lens) or sum(lens) != N:
+        raise DGLError("%s: segment lengths %s do not sum to the %d points" % (who, lens if len(lens) <= 8 else lens[:8] + ["..."], N))
+    short = [n for n in lens if n < k]
+    if short:
+        raise DGLError("%s: a segment of %d points has no %d nearest neighbours (every segment needs at least k points)" % (who, short[0], k))
+    if len(set(lens)) == 1:  # equal sets (knn_graph of [B, n, D]): the lengths are filled in on the device, no host-to-device copy
+        seglen = torch.full((len(lens),), lens[0], dtype=torch.int64, device=x2d.device)
+    else:
+        seglen = torch.tensor(lens, dtype=torch.int64)
+    index = ops.segment_knn(seglen, x2d.detach().float(), k, total=N)
+    idtype = torch.int32 if N * k < 2 ** 31 else torch.int64
+    indptr = torch.arange(N + 1, dtype=idtype, device=x2d.device) * k
+    csc = CsrView(N, N, indptr, index.reshape(-1).to(idtype), None)
+    if k <= 256:
+        csc._plan = None  # every row has k entries: nothing to split or balance, and no host read of the lengths
+    idx = GraphIndex(N, N, csc=csc)
+    idx.max_in_degree_hint = k
+    idx.ephemeral = True  # rebuilt before every layer of every step
+    idx._mark_ephemeral(csc)
+    idx._zero_in_deg = False
+    return DGLGraph(idx)
+
+
+def knn_graph(x, k):
+    """dgl.knn_graph: x [N, D] is one set of points, x [B, n, D] is B sets of n points whose nodes are numbered b * n + i.  Every node's
+    predecessors are its k nearest points of its own set (squared Euclidean distance, itself included, ties to the lower point)."""
+    if not torch.is_tensor(x) or x.dim() not in (2, 3):
+        raise DGLError("knn_graph: expected points [N, D] or [B, n, D], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    if x.dim() == 2:
+        return _knn_graph_of(x, k, [x.shape[0]], "knn_graph")
+    return _knn_graph_of(x.reshape(-1, x.shape[2]), k, [x.shape[1]] * x.shape[0], "knn_graph")
+
+
+def segmented_knn_graph(x, k, segs):
+    """dgl.segmented_knn_graph: x [N, D] holds consecutive sets of segs[0], segs[1], ... points (a Python list of lengths); every
+    node's predecessors are its k nearest points of its own set."""
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise DGLError("segmented_knn_graph: expected points [N, D], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    return _knn_graph_of(x, k, list(segs), "segmented_knn_graph")
+
+
 def metis_partition_assignment(g, k, balance_ntypes=None, balance_edges=False):
     """k-way edge-cut node partition -> [N] part ids.  The role of dgl.transform.metis_partition_assignment
     (end_to_end/sampling/link-prediction/dgl_cluster_sampler.py:24); METIS itself is not available offline, the

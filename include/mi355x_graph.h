@@ -739,6 +739,22 @@ int32_t mgx_segment_topk_fwd(int64_t num_segments, const int64_t* offsets, int64
 int32_t mgx_segment_topk_bwd(int64_t N, int64_t D, int32_t mode, const int32_t* slot, const float* d_values, float* d_feat,
                              void* stream);
 
+/* ------------------------------------------------------------------ point clouds: segment k nearest neighbours (csrc/knn.hip)
+ * dgl.knn_graph / segmented_knn_graph over the segments described above: for every row i of x [N, ld] fp32 (the first D floats of a
+ * row are the point, ld >= D, no alignment asked) the k rows j of i's own segment, i included, with the smallest
+ *   d(i, j) = sum_c (x[i,c] - x[j,c])^2      (fp32, c ascending, one fma per term; the direct difference form)
+ * ordered by (d, j) ascending: equal distances keep the lower row first, a NaN distance is the greatest key and NaNs tie.
+ *   index int64 [N, k]: global row numbers in x;  dist fp32 [N, k] or NULL: the distances of those ranks.
+ * A segment shorter than k: ranks >= len hold index -1 and dist +inf; so does every rank of a row that no segment holds.  Every
+ * output element is written: no memset is needed.  Distances and selection are one launch: no [n, n] matrix exists.
+ * Supported (mgx_segment_knn_supported(k, D); everything else is MGX_ERR_UNSUPPORTED before a launch and the caller composes a
+ * sort): 1 <= k <= 64, 1 <= D <= 256, N and num_segments < 2^31, N * ld * 4 bytes < 4 GiB.  One 256-thread workgroup per 16 query
+ * rows streams the rows of their segments through LDS.  Nothing is read back to the host and the launch depends on N only:
+ * capture-safe.  Deterministic: no atomics.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_segment_knn_supported(int64_t k, int64_t D);
+int32_t mgx_segment_knn(int64_t num_segments, const int64_t* offsets, int64_t N, int64_t D, int64_t ld, const float* x, int64_t k,
+                        int64_t* index, float* dist /* may be NULL */, void* stream);
+
 /* ------------------------------------------------------------------ formats (integer, bit-exact)
  * Replace the lazy COO->CSR/CSC construction behind g.formats(...)/first kernel call
  * (main_dgl_product_sage.py:158, kernel/dgl-new.py:63) and g.in_degrees()
