@@ -9,6 +9,17 @@
 // instruction wants, no LDS staging and no transpose; a wave keeps the whole (M/16) x (K/16) grid of 16x16 accumulators
 // (<= 4 x 8 x 4 = 128 VGPRs) and walks 16 rows per trip.  Every wave writes its partial tile; a second launch adds the
 // partials in wave order (deterministic, no atomics).
+//
+// What is here:
+//   xty_walk_dword<MT, KT>               the row walk with dword loads: loads, MFMAs and the partial-tile store; the body of
+//     xty_partial_kernel<MT, KT>           one tile, any stride and alignment
+//     xty_partial_grid_kernel              outputs wider than one tile, blockIdx.y = a 64 x 128 tile
+//   xty_partial_v4_kernel                the walk with 16-byte loads for the operand(s) that allow it, column sums, a row list or a
+//                                        position map; a __global__ body of its own
+//   xty_masked_partial_kernel            the masked one-pass form (two waves per partition, a register ring)
+//   xty_sum_partials, xty_sum_column     the ONE order in which partial tiles resp. partial column sums are added: every finish
+//                                        kernel (plain, grid, column sums, masked) is index arithmetic around them
+//   xty_col                              the real column behind (tile, index) of an operand cut into float4 groups + dword tiles
 #include "common.h"
 
 namespace mgx {
@@ -24,9 +35,14 @@ static int xty_waves(int64_t n) {
   return (int)w;
 }
 
+// The walk with dword loads: any stride and alignment, no column sums, no list.  Wave gw = blockIdx.x's wave takes rows gw * 16 .. + 15,
+// then on by all the waves of gridDim.x, and writes the gw-th partial tile [MT*16][KT*16] behind part.  Shared by the dword kernels
+// and the grid of tiles.  (It is xty_partial_v4_kernel<0, MT, 0, KT, 0> with part_sum = b_rows = NULL -- the same loads, the same MFMAs
+// in the same order, the same partial layout -- and exists beside it because that kernel keeps its register counts only as a
+// __global__ body, see docs/LOG_xty_body.md.)
 template <int MT, int KT>
-__global__ __launch_bounds__(kBlock) void xty_partial_kernel(int64_t n, int M, int K, const float* __restrict__ A, int64_t lda,
-                                                             const float* __restrict__ B, int64_t ldb, float* __restrict__ part) {
+__device__ __forceinline__ void xty_walk_dword(int64_t n, int M, int K, const float* __restrict__ A, int64_t lda,
+                                               const float* __restrict__ B, int64_t ldb, float* __restrict__ part) {
   const int lane = threadIdx.x & (kWave - 1);
   const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
   const int c = lane % 16, q = lane / 16;
@@ -69,7 +85,13 @@ __global__ __launch_bounds__(kBlock) void xty_partial_kernel(int64_t n, int M, i
       for (int r = 0; r < 4; ++r) p[(i * 16 + 4 * q + r) * (KT * 16) + j * 16 + c] = acc[i][j][r];
 }
 
-// Round 4: the same partial kernel with 16-BYTE operand loads.  The MFMA wants lane (c, q) to supply A[row + q][m = c] of a 16-column
+template <int MT, int KT>
+__global__ __launch_bounds__(kBlock) void xty_partial_kernel(int64_t n, int M, int K, const float* __restrict__ A, int64_t lda,
+                                                             const float* __restrict__ B, int64_t ldb, float* __restrict__ part) {
+  xty_walk_dword<MT, KT>(n, M, K, A, lda, B, ldb, part);
+}
+
+// The same walk with 16-BYTE operand loads.  The MFMA wants lane (c, q) to supply A[row + q][m = c] of a 16-column
 // tile -- a dword per lane, i.e. 256 bytes per load instruction for 16 rows.  But which 16 columns form a "tile" is only a labelling of the
 // OUTPUT: a lane that loads the float4 A[row][4c .. 4c+3] holds one column of FOUR tiles (tile t = component t, its 16 columns are
 // 4c + t), so a 64-column operand arrives in one 16-byte load per lane and row, and the epilogue writes accumulator (tile t, index c) to
@@ -85,7 +107,13 @@ __global__ __launch_bounds__(kBlock) void xty_partial_kernel(int64_t n, int M, i
 // [n, M] matrix -- same rows per wave, same place of every row in its MFMA; a step of four rows without any row of A is skipped.
 // (For FINITE B: an Inf or NaN in a row of B that meets a zero row of A gives NaN in that product and is not even read here.)
 constexpr int kXtyBRows = 1, kXtyAPos = 2;
-template <int AVG, int AST, int BVG, int BST, int ROWS = 0>
+
+// the real column behind (tile j, index x) of an operand cut into vg float4 groups of 64 columns, then dword tiles of 16
+__device__ __forceinline__ constexpr int xty_col(int vg, int j, int x) {
+  return j < vg * 4 ? (j / 4) * 64 + 4 * x + j % 4 : vg * 64 + (j - vg * 4) * 16 + x;
+}
+
+template <int AVG, int AST, int BVG, int BST, int ROWS>
 __global__ __launch_bounds__(kBlock) void xty_partial_v4_kernel(int64_t n, int M, int K, int mt16, int kt16, const float* __restrict__ A,
                                                                 int64_t lda, const float* __restrict__ B, int64_t ldb,
                                                                 float* __restrict__ part, float* __restrict__ part_sum,
@@ -168,8 +196,7 @@ __global__ __launch_bounds__(kBlock) void xty_partial_v4_kernel(int64_t n, int M
     for (int i = 0; i < AT; ++i)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int mi = 4 * q + r;
-        const int m = i < AVG * 4 ? (i / 4) * 64 + 4 * mi + (i % 4) : AVG * 64 + (i - AVG * 4) * 16 + mi;
+        const int m = xty_col(AVG, i, 4 * q + r);
         if (m < mt16) part_sum[gw * (int64_t)mt16 + m] = accs[i][r];
       }
   }
@@ -179,40 +206,52 @@ __global__ __launch_bounds__(kBlock) void xty_partial_v4_kernel(int64_t n, int M
   for (int i = 0; i < AT; ++i)
 #pragma unroll
     for (int j = 0; j < BT; ++j) {
-      const int k = j < BVG * 4 ? (j / 4) * 64 + 4 * c + (j % 4) : BVG * 64 + (j - BVG * 4) * 16 + c;
+      const int k = xty_col(BVG, j, c);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int mi = 4 * q + r;
-        const int m = i < AVG * 4 ? (i / 4) * 64 + 4 * mi + (i % 4) : AVG * 64 + (i - AVG * 4) * 16 + mi;
+        const int m = xty_col(AVG, i, 4 * q + r);
         if (m < mt16 && k < kt16) p[m * kt16 + k] = acc[i][j][r];
       }
     }
 }
 
+// Outputs wider than one 64 x 128 tile (arxiv's 256 x 512, GAT's 128 x 602, the stacked 64 x 200 of the one-GEMM SAGE layer):
+// ONE launch, blockIdx.y = output tile.  The waves of different tiles walk the same data rows at the same time, so an operand
+// row is read from HBM once and from L2 by the other tiles, and 4 waves per SIMD are resident -- against one launch per tile,
+// each streaming both operands again with less than one wave per SIMD.  About kXtyGridTotal waves in all (4 per SIMD at 128
+// VGPRs) shared evenly by the tiles; partials per (tile, wave).
+constexpr int kXtyGridTotal = 4096;
+constexpr int kXtyTileM = 64, kXtyTileK = 128;
+
+__global__ __launch_bounds__(kBlock) void xty_partial_grid_kernel(int64_t n, int M, int K, int tiles_k, const float* __restrict__ A,
+                                                                  int64_t lda, const float* __restrict__ B, int64_t ldb,
+                                                                  float* __restrict__ part) {
+  const int tile = blockIdx.y;
+  const int m0 = (tile / tiles_k) * kXtyTileM, k0 = (tile % tiles_k) * kXtyTileK;
+  const int Mt = M - m0 < kXtyTileM ? M - m0 : kXtyTileM, Kt = K - k0 < kXtyTileK ? K - k0 : kXtyTileK;
+  const int64_t wpt = (int64_t)gridDim.x * kWavesPerBlock;  // waves per tile
+  xty_walk_dword<kXtyTileM / 16, kXtyTileK / 16>(n, Mt, Kt, A + m0, lda, B + k0, ldb, part + (int64_t)tile * wpt * (kXtyTileM * kXtyTileK));
+}
+
 template <int AVG, int AST>
 static bool launch_xty_v4_b(int bvg, int bst, int waves, int64_t n, int M, int K, int mt16, int kt16, const float* A, int64_t lda,
                             const float* B, int64_t ldb, float* part, float* part_sum, hipStream_t s, const int64_t* b_rows, int mode) {
-  if (b_rows && mode == kXtyAPos) {
-#define MGX_XTY4P(G) if (AVG == 0 && AST == 3 && bvg == G && bst == 0) { hipLaunchKernelGGL((xty_partial_v4_kernel<0, 3, G, 0, kXtyAPos>), dim3(waves / kWavesPerBlock), dim3(kBlock), 0, s, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, b_rows); return true; }
-    MGX_XTY4P(2) MGX_XTY4P(1)
-#undef MGX_XTY4P
+#define MGX_XTY4(G, T, ROWS) if (bvg == G && bst == T) { hipLaunchKernelGGL((xty_partial_v4_kernel<AVG, AST, G, T, ROWS>), dim3(waves / kWavesPerBlock), dim3(kBlock), 0, s, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, b_rows); return true; }
+  if (b_rows) {  // the list forms that are built: a dword-loaded A (the 47-column output gradient) against 128 or 64 float4 columns
+    if constexpr (AVG == 0 && AST == 3) {
+      if (mode == kXtyAPos) { MGX_XTY4(2, 0, kXtyAPos) MGX_XTY4(1, 0, kXtyAPos) }
+      else { MGX_XTY4(2, 0, kXtyBRows) MGX_XTY4(1, 0, kXtyBRows) }
+    }
     return false;
   }
-  if (b_rows) {  // the row-list forms that are built: a dword-loaded A (the 47-column output gradient) against 128 or 64 float4 columns
-#define MGX_XTY4R(G) if (AVG == 0 && AST == 3 && bvg == G && bst == 0) { hipLaunchKernelGGL((xty_partial_v4_kernel<0, 3, G, 0, kXtyBRows>), dim3(waves / kWavesPerBlock), dim3(kBlock), 0, s, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, b_rows); return true; }
-    MGX_XTY4R(2) MGX_XTY4R(1)
-#undef MGX_XTY4R
-    return false;
-  }
-#define MGX_XTY4(G, T) if (bvg == G && bst == T) { hipLaunchKernelGGL((xty_partial_v4_kernel<AVG, AST, G, T>), dim3(waves / kWavesPerBlock), dim3(kBlock), 0, s, n, M, K, mt16, kt16, A, lda, B, ldb, part, part_sum, b_rows); return true; }
-  MGX_XTY4(2, 0) MGX_XTY4(1, 0) MGX_XTY4(1, 1) MGX_XTY4(1, 2) MGX_XTY4(1, 3) MGX_XTY4(1, 4)
+  MGX_XTY4(2, 0, 0) MGX_XTY4(1, 0, 0) MGX_XTY4(1, 1, 0) MGX_XTY4(1, 2, 0) MGX_XTY4(1, 3, 0) MGX_XTY4(1, 4, 0)
 #undef MGX_XTY4
   return false;
 }
 
 // 16-byte loads for the operand(s) that allow it; false = use the dword kernels above
 static bool launch_xty_v4(int mt, int kt, int waves, int64_t n, int M, int K, const float* A, int64_t lda, const float* B, int64_t ldb,
-                          float* part, float* part_sum, hipStream_t s, const int64_t* b_rows = nullptr, int mode = 0) {
+                          float* part, float* part_sum, hipStream_t s, const int64_t* b_rows, int mode) {
   const bool bvec = ldb % 4 == 0 && (uintptr_t)B % 16 == 0 && K % 4 == 0 && K >= 64;
   if (!bvec) return false;
   const int bvg = K >= 128 ? 2 : 1, bst = (K - bvg * 64 + 15) / 16;
@@ -227,123 +266,6 @@ static bool launch_xty_v4(int mt, int kt, int waves, int64_t n, int M, int K, co
   }
 }
 
-// 16 output elements x 16 slices of the partial list per workgroup; slices combined in slice order
-__global__ __launch_bounds__(kBlock) void xty_finish_kernel(int M, int K, int ldm /* KT*16 */, int tile /* MT*16*KT*16 */, int waves,
-                                                            const float* __restrict__ part, float* __restrict__ out, int64_t ldc) {
-  __shared__ float red[16][17];
-  const int e = threadIdx.x % 16, sl = threadIdx.x / 16;
-  const int idx = blockIdx.x * 16 + e;  // over M*K
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (idx < M * K) {
-    const int m = idx / K, k = idx % K;
-    const float* p = part + (int64_t)m * ldm + k;
-    const int per = waves / 16;
-    for (int w = sl * per; w < (sl + 1) * per; w += 4) {
-      s0 += p[(int64_t)w * tile];
-      s1 += p[(int64_t)(w + 1) * tile];
-      s2 += p[(int64_t)(w + 2) * tile];
-      s3 += p[(int64_t)(w + 3) * tile];
-    }
-  }
-  red[sl][e] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (sl == 0 && idx < M * K) {
-    float s = 0.f;
-    for (int i = 0; i < 16; ++i) s += red[i][e];
-    out[(int64_t)(idx / K) * ldc + idx % K] = s;
-  }
-}
-
-// Outputs wider than one 64 x 128 tile (arxiv's 256 x 512, GAT's 128 x 602, the stacked 64 x 200 of the one-GEMM SAGE layer):
-// ONE launch, blockIdx.y = output tile.  The waves of different tiles walk the same data rows at the same time, so an operand
-// row is read from HBM once and from L2 by the other tiles, and 4 waves per SIMD are resident -- against one launch per tile,
-// each streaming both operands again with less than one wave per SIMD.  About kXtyGridTotal waves in all (4 per SIMD at 128
-// VGPRs) shared evenly by the tiles; partials per (tile, wave).
-constexpr int kXtyGridTotal = 4096;
-constexpr int kXtyTileM = 64, kXtyTileK = 128;
-
-__global__ __launch_bounds__(kBlock) void xty_partial_grid_kernel(int64_t n, int M, int K, int tiles_k, const float* __restrict__ A,
-                                                                  int64_t lda, const float* __restrict__ B, int64_t ldb,
-                                                                  float* __restrict__ part) {
-  constexpr int MT = 4, KT = 8;
-  const int tile = blockIdx.y;
-  const int m0 = (tile / tiles_k) * kXtyTileM, k0 = (tile % tiles_k) * kXtyTileK;
-  const int Mt = M - m0 < kXtyTileM ? M - m0 : kXtyTileM, Kt = K - k0 < kXtyTileK ? K - k0 : kXtyTileK;
-  A += m0;
-  B += k0;
-  const int lane = threadIdx.x & (kWave - 1);
-  const int64_t gw = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-  const int c = lane % 16, q = lane / 16;
-  v4f acc[MT][KT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < KT; ++j) acc[i][j] = (v4f)(0.f);
-  bool am[MT], bm[KT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i) am[i] = i * 16 + c < Mt;
-#pragma unroll
-  for (int j = 0; j < KT; ++j) bm[j] = j * 16 + c < Kt;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock * 16;
-  for (int64_t r0 = gw * 16; r0 < n; r0 += stride) {
-    float a[4][MT], b[4][KT];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int64_t row = r0 + s * 4 + q;
-      const bool ok = row < n;
-#pragma unroll
-      for (int i = 0; i < MT; ++i) a[s][i] = (ok && am[i]) ? A[row * lda + i * 16 + c] : 0.f;
-#pragma unroll
-      for (int j = 0; j < KT; ++j) b[s][j] = (ok && bm[j]) ? B[row * ldb + j * 16 + c] : 0.f;
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < KT; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s][i], b[s][j], acc[i][j], 0, 0, 0);
-  }
-  const int64_t wpt = (int64_t)gridDim.x * kWavesPerBlock;  // waves per tile
-  float* p = part + ((int64_t)tile * wpt + gw) * (int64_t)(kXtyTileM * kXtyTileK);
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < KT; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) p[(i * 16 + 4 * q + r) * kXtyTileK + j * 16 + c] = acc[i][j][r];
-}
-
-// blockIdx.y = tile; blockIdx.x over the 64 x 128 elements of a tile, 16 per workgroup; slices combined in slice order
-__global__ __launch_bounds__(kBlock) void xty_finish_grid_kernel(int M, int K, int tiles_k, int wpt, const float* __restrict__ part,
-                                                                 float* __restrict__ out, int64_t ldc) {
-  __shared__ float red[16][17];
-  const int tile = blockIdx.y;
-  const int m0 = (tile / tiles_k) * kXtyTileM, k0 = (tile % tiles_k) * kXtyTileK;
-  const int e = threadIdx.x % 16, sl = threadIdx.x / 16;
-  const int idx = blockIdx.x * 16 + e;  // over the tile's 64 x 128 elements
-  const int m = idx / kXtyTileK, k = idx % kXtyTileK;
-  const bool live = m0 + m < M && k0 + k < K;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  if (live) {
-    const int tsz = kXtyTileM * kXtyTileK;
-    const float* p = part + (int64_t)tile * wpt * tsz + idx;
-    const int per = wpt / 16;
-    for (int w = sl * per; w < (sl + 1) * per; w += 4) {
-      s0 += p[(int64_t)w * tsz];
-      s1 += p[(int64_t)(w + 1) * tsz];
-      s2 += p[(int64_t)(w + 2) * tsz];
-      s3 += p[(int64_t)(w + 3) * tsz];
-    }
-  }
-  red[sl][e] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (sl == 0 && live) {
-    float s = 0.f;
-    for (int i = 0; i < 16; ++i) s += red[i][e];
-    out[(int64_t)(m0 + m) * ldc + k0 + k] = s;
-  }
-}
-
 template <int MT>
 static bool launch_xty_kt(int kt, int waves, int64_t n, int M, int K, const float* A, int64_t lda, const float* B, int64_t ldb,
                           float* part, hipStream_t s) {
@@ -355,20 +277,72 @@ static bool launch_xty_kt(int kt, int waves, int64_t n, int M, int K, const floa
   }
 }
 
-}  // namespace mgx
+// One output element's sum over the partial list, by the 16 threads that share threadIdx.x % 16: thread (e, sl) adds slice sl of the
+// list in four running sums, the slices are added in slice order.  at(): the element in partial 0, asked for a live element only (an
+// address worked out before the test is carried through the sum: four more VGPRs in xty_finish_kernel); the total comes back in the
+// sl == 0 threads of a live element.  Every thread of the workgroup calls this (one __syncthreads()).
+template <class At>
+__device__ __forceinline__ float xty_sum_partials(At at, int64_t tile, int waves, bool live, float (*red)[17]) {
+  const int e = threadIdx.x % 16, sl = threadIdx.x / 16;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  if (live) {
+    const float* __restrict__ p = at();
+    const int per = waves / 16;
+    for (int w = sl * per; w < (sl + 1) * per; w += 4) {
+      s0 += p[w * tile];
+      s1 += p[(w + 1) * tile];
+      s2 += p[(w + 2) * tile];
+      s3 += p[(w + 3) * tile];
+    }
+  }
+  red[sl][e] = (s0 + s1) + (s2 + s3);
+  __syncthreads();
+  float s = 0.f;
+  if (sl == 0 && live)
+    for (int i = 0; i < 16; ++i) s += red[i][e];
+  return s;
+}
 
-namespace mgx {
-// column sums: the [waves][mt16] partial vectors added in wave order, one wave per output column
+// One column's sum over the [waves][ld] partial vectors by one wave: lanes stride the list, then a butterfly.  p: the column in vector 0.
+__device__ __forceinline__ float xty_sum_column(const float* __restrict__ p, int ld, int waves) {
+  float s = 0.f;
+  for (int w = threadIdx.x % kWave; w < waves; w += kWave) s += p[(int64_t)w * ld];
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, kWave);
+  return s;
+}
+
+// 16 output elements per workgroup, over M * K
+__global__ __launch_bounds__(kBlock) void xty_finish_kernel(int M, int K, int ldm /* KT*16 */, int tile /* MT*16*KT*16 */, int waves,
+                                                            const float* __restrict__ part, float* __restrict__ out, int64_t ldc) {
+  __shared__ float red[16][17];
+  const int idx = blockIdx.x * 16 + threadIdx.x % 16;
+  const bool live = idx < M * K;
+  const float s = xty_sum_partials([&] { return part + (int64_t)(idx / K) * ldm + idx % K; }, tile, waves, live, red);
+  if (threadIdx.x < 16 && live) out[(int64_t)(idx / K) * ldc + idx % K] = s;
+}
+
+// blockIdx.y = tile; blockIdx.x over the 64 x 128 elements of a tile, 16 per workgroup
+__global__ __launch_bounds__(kBlock) void xty_finish_grid_kernel(int M, int K, int tiles_k, int wpt, const float* __restrict__ part,
+                                                                 float* __restrict__ out, int64_t ldc) {
+  __shared__ float red[16][17];
+  constexpr int tsz = kXtyTileM * kXtyTileK;
+  const int tile = blockIdx.y;
+  const int m0 = (tile / tiles_k) * kXtyTileM, k0 = (tile % tiles_k) * kXtyTileK;
+  const int idx = blockIdx.x * 16 + threadIdx.x % 16;
+  const int m = idx / kXtyTileK, k = idx % kXtyTileK;
+  const bool live = m0 + m < M && k0 + k < K;
+  const float s = xty_sum_partials([&] { return part + (int64_t)tile * wpt * tsz + idx; }, tsz, wpt, live, red);
+  if (threadIdx.x < 16 && live) out[(int64_t)(m0 + m) * ldc + k0 + k] = s;
+}
+
+// column sums: the [waves][mt16] partial vectors, one wave per output column
 __global__ __launch_bounds__(kBlock) void xty_colsum_finish_kernel(int M, int mt16, int waves, const float* __restrict__ part_sum,
                                                                    float* __restrict__ colsum) {
   const int m = blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-  const int lane = threadIdx.x % kWave;
   if (m >= M) return;
-  float s = 0.f;
-  for (int w = lane; w < waves; w += kWave) s += part_sum[(int64_t)w * mt16 + m];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, kWave);
-  if (lane == 0) colsum[m] = s;
+  const float s = xty_sum_column(part_sum + m, mt16, waves);
+  if (threadIdx.x % kWave == 0) colsum[m] = s;
 }
 
 // mgx_xty_colsum_masked: relu_dropout_bwd_kernel + xty_partial_v4_kernel<1, 0, ...> per 128-column block of B + the column sums in ONE
@@ -486,8 +460,8 @@ __global__ __launch_bounds__(kBlock) void xty_masked_partial_kernel(int64_t n, i
     }
 }
 
-// One finish launch for out [64, K] and colsum [64]: the element workgroups run xty_finish_kernel's additions (16 slices of the partition
-// list, four running sums per slice, slices added in slice order), the last 16 workgroups xty_colsum_finish_kernel's (one wave per column).
+// One finish launch for out [64, K] and colsum [64]: the element workgroups are xty_finish_kernel's, the last 16 workgroups
+// xty_colsum_finish_kernel's (one wave per column).
 __global__ __launch_bounds__(kBlock) void xty_masked_finish_kernel(int K, int waves, const float* __restrict__ part,
                                                                    const float* __restrict__ part_sum, float* __restrict__ out, int64_t ldc,
                                                                    float* __restrict__ colsum) {
@@ -495,34 +469,15 @@ __global__ __launch_bounds__(kBlock) void xty_masked_finish_kernel(int K, int wa
   const int elem_blocks = 64 * K / 16;
   if ((int)blockIdx.x >= elem_blocks) {
     const int m = ((int)blockIdx.x - elem_blocks) * kWavesPerBlock + threadIdx.x / kWave;
-    const int lane = threadIdx.x % kWave;
-    float s = 0.f;
-    for (int w = lane; w < waves; w += kWave) s += part_sum[(int64_t)w * 64 + m];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, kWave);
-    if (lane == 0) colsum[m] = s;
+    const float s = xty_sum_column(part_sum + m, 64, waves);
+    if (threadIdx.x % kWave == 0) colsum[m] = s;
     return;
   }
-  const int e = threadIdx.x % 16, sl = threadIdx.x / 16;
-  const int idx = blockIdx.x * 16 + e;  // over 64 * K, a multiple of 16
-  const int tile = 64 * K;
-  const float* p = part + idx;
-  const int per = waves / 16;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  for (int w = sl * per; w < (sl + 1) * per; w += 4) {
-    s0 += p[(int64_t)w * tile];
-    s1 += p[(int64_t)(w + 1) * tile];
-    s2 += p[(int64_t)(w + 2) * tile];
-    s3 += p[(int64_t)(w + 3) * tile];
-  }
-  red[sl][e] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (sl == 0) {
-    float s = 0.f;
-    for (int i = 0; i < 16; ++i) s += red[i][e];
-    out[(int64_t)(idx / K) * ldc + idx % K] = s;
-  }
+  const int idx = blockIdx.x * 16 + threadIdx.x % 16;  // over 64 * K, a multiple of 16
+  const float s = xty_sum_partials([&] { return part + idx; }, 64 * K, waves, true, red);
+  if (threadIdx.x < 16) out[(int64_t)(idx / K) * ldc + idx % K] = s;
 }
+
 }  // namespace mgx
 
 extern "C" int64_t mgx_xty_workspace(int64_t M, int64_t K) {
@@ -536,37 +491,7 @@ extern "C" int64_t mgx_xty_workspace(int64_t M, int64_t K) {
 }
 
 static int32_t xty_impl(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int64_t ldc,
-                        float* colsum, void* workspace, void* stream, const int64_t* b_rows = nullptr, int mode = 0);
-
-extern "C" int32_t mgx_xty(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out,
-                           int64_t ldc, void* workspace, void* stream) {
-  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, nullptr, workspace, stream);
-}
-
-extern "C" int32_t mgx_xty_colsum(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out,
-                                  int64_t ldc, float* colsum, void* workspace, void* stream) {
-  if (!colsum) return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, nullptr, workspace, stream);
-  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream);
-}
-
-extern "C" int32_t mgx_xty_rows(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb,
-                                const int64_t* b_rows, float* out, int64_t ldc, void* workspace, void* stream) {
-  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, nullptr, workspace, stream, b_rows, b_rows ? mgx::kXtyBRows : 0);
-}
-
-extern "C" int32_t mgx_xty_colsum_rows(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb,
-                                       const int64_t* b_rows, float* out, int64_t ldc, float* colsum, void* workspace, void* stream) {
-  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream, b_rows, b_rows ? mgx::kXtyBRows : 0);
-}
-
-extern "C" int32_t mgx_xty_colsum_pos(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const int64_t* a_pos, const float* b,
-                                      int64_t ldb, float* out, int64_t ldc, float* colsum, void* workspace, void* stream) {
-  if (!a_pos) return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream);
-  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream, a_pos, mgx::kXtyAPos);
-}
-
-static int32_t xty_impl(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out, int64_t ldc,
-                        float* colsum, void* workspace, void* stream, const int64_t* b_rows, int mode) {
+                        float* colsum, void* workspace, void* stream, const int64_t* b_rows = nullptr, int mode = 0) {
   using namespace mgx;
   MGX_ENTER();
   MGX_CHECK_ARG(n >= 0 && M >= 1 && K >= 1, "mgx_xty: bad sizes");
@@ -623,6 +548,32 @@ static int32_t xty_impl(int64_t n, int64_t M, int64_t K, const float* a, int64_t
     MGX_CHECK_LAUNCH();
   }
   return MGX_OK;
+}
+
+// b_rows with mode kXtyBRows: the row list of b; with kXtyAPos: the position map of a.  A NULL list is the plain form.
+extern "C" int32_t mgx_xty(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out,
+                           int64_t ldc, void* workspace, void* stream) {
+  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, nullptr, workspace, stream);
+}
+
+extern "C" int32_t mgx_xty_colsum(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb, float* out,
+                                  int64_t ldc, float* colsum, void* workspace, void* stream) {
+  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream);
+}
+
+extern "C" int32_t mgx_xty_rows(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb,
+                                const int64_t* b_rows, float* out, int64_t ldc, void* workspace, void* stream) {
+  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, nullptr, workspace, stream, b_rows, mgx::kXtyBRows);
+}
+
+extern "C" int32_t mgx_xty_colsum_rows(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const float* b, int64_t ldb,
+                                       const int64_t* b_rows, float* out, int64_t ldc, float* colsum, void* workspace, void* stream) {
+  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream, b_rows, mgx::kXtyBRows);
+}
+
+extern "C" int32_t mgx_xty_colsum_pos(int64_t n, int64_t M, int64_t K, const float* a, int64_t lda, const int64_t* a_pos, const float* b,
+                                      int64_t ldb, float* out, int64_t ldc, float* colsum, void* workspace, void* stream) {
+  return xty_impl(n, M, K, a, lda, b, ldb, out, ldc, colsum, workspace, stream, a_pos, mgx::kXtyAPos);
 }
 
 extern "C" int64_t mgx_xty_masked_workspace(int64_t K) {

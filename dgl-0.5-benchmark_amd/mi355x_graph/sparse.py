@@ -1345,6 +1345,22 @@ class HipBackend(object):
     XTY_MAX = (256, 1024)     # the grid of tiles in one launch goes up to this output shape
     XTY_MIN_ROWS = 1 << 16    # shorter reductions stay with the GEMM library
 
+    def _xty_call(self, dev, M, K, colsum, call, out=None):
+        """One call of an mgx_xty* entry point: allocates out [M, K] (unless the caller hands in the tile of a larger output), sums [M]
+        if colsum and the workspace of mgx_xty_workspace(M, K); call(L, out, ldc, sums, workspace, stream) -> status.
+        (out, sums), or None -- nothing launched -- when the library has no kernel for the operands (ERR_UNSUPPORTED)."""
+        L = _lib.lib()
+        if out is None:
+            out = torch.empty((M, K), dtype=torch.float32, device=dev)
+        sums = torch.empty(M, dtype=torch.float32, device=dev) if colsum else None
+        ws = torch.empty(max(L.mgx_xty_workspace(M, K), 4) // 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            st = call(L, _ptr(out), out.stride(0), _ptr(sums), _ptr(ws), _stream(dev))
+        if st == _lib.ERR_UNSUPPORTED:
+            return None
+        _lib.check(st)
+        return out, sums
+
     def _xty_rows(self, a2d, b2d, rows, colsum):
         """xty over the row list in the kernel (mgx_xty_rows / mgx_xty_colsum_rows); None when the library has no kernel for the shape."""
         dev = self._check_dev(a2d, b2d, rows)
@@ -1353,21 +1369,11 @@ class HipBackend(object):
         tm, tk = self.XTY_TILE
         if (M > tm or K > tk or a2d.stride(1) != 1 or b2d.stride(1) != 1 or a2d.dtype != torch.float32 or b2d.dtype != torch.float32):
             return None
-        L = _lib.lib()
-        out = torch.empty((M, K), dtype=torch.float32, device=dev)
-        sums = torch.empty(M, dtype=torch.float32, device=dev) if colsum else None
-        ws = torch.empty(max(L.mgx_xty_workspace(M, K), 4) // 4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            if colsum:
-                st = L.mgx_xty_colsum_rows(n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(b2d), max(b2d.stride(0), K), _ptr(rows),
-                                           _ptr(out), out.stride(0), _ptr(sums), _ptr(ws), _stream(dev))
-            else:
-                st = L.mgx_xty_rows(n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(b2d), max(b2d.stride(0), K), _ptr(rows),
-                                    _ptr(out), out.stride(0), _ptr(ws), _stream(dev))
-        if st == _lib.ERR_UNSUPPORTED:
-            return None
-        _lib.check(st)
-        return (out, sums) if colsum else out
+        head = (n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(b2d), max(b2d.stride(0), K), _ptr(rows))
+        if colsum:
+            return self._xty_call(dev, M, K, True, lambda L, *tail: L.mgx_xty_colsum_rows(*head, *tail))
+        res = self._xty_call(dev, M, K, False, lambda L, out, ldc, _, ws, stream: L.mgx_xty_rows(*head, out, ldc, ws, stream))
+        return None if res is None else res[0]
 
     def xty_pos(self, a2d, a_pos, b2d, colsum=False):
         """a^T b over all n rows of b2d [n, K] for an a that is zero outside some rows and stored without them: a2d [R, M], a_pos int64 [n]
@@ -1380,17 +1386,9 @@ class HipBackend(object):
         if (a_pos.dtype != torch.int64 or a_pos.shape != (n,) or not a_pos.is_contiguous() or a2d.shape[0] == 0 or M > tm or K > tk or a2d.stride(1) != 1
                 or b2d.stride(1) != 1 or a2d.dtype != torch.float32 or b2d.dtype != torch.float32):
             return None
-        L = _lib.lib()
-        out = torch.empty((M, K), dtype=torch.float32, device=dev)
-        sums = torch.empty(M, dtype=torch.float32, device=dev) if colsum else None
-        ws = torch.empty(max(L.mgx_xty_workspace(M, K), 4) // 4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            st = L.mgx_xty_colsum_pos(n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(a_pos), _ptr(b2d), max(b2d.stride(0), K),
-                                      _ptr(out), out.stride(0), _ptr(sums), _ptr(ws), _stream(dev))
-        if st == _lib.ERR_UNSUPPORTED:
-            return None
-        _lib.check(st)
-        return (out, sums) if colsum else out
+        res = self._xty_call(dev, M, K, colsum, lambda L, *tail: L.mgx_xty_colsum_pos(
+            n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(a_pos), _ptr(b2d), max(b2d.stride(0), K), *tail))
+        return res if colsum or res is None else res[0]
 
     def xty_masked(self, dy, mask, p, b2d):
         """(dz^T b2d [64, K], column sums of dz [64]) for dz = relu_dropout_bwd(dy, mask, p), which is never stored: the mask is applied
@@ -1435,41 +1433,36 @@ class HipBackend(object):
         if M > self.XTY_MAX[0] or K > self.XTY_MAX[1]:
             raise DGLError("mgx_xty: at most %d x %d outputs, got %d x %d" % (self.XTY_MAX + (M, K)))
         out = torch.empty((M, K), dtype=torch.float32, device=dev)
-        sums = torch.empty(M, dtype=torch.float32, device=dev) if colsum else None
-        have_sums = False
-        L = _lib.lib()
         tm, tk = self.XTY_TILE
         ntiles = ((M + tm - 1) // tm) * ((K + tk - 1) // tk)
 
-        def one(a_t, b_t, o_t, ws, want_sums):
+        def one(a_t, b_t, o_t, want_sums):
+            """a_t^T b_t into o_t; the column sums of a_t where they were wanted and the library forms them in the same pass, else None"""
+            Mt, Kt = a_t.shape[1], b_t.shape[1]
+            head = (n, Mt, Kt, _ptr(a_t), max(a2d.stride(0), M), _ptr(b_t), max(b2d.stride(0), K))
             if want_sums:
-                st = L.mgx_xty_colsum(n, a_t.shape[1], b_t.shape[1], _ptr(a_t), max(a2d.stride(0), M), _ptr(b_t), max(b2d.stride(0), K),
-                                      _ptr(o_t), out.stride(0), _ptr(sums), _ptr(ws), _stream(dev))
-                if st != _lib.ERR_UNSUPPORTED:
-                    _lib.check(st)
-                    return True
-            _lib.check(L.mgx_xty(n, a_t.shape[1], b_t.shape[1], _ptr(a_t), max(a2d.stride(0), M), _ptr(b_t), max(b2d.stride(0), K),
-                                 _ptr(o_t), out.stride(0), _ptr(ws), _stream(dev)))
-            return False
+                res = self._xty_call(dev, Mt, Kt, True, lambda L, *tail: L.mgx_xty_colsum(*head, *tail), out=o_t)
+                if res is not None:
+                    return res[1]
+            if self._xty_call(dev, Mt, Kt, False, lambda L, o, ldc, _, ws, stream: L.mgx_xty(*head, o, ldc, ws, stream), out=o_t) is None:
+                _lib.check(_lib.ERR_UNSUPPORTED)
+            return None
 
-        with torch.cuda.device(dev):
-            if ntiles == 1 or ntiles >= 4:
-                # a single 64 x 128 tile, or the grid of tiles in ONE launch (operand rows shared through L2): measured
-                # 256 x 512 at n = 169 k 1.07 -> 0.56 ms, 128 x 602 at n = 233 k 0.78 -> 0.57 ms (experiments/exp_wgrad_shapes.py)
-                ws = torch.empty(max(L.mgx_xty_workspace(M, K), 4) // 4, dtype=torch.float32, device=dev)
-                have_sums = one(a2d, b2d, out, ws, colsum and ntiles == 1)
-            else:
-                # two or three tiles (the stacked 64 x 200 of the products layer): one launch per tile, each with the exact tile
-                # shape, is faster than the grid's padded 64 x 128 tiles (n = 2.45 M: 0.93 against 1.04 ms)
-                ws = torch.empty(max(L.mgx_xty_workspace(min(M, tm), min(K, tk)), 4) // 4, dtype=torch.float32, device=dev)
-                for m0 in range(0, M, tm):
-                    for k0 in range(0, K, tk):
-                        a_t, b_t, o_t = a2d[:, m0:m0 + tm], b2d[:, k0:k0 + tk], out[m0:m0 + tm, k0:k0 + tk]
-                        if one(a_t, b_t, o_t, ws, colsum and M <= tm and k0 == 0):
-                            have_sums = True
+        sums = None
+        if ntiles == 1 or ntiles >= 4:
+            # a single 64 x 128 tile, or the grid of tiles in ONE launch (operand rows shared through L2): measured
+            # 256 x 512 at n = 169 k 1.07 -> 0.56 ms, 128 x 602 at n = 233 k 0.78 -> 0.57 ms (experiments/exp_wgrad_shapes.py)
+            sums = one(a2d, b2d, out, colsum and ntiles == 1)
+        else:
+            # two or three tiles (the stacked 64 x 200 of the products layer): one launch per tile, each with the exact tile
+            # shape, is faster than the grid's padded 64 x 128 tiles (n = 2.45 M: 0.93 against 1.04 ms)
+            for m0 in range(0, M, tm):
+                for k0 in range(0, K, tk):
+                    got = one(a2d[:, m0:m0 + tm], b2d[:, k0:k0 + tk], out[m0:m0 + tm, k0:k0 + tk], colsum and M <= tm and k0 == 0)
+                    sums = got if got is not None else sums
         if not colsum:
             return out
-        return out, (sums if have_sums else self.column_sum(a2d if a2d.is_contiguous() else a2d.contiguous()))
+        return out, (sums if sums is not None else self.column_sum(a2d if a2d.is_contiguous() else a2d.contiguous()))
 
     def _rows_gemm_lists(self, a2d, b2d, b_transposed, bias, row_scale, scale_from, split_col, rows, scatter_rows, out2):
         """rows_gemm with a row list in the kernel (mgx_rows_gemm_rows); None when the library has no kernel for the shape."""

@@ -1106,6 +1106,64 @@ def test_xty_colsum_is_plain_fp32_on_integers(n, M, K):
     assert_exact(N(sums), A.astype(np.int64).sum(0), "column sums of xty, strided")
 
 
+_xty_small = {}
+
+
+def _xty_small_operands(n):
+    """One [n, 64] x [n, 128] pair per n (values in [-3, 3], 4117 x 9 < 2^24) with its exact product, made once and never written:
+    the cases below take columns of it.  n = 37: a ragged last step, and 253 of the 256 waves have no row.  n = 4117: xty_waves
+    gives 256 waves, one sweep covers 4096 rows, so wave 0 makes a full second trip and wave 1 a ragged one."""
+    if n not in _xty_small:
+        A, B, want = _xty_operands(n, 64, 128)
+        _xty_small[n] = (A, want, T(A, DEV), T(B, DEV))
+    return _xty_small[n]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kt", range(1, 9))
+@pytest.mark.parametrize("mt", range(1, 5))
+@pytest.mark.parametrize("n", [37, 4117])
+def test_xty_every_dword_instantiation(n, mt, kt):
+    """The dword-load kernel <mt, kt> with ragged last tiles; a row stride of K = 16 kt - 1 floats can never take the 16-byte form."""
+    M, K = 16 * mt - 3, 16 * kt - 1
+    _, want, a, b = _xty_small_operands(n)
+    a, b = a[:, :M].contiguous(), b[:, :K].contiguous()
+    assert_exact(N(sparse.backend_for(a).xty(a, b)), want[:M, :K], "xty, dword form <%d, %d>" % (mt, kt))
+
+
+@pytest.mark.gpu
+def test_xty_dword_form_through_a_misaligned_view():
+    """K % 4 == 0 and a row stride of 128 floats, but the view starts one float in: 4-byte aligned only, so the dword form <4, 4>;
+    with colsum=True mgx_xty_colsum has no kernel for it and the sums come from mgx_column_sum."""
+    A, want, a, wide = _xty_small_operands(4117)
+    b = wide[:, 1:65]
+    assert b.data_ptr() % 16 == 4 and b.stride(0) % 4 == 0
+    be = sparse.backend_for(a)
+    assert_exact(N(be.xty(a, b)), want[:, 1:65], "xty, misaligned b")
+    got, sums = be.xty(a, b, colsum=True)
+    assert_exact(N(got), want[:, 1:65], "xty with column sums, misaligned b")
+    assert_exact(N(sums), A.astype(np.int64).sum(0), "column sums of xty, misaligned b")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,M,K", [(37, 65, 129),        # four tiles, ragged in both directions, almost every wave without a row
+                                   (4117, 200, 300)])   # twelve tiles, 64 waves per tile: five trips, the last one ragged
+def test_xty_grid_of_tiles_at_small_n(n, M, K):
+    A, B, want = _xty_operands(n, M, K)
+    a, b = T(A, DEV), T(B, DEV)
+    assert_exact(N(sparse.backend_for(a).xty(a, b)), want, "xty, grid of tiles")
+
+
+@pytest.mark.gpu
+def test_xty_two_tiles_one_launch_each_with_column_sums():
+    """64 x 200: a 64 x 128 and a 64 x 72 tile, one launch each; the column sums come with the first."""
+    A, B, want = _xty_operands(4117, 64, 200)
+    a, b = T(A, DEV), T(B, DEV)
+    got, sums = sparse.backend_for(a).xty(a, b, colsum=True)
+    assert_exact(N(got), want, "xty, two tiles")
+    assert_exact(N(sums), A.astype(np.int64).sum(0), "column sums of xty, two tiles")
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("K,M,bt,lda_pad,n", [(200, 64, True, 0, 70001), (128, 64, True, 0, 65600), (128, 47, True, 0, 66000),
                                               (64, 128, False, 0, 70000), (47, 128, False, 0, 65599), (64, 128, False, 8, 5000),
