@@ -25,8 +25,10 @@ __global__ __launch_bounds__(kBlock) void relu_dropout_fwd_kernel(int64_t n4, co
     const v4f v = __builtin_nontemporal_load(&x[r * ldx4 + c]);
     const uint64_t r0 = splitmix64(seed ^ ((offset + (uint64_t)i) * 2));
     const uint64_t r1 = splitmix64(seed ^ ((offset + (uint64_t)i) * 2 + 1));
-    const bool k0 = (uint32_t)r0 >= drop_below && v.x > 0.f, k1 = (uint32_t)(r0 >> 32) >= drop_below && v.y > 0.f;
-    const bool k2 = (uint32_t)r1 >= drop_below && v.z > 0.f, k3 = (uint32_t)(r1 >> 32) >= drop_below && v.w > 0.f;
+    // relu as !(v <= 0): a NaN is not laundered into a clean zero -- at a kept position it stays NaN with its bit SET, so the backward
+    // passes dy * scale there (finite values and infinities: the same bits as v > 0)
+    const bool k0 = (uint32_t)r0 >= drop_below && !(v.x <= 0.f), k1 = (uint32_t)(r0 >> 32) >= drop_below && !(v.y <= 0.f);
+    const bool k2 = (uint32_t)r1 >= drop_below && !(v.z <= 0.f), k3 = (uint32_t)(r1 >> 32) >= drop_below && !(v.w <= 0.f);
     v4f o;
     o.x = k0 ? v.x * scale : 0.f;
     o.y = k1 ? v.y * scale : 0.f;

@@ -152,8 +152,9 @@ __global__ __launch_bounds__(kRgBlock, rows_gemm_waves(KS, MT, V4, ACT)) void ro
             const uint64_t i = (uint64_t)row * (uint64_t)(M / 4) + (uint64_t)(m0 / 4);
             const uint64_t q0 = splitmix64(act.seed ^ ((act.offset + i) * 2));
             const uint64_t q1 = splitmix64(act.seed ^ ((act.offset + i) * 2 + 1));
-            const bool k0 = (uint32_t)q0 >= act.drop_below && v[0] > 0.f, k1 = (uint32_t)(q0 >> 32) >= act.drop_below && v[1] > 0.f;
-            const bool k2 = (uint32_t)q1 >= act.drop_below && v[2] > 0.f, k3 = (uint32_t)(q1 >> 32) >= act.drop_below && v[3] > 0.f;
+            // (!(v <= 0), as relu_dropout_fwd_kernel: a NaN at a kept position stays NaN with its bit set)
+            const bool k0 = (uint32_t)q0 >= act.drop_below && !(v[0] <= 0.f), k1 = (uint32_t)(q0 >> 32) >= act.drop_below && !(v[1] <= 0.f);
+            const bool k2 = (uint32_t)q1 >= act.drop_below && !(v[2] <= 0.f), k3 = (uint32_t)(q1 >> 32) >= act.drop_below && !(v[3] <= 0.f);
             v4f o;
             o.x = k0 ? v[0] * act.scale : 0.f;
             o.y = k1 ? v[1] * act.scale : 0.f;

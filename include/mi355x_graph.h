@@ -422,7 +422,8 @@ int32_t mgx_gat_attention_bwd(const mgx_csr* csr, const mgx_spmm_plan* plan /* m
  * feat [num_cols, H*F], el [num_cols, H], er [num_rows, H], out / d_out [num_rows, H*F], nstat [num_rows, H, 4], 16-byte
  * aligned; F in {4, 8, ..., 256} with H*F <= 256, or ONE head of any width 4 < F <= 256 (e.g. a 41-class output layer: rows moved
  * in dword-aligned 16-byte windows); 32-bit indices (else MGX_ERR_UNSUPPORTED: callers fall back to mgx_gat_attention_* +
- * mgx_spmm_csr).  keep(e,h) = hash(seed, e*H + h) >= p * 2^32 (counter based; drop_p = 0: no mask).
+ * mgx_spmm_csr).  keep(e,h) = hash(seed, edge id e, head h) >= p * 2^32 (counter based; drop_p = 0: no mask), e = eids[q] of
+ * CSR position q, or q itself when eids is NULL; the hash is a 32-bit mixer of the two key words (gat_hash in csrc/gatfused.hip).
  * workspace: max over the plans passed of mgx_gat_fused_workspace(plan, H, F) bytes (NULL when no plan splits rows).
  * pack_ws (may be NULL): mgx_gat_fused_pack_workspace(num_src, num_dst, H, F) bytes of scratch; when given and the layer is
  *   narrow enough that a node's feature row and its per-head attention terms fit the row's 128-byte lines (one head of
@@ -649,7 +650,13 @@ int32_t mgx_rows_gemm_relu_dropout(int64_t n, int64_t K, int64_t M, const float*
 /* y = dropout_p(relu(x)) in one pass (inverted dropout: kept values scaled by 1/(1-p)); the activation between two
  * aggregations (main_dgl_product_sage.py:93-95).  n elements, n % 4 == 0, 16-byte aligned; mask: n/4 bytes, 4 bits per
  * float4 = (x > 0 AND kept), all that backward needs: dx = mask ? dy/(1-p) : 0.  Random bits are a counter-based function
- * of (seed, offset + element index): the caller advances `offset` by n between calls. */
+ * of (seed, offset + element index): the caller advances `offset` by n between calls.
+ * The stream: float4 number i of the dense tensor draws r0 = splitmix64(seed ^ ((offset + i) * 2)) and r1 = splitmix64(seed ^
+ * ((offset + i) * 2 + 1)), modulo 2^64; x, y, z, w are kept when (uint32)r0, r0 >> 32, (uint32)r1, r1 >> 32 are >= uint32(p * 2^32).
+ * NaN rule: "x > 0" is evaluated as !(x <= 0), so a NaN is never turned into a clean zero.  At a kept position it gives NaN with
+ * its mask bit SET (backward passes dy/(1-p) there); at a dropped position 0 with a clear bit.  Finite and infinite inputs are not
+ * affected.  mgx_rows_gemm_relu_dropout follows the same rule, and what derives sparsity from y (mgx_rows_slots_pack*,
+ * mgx_row_nonzero_bits, mgx_rows_pack_count) tests != 0, which counts a NaN as a value. */
 int32_t mgx_relu_dropout_fwd(int64_t n, const float* x, float p, uint64_t seed, uint64_t offset, float* y, uint8_t* mask,
                              void* stream);
 int32_t mgx_relu_dropout_bwd(int64_t n, const float* dy, const uint8_t* mask, float p, float* dx, void* stream);
