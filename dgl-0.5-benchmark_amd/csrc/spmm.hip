@@ -1027,6 +1027,7 @@ static bool try_spmm_slots(const SpmmFastArgs<int32_t>& a, const void* slots, hi
   // short items whose rows carry no factor keep the dense lane-group kernel (products head: 0.32 - 0.33 ms against 0.37 - 0.38 ms on
   // the slot form: a 3-edge row is a dependent chain either way); with a factor the slots are the only operand that has it applied
   if (a.short_rows && !a.src_scale) return false;
+  if (a.init_pos && a.src_rows == 0) return false;  // (the probe kernel reads slot 0 for the lanes past an item's end)
   launch_spmm_slots(a, slots, s);
   return true;
 }

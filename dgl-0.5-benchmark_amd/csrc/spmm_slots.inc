@@ -160,151 +160,161 @@ __global__ __launch_bounds__(kBlock) void spmm_slots_kernel(const SpmmFastArgs<i
 }
 
 // mgx_spmm_copy_u_slots_init: the INIT launch of spmm_rowwave32_kernel<4, 16, ...> (plain copy_u sum whose initial value comes from a compact
-// matrix, `out` write-only) over slots -- for a gathered matrix most of whose ROWS are zero (d neigh / deg of a loss taken on 8 % of the
-// nodes): an empty slot is one line per edge instead of the dense row's two and adds nothing.
+// matrix, `out` write-only) for a gathered matrix most of whose ROWS are zero (d neigh / deg of a loss taken on 8 % of the nodes).  The
+// slots are the PROBE: the lane that holds an edge's id fetches the first meta word of that source's slot -- one line per edge -- and the
+// row is LIVE iff that word carries the flag 255 or a column below 64 (slot_pack_rows4 fills group 0 first: exactly "the row has a
+// non-zero").  A live row is gathered whole from the dense matrix, zeros included, whether its slot holds values or the flag; a dead
+// edge costs its probe and nothing else.
 //
-// The sum has the dense INIT launch's bits, which fixes the order of additions: that kernel keeps four accumulators, edge e of an item
-// (counted from the item's first edge) is added to accumulator e % 4 in increasing e, accumulator 0 starts from the initial value, and
-// the result is (A0 + A1) + (A2 + A3).  Here the four accumulators are four LDS rows of the wave.  Lane group g of a step holds edge
-// k + 8 u + g (k a multiple of 16), so groups g and g + 4 feed accumulator g & 3: the lower half of the wave adds first, then the upper
-// half (a wave's LDS operations execute in order), u ascending.  An empty slot adds nothing -- eight empty slots skip the whole path,
-// tested wave-uniformly --; a slot with values adds them at their columns by read - add - write; a flagged slot (more than 24
-// non-zeros) adds the dense row.  A skipped addend is an exact +0.0f, so the result is the dense launch's bit for bit wherever no
-// element of the operands is -0.0f, and equal as a number otherwise (only the sign of an exactly-zero result can differ).
+// The sum has the dense INIT launch's bits, which fixes the order of additions: that kernel keeps one float4 accumulator per lane group
+// (16 lanes, four groups), edge e of an item (counted from the item's first edge) is added to group e % 4's in increasing e, group 0's
+// starts from the initial value, and the result is (A0 + A1) + (A2 + A3) through the xor-shuffle tree.  Here lane group s walks the
+// LIVE edges among e = s, s + 4, s + 8, ... of a 64-edge chunk in increasing e, four per step -- its own bits of the chunk's live ballot,
+// lowest first -- so every accumulator receives the addends of the dense launch in the dense launch's order, minus the rows that are
+// all zero.  Such a row's addend is +0.0f in every column.  x + (+0.0f) is x for every x but -0.0f, and an accumulator that is -0.0f at
+// the end of an item leaves the result unchanged too: A1 .. A3 start from +0.0f and a sum that started from +0.0f is never -0.0f, so
+// A0 = -0.0f and A0 = +0.0f give the same (A0 + A1).  Edges are never moved between lane groups (that is spmm_rowwave32_kernel's
+// MASKED form, another sum).
 //
-// Schedule: spmm_slots_kernel's (two steps of 16 slots in ping-pong); the dense rows of a step's flagged slots are read where they are
-// added, both halves' at once.  (Requesting them one step ahead -- a third stage, 108 - 138 VGPRs at U = 2, 70 at U = 1 -- was
-// measured on the products graph with 8 % dense rows and lost to this form and to the dense launch: docs/LOG_head_slots.md.)
-template <int U>
-__global__ __launch_bounds__(kBlock) void spmm_slots_init_kernel(const SpmmFastArgs<int32_t> a, const char* __restrict__ slots) {
-  __shared__ __attribute__((aligned(16))) float acc_all[kWavesPerBlock][4][kSlotAccStride];
+// Schedule: the bounds and map entries of all of a wave's items are fetched at once, one item per lane.  The items then are one stream of
+// 64-edge chunks with three of them open -- the ids of chunk c + 2 and the probes of chunk c + 1 are requested before the gathers of
+// chunk c and consumed after them, so neither round trip is paid per chunk or per item.  With 8 % live rows a lane group has 1.3 live
+// edges per chunk, so one step of four gathers per group covers a chunk (more than four live among a group's sixteen: 0.7 % of the
+// groups) and one value buffer is enough: 42 VGPRs, 8 waves per SIMD.  (Two buffers in ping-pong as in spmm_rowwave32_kernel: 78 VGPRs,
+// 6 waves, 1.54 ms against 1.51 ms for the whole call on the products graph -- docs/LOG_head_probe.md.)  Every gather is unconditional:
+// a lane group with no live edge left reads the matrix's first 16 bytes (one hot line for all such lanes of the wave) and the value is
+// dropped where it is consumed, so the wait counts stay exact.  No LDS.
+__device__ __forceinline__ bool slot_meta_live(uint32_t meta) { return (meta >> 24) == 255u || (meta & 0xffu) < 64u; }
+
+__global__ __launch_bounds__(kBlock) void spmm_probe_init_kernel(const SpmmFastArgs<int32_t> a, const char* __restrict__ slots) {
+  constexpr int G = 16, U = 4;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int grp = lane >> 3, gi = lane & 7;
-  float* accw = &acc_all[wave][0][0];
-  float* accg = accw + (grp & 3) * kSlotAccStride;
-  for (int i = lane; i < 4 * kSlotAccStride; i += kWave) accw[i] = 0.f;
+  const int sub = lane / G;
+  const uint32_t f4 = (uint32_t)(lane % G) * 16u;
   int64_t item_base, item_stop;
   xcd_stretch(a.xcd, item_base, item_stop);
-  item_base += (int64_t)(blockIdx.x / kXcds) * a.rpb;
-  int r = wave;
-  if (r >= a.rpb || item_base + r >= item_stop) return;
-  const uint32_t laneoff = (uint32_t)gi * 16u;
-  const char* __restrict__ srcb = reinterpret_cast<const char*>(a.src);
+  item_base += (int64_t)(blockIdx.x / kXcds) * a.rpb + wave;  // this wave's items: item_base + kWavesPerBlock * i
   const uint32_t rowbytes = (uint32_t)a.lds * 4u;
+  const char* __restrict__ srcb = reinterpret_cast<const char*>(a.src);
 
-  auto load_meta = [&](int64_t item, int64_t& row, int32_t& beg, int32_t& end, int32_t& ipos) {
-    if (a.item_row) {
-      row = (int64_t)a.item_row[item];
-      beg = a.item_beg[item];
-      end = a.item_end[item];
+  // The wave's items all at once, item i in lane i (at most 64: launch_spmm_slots keeps rpb <= 64 * kWavesPerBlock): one round trip for the
+  // bounds of all of them and one for their map entries, instead of that chain per item.
+  int32_t rowv = 0, begv = 0, endv = 0, iposv = -1;
+  {
+    const int r = wave + kWavesPerBlock * lane;
+    const int64_t item = item_base + (int64_t)kWavesPerBlock * lane;
+    if (r < a.rpb && item < item_stop) {
+      if (a.item_row) {
+        rowv = a.item_row[item];
+        begv = a.item_beg[item];
+        endv = a.item_end[item];
+        if (rowv >= 0) iposv = (int32_t)a.init_pos[rowv];  // (a chunk of a split row starts from zero: its row's value enters in the fix-up)
+      } else {
+        begv = a.indptr[item];
+        endv = a.indptr[item + 1];
+        iposv = (int32_t)a.init_pos[item];
+      }
+    }
+  }
+  const int n_mine = __popcll(__ballot(wave + kWavesPerBlock * lane < a.rpb && item_base + (int64_t)kWavesPerBlock * lane < item_stop));
+  if (n_mine == 0) return;
+
+  struct Chunk {  // 64 edges [cbase, min(cbase + 64, end)) of the wave's item i (an item without edges: one empty chunk)
+    int i;
+    bool ok;
+    int32_t beg, end, cbase;
+  };
+  auto open_item = [&](Chunk& c) {
+    c.ok = c.i < n_mine;
+    c.beg = 0; c.end = 0;
+    if (c.ok) {
+      c.beg = __builtin_amdgcn_readlane(begv, c.i);
+      c.end = __builtin_amdgcn_readlane(endv, c.i);
+    }
+    c.cbase = c.beg;
+  };
+  auto next_chunk = [&](Chunk& c) {
+    if (!c.ok) return;
+    if (c.cbase + kWave < c.end) {
+      c.cbase += kWave;
     } else {
-      row = item;
-      beg = a.indptr[item];
-      end = a.indptr[item + 1];
+      c.i += 1;
+      open_item(c);
     }
-    ipos = row >= 0 ? (int32_t)a.init_pos[row] : -1;  // (a chunk of a split row starts from zero: its row's value enters in the fix-up)
   };
-  auto load_ids = [&](int32_t base, int32_t end) -> uint32_t {
-    const int32_t q = base + lane;
-    return q < end ? (uint32_t)__builtin_nontemporal_load(&a.indices[q]) * (uint32_t)kSlotBytes : 0u;
+  auto load_ids = [&](const Chunk& c) -> uint32_t {  // lane j: source row of edge cbase + j (0 past the end)
+    const int32_t q = c.cbase + lane;
+    return (c.ok && q < c.end) ? (uint32_t)__builtin_nontemporal_load(&a.indices[q]) : 0u;
   };
-  // the gathers of one step: 8 U edges from edge k of the current 64-edge chunk on, one 16-byte piece of a slot per lane
-  auto issue = [&](int k, int cnt, uint32_t goff, v4f (&val)[U], uint32_t (&roff)[U]) {
+  auto probe = [&](uint32_t gid) -> uint32_t {  // unconditional: a lane past the end reads slot 0
+    return *reinterpret_cast<const uint32_t*>(slots + gid * (uint32_t)kSlotBytes);
+  };
+  // one step of a lane group: its next four live edges, lowest first; `m` = the group's live edges still to gather, bit 4 t = edge 4 t + sub
+  auto issue_step = [&](uint64_t& m, uint32_t goff, v4f (&val)[U], uint32_t& has) {
+    has = 0;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const int e = k + u * 8 + grp;
-      roff[u] = (uint32_t)__builtin_amdgcn_ds_bpermute((e < cnt ? e : 0) * 4, (int)goff);
-      val[u] = *reinterpret_cast<const v4f*>(slots + roff[u] + laneoff);
+      const bool h = m != 0;
+      const int e = h ? (int)__builtin_ctzll(m) + sub : 0;
+      m &= m - 1;
+      const uint32_t g = (uint32_t)__builtin_amdgcn_ds_bpermute(e * 4, (int)goff);
+      val[u] = *reinterpret_cast<const v4f*>(srcb + (h ? g + f4 : 0u));
+      has |= (h ? 1u : 0u) << u;
     }
   };
-  auto consume = [&](int k, int cnt, const v4f (&val)[U], const uint32_t (&roff)[U]) {
+  auto consume_step = [&](const v4f (&val)[U], uint32_t has, v4f& acc) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const bool live = k + u * 8 + grp < cnt;
-      const uint32_t meta = (uint32_t)__float_as_int(val[u].x);
-      const uint32_t c0 = meta & 0xffu, c1 = (meta >> 8) & 0xffu, c2 = (meta >> 16) & 0xffu;
-      const bool dense = live && (meta >> 24) == 255u;
-      const bool valued = live && !dense && c0 < 64u;  // (a lane's values fill c0 first)
-      const uint64_t busy = __ballot(dense || valued);
-      if (busy == 0) continue;  // eight empty slots: nothing to add
-      v4f d0 = (v4f)(0.f), d1 = (v4f)(0.f);
-      if (dense) {  // more than 24 non-zeros: the dense row, 8 columns per lane
-        const char* dr = srcb + ((roff[u] / (uint32_t)kSlotBytes) * rowbytes + (uint32_t)gi * 32u);
-        d0 = *reinterpret_cast<const v4f*>(dr);
-        d1 = *reinterpret_cast<const v4f*>(dr + 16);
-      }
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {  // groups g before groups g + 4: the order of the additions to accumulator g & 3
-        if (((busy >> (32 * half)) & 0xffffffffull) == 0) continue;
-        if ((grp >> 2) == half) {
-          if (valued) {
-            const float a0 = accg[c0], a1 = accg[c1], a2 = accg[c2];  // (column 64 = the padding element of the accumulator row)
-            accg[c0] = a0 + val[u].y;
-            if (c1 < 64u) accg[c1] = a1 + val[u].z;
-            if (c2 < 64u) accg[c2] = a2 + val[u].w;
-          } else if (dense) {
-            v4f* ar = reinterpret_cast<v4f*>(accg + gi * 8);
-            ar[0] += d0;
-            ar[1] += d1;
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
+    for (int u = 0; u < U; ++u) acc += ((has >> u) & 1u) ? val[u] : (v4f)(0.f);
   };
 
-  int64_t row;
-  int32_t beg, end, ipos;
-  load_meta(item_base + r, row, beg, end, ipos);
-  uint32_t goff = load_ids(beg, end);
+  Chunk c0;
+  c0.i = 0;
+  open_item(c0);
+  uint32_t g0 = load_ids(c0);
+  Chunk c1 = c0;
+  next_chunk(c1);
+  uint32_t g1 = load_ids(c1);
+  bool live0 = c0.cbase + lane < c0.end && slot_meta_live(probe(g0));
+  Chunk c2 = c1;
+  v4f acc = (v4f)(0.f);
   for (;;) {
-    // the initial value is requested before anything else of the item and enters accumulator 0 behind the first step's gathers
-    float iv = 0.f;
-    if (ipos >= 0) iv = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.init) + ((uint32_t)ipos * ((uint32_t)a.ldi * 4u) + (uint32_t)lane * 4u));
-    const int rn = r + kWavesPerBlock;
-    const bool has_next = rn < a.rpb && item_base + rn < item_stop;
-    int64_t nrow = 0;
-    int32_t nbeg = 0, nend = 0, nipos = -1;
-    uint32_t ngoff = 0;
-    if (has_next) {
-      load_meta(item_base + rn, nrow, nbeg, nend, nipos);
-      ngoff = load_ids(nbeg, nend);
+    next_chunk(c2);
+    const uint32_t g2 = load_ids(c2);
+    const uint32_t p1 = probe(g1);
+    // the initial value is requested before the item's gathers, as lane group 0's accumulator (spmm_rowwave32_kernel's reason)
+    if (c0.cbase == c0.beg) {
+      const int32_t ipos = __builtin_amdgcn_readlane(iposv, c0.i);
+      acc = (v4f)(0.f);
+      if (ipos >= 0 && sub == 0)
+        acc = *reinterpret_cast<const v4f*>(reinterpret_cast<const char*>(a.init) + ((uint32_t)ipos * ((uint32_t)a.ldi * 4u) + f4));
     }
-    for (int32_t cbase = beg; cbase < end; cbase += kWave) {
-      if (cbase != beg) goff = load_ids(cbase, end);
-      const int cnt = (end - cbase) < kWave ? (end - cbase) : kWave;
-      v4f va[U], vb[U];
-      uint32_t ra[U], rb[U];
-      issue(0, cnt, goff, va, ra);
-      if (cbase == beg) accw[lane] = iv;
-      int k = 0;
-      for (;;) {
-        if (k + 8 * U >= cnt) { consume(k, cnt, va, ra); break; }
-        issue(k + 8 * U, cnt, goff, vb, rb);
-        consume(k, cnt, va, ra);
-        k += 8 * U;
-        if (k + 8 * U >= cnt) { consume(k, cnt, vb, rb); break; }
-        issue(k + 8 * U, cnt, goff, va, ra);
-        consume(k, cnt, vb, rb);
-        k += 8 * U;
+    const uint64_t lb = __ballot(live0);
+    if (lb != 0) {  // (a chunk without a live source adds nothing)
+      const uint32_t goff = g0 * rowbytes;
+      uint64_t m = (lb >> sub) & 0x1111111111111111ull;
+      do {
+        v4f val[U];
+        uint32_t has;
+        issue_step(m, goff, val, has);
+        consume_step(val, has, acc);
+      } while (__ballot(m != 0) != 0);
+    }
+    if (c0.cbase + kWave >= c0.end) {  // the item's last chunk
+#pragma unroll
+      for (int off = G; off < kWave; off <<= 1) acc += vec_shfl_xor<4>(acc, off);
+      if (sub == 0) {
+        const int64_t row = a.item_row ? (int64_t)__builtin_amdgcn_readlane(rowv, c0.i) : item_base + (int64_t)kWavesPerBlock * c0.i;
+        if (row >= 0) __builtin_nontemporal_store(acc, reinterpret_cast<v4f*>(a.out + row * (int64_t)a.ldo + (f4 >> 2)));
+        else *reinterpret_cast<v4f*>(a.partial + (-(row + 1)) * (int64_t)64 + (f4 >> 2)) = acc;
       }
     }
-    float A[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      A[j] = accw[j * kSlotAccStride + lane];
-      accw[j * kSlotAccStride + lane] = 0.f;
-    }
-    if (end <= beg) A[0] = iv;  // no edge: the initial value never reached the accumulator
-    const float res = (A[0] + A[1]) + (A[2] + A[3]);
-    if (row >= 0) __builtin_nontemporal_store(res, a.out + row * (int64_t)a.ldo + lane);
-    else a.partial[(-(row + 1)) * (int64_t)64 + lane] = res;
-    if (!has_next) break;
-    r = rn;
-    row = nrow; beg = nbeg; end = nend; ipos = nipos;
-    goff = ngoff;
+    if (!c1.ok) break;
+    live0 = c1.cbase + lane < c1.end && slot_meta_live(p1);
+    c0 = c1;
+    c1 = c2;
+    g0 = g1;
+    g1 = g2;
   }
 }
 
@@ -505,10 +515,11 @@ static bool spmm_slots_eligible(const SpmmFastArgs<int32_t>& a) {
 // items (a.short_rows: a lane group per item)
 static void launch_spmm_slots(SpmmFastArgs<int32_t> a, const void* slots, hipStream_t s) {
   if (a.init_pos) {  // mgx_spmm_copy_u_slots_init (its entry point checked; short items never come here: they carry no src_scale)
+    static_assert(kItemsPerBlock <= 64 * kWavesPerBlock, "spmm_probe_init_kernel holds a wave's items one per lane");
     a.rpb = kItemsPerBlock;
     const dim3 grid((unsigned)xcd_ranges(a.plan, a.n_items, a.rpb, a.xcd));
     note_spmm_kernel("slots");
-    hipLaunchKernelGGL((spmm_slots_init_kernel<2>), grid, dim3(kBlock), 0, s, a, (const char*)slots);
+    hipLaunchKernelGGL(spmm_probe_init_kernel, grid, dim3(kBlock), 0, s, a, (const char*)slots);
     return;
   }
   if (a.short_rows) {

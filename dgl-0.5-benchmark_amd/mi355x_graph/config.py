@@ -22,8 +22,11 @@ SAGE_PROJECT_FIRST = True  # project before aggregating when that moves fewer co
 SAGE_HEAD_ROWS = True      # the last layer's dense work on the loss rows only (ops.SageMeanCatHeadFn; MGX_SAGE_HEAD_ROWS=0 turns it off)
 SAGE_HEAD_INIT = True      # ... its reversed aggregation started from the compact d self (mgx_spmm_copy_u_strided_init), d neigh / deg scattered into
                            # one [N, K] matrix kept zero elsewhere between steps (ops._head_dn): no zero fill, no copy of d self into one
-SAGE_HEAD_SLOTS = True     # ... and, on a graph of PACKED_GATHER_MIN_NNZ edges with K = 64, gathering that matrix as 128-byte slots kept beside it: an
-                           # empty slot per zero row, the dense row on a flag (mgx_spmm_copy_u_slots_init, same bits; MGX_SAGE_HEAD_SLOTS=0 turns it off)
+SAGE_HEAD_SLOTS = True     # ... and, on a graph of PACKED_GATHER_MIN_NNZ edges with K = 64, gathering that matrix behind its 128-byte slots kept beside it: an
+                           # empty slot's first word per zero row, the dense row otherwise (mgx_spmm_copy_u_slots_init, same bits; MGX_SAGE_HEAD_SLOTS=0 turns it off)
+SAGE_HEAD_SLOTS_MIN_NNZ = 12_000_000  # ... from this many edges on (or PACKED_GATHER_MIN_NNZ where that is lower): products shape x 0.1 / 0.2 / 0.3 / 0.5 / 1,
+                           # dense call 0.225 / 0.412 / 0.635 / 1.091 / 2.289 ms, this call 0.162 / 0.291 / 0.445 / 0.731 / 1.506 ms (docs/LOG_head_probe.md);
+                           # not measured below 12 M edges
 ROWS_GEMM = True           # mgx_rows_gemm for the projections of a layer over >= 65 536 rows (else the library GEMM)
 LINEAR_XTY = True          # tall-skinny weight gradients by mgx_xty (else the library GEMM)
 XTY_COLSUM = True          # ... with the bias gradient from the same pass (mgx_xty_colsum)

@@ -1315,8 +1315,8 @@ def _head_dn(csr, K, rows, n, like, be):
     Internal to the node: the aggregation reads it, autograd never sees it.  Inside a HIP-graph capture the step gets a zero matrix
     of its own, filled in the captured step: a replay runs none of this bookkeeping, and eager steps with other lists in between
     must not leave their rows in what it reads.
-    config.SAGE_HEAD_SLOTS (_head_slots_wanted): the matrix's 128-byte slots are kept beside it, for the aggregation to gather instead of
-    the dense rows (mgx_spmm_copy_u_slots_init) -- all of them packed when the matrix is created or cleared as a whole, the slots of a
+    config.SAGE_HEAD_SLOTS (_head_slots_wanted): the matrix's 128-byte slots are kept beside it, for the aggregation to probe before it
+    gathers a dense row (mgx_spmm_copy_u_slots_init) -- all of them packed when the matrix is created or cleared as a whole, the slots of a
     previous list's rows packed again (empty) when those rows are cleared; the step's rows are packed by the caller once the scatter has
     written them (_head_dn_slots).  A captured step has no slots."""
     if torch.cuda.is_current_stream_capturing():
@@ -1349,7 +1349,7 @@ def _head_dn(csr, K, rows, n, like, be):
 def _head_slots_wanted(csr, K, be):
     """Does the reversed aggregation of SageMeanCatHeadFn gather d neigh / deg over `csr` as 128-byte slots (config.SAGE_HEAD_SLOTS)?"""
     return (config.SAGE_HEAD_SLOTS and config.SAGE_HEAD_INIT and os.environ.get("MGX_SAGE_HEAD_SLOTS", "1") != "0" and K == 64
-            and csr.nnz >= config.PACKED_GATHER_MIN_NNZ and hasattr(be, "spmm_copy_u_slots_init") and hasattr(be, "rows_slots_pack_rows"))
+            and csr.nnz >= min(config.SAGE_HEAD_SLOTS_MIN_NNZ, config.PACKED_GATHER_MIN_NNZ) and hasattr(be, "spmm_copy_u_slots_init") and hasattr(be, "rows_slots_pack_rows"))
 
 
 def _head_dn_slots(csr, dn):
@@ -1418,7 +1418,7 @@ class SageMeanCatHeadFn(torch.autograd.Function):
     Both aggregations are untouched: every row is aggregated forward, and the reversed one gathers every source row over every edge
     from d neigh / deg, which is zero outside the rows: an [N, K] matrix the GEMM scatters into, kept zero elsewhere from step to step
     (_head_dn) -- as 128-byte slots kept beside it on a big graph with K = 64 (config.SAGE_HEAD_SLOTS, mgx_spmm_copy_u_slots_init: the
-    slot of a zero row is empty, a dense row is read on its slot's flag), else as the dense rows.  Its sums start from d self, which
+    slot of a zero row is empty and ends that edge's work, any other slot sends the walk to the dense row), else as the dense rows.  Its sums start from d self, which
     stays the compact [R, K] matrix the GEMM wrote: the aggregation takes it through the position map
     (mgx_spmm_copy_u_strided_init) and writes every row of d h once.  config.SAGE_HEAD_INIT = False, or operands that entry point declines: a zero-filled [N, K] per step, d self copied into a second one, the accumulating aggregation.
     Every sum is formed in the order the layer over all rows forms it, so the gradients are that layer's bit for bit.  No atomics,
@@ -1441,8 +1441,8 @@ class SageMeanCatHeadFn(torch.autograd.Function):
             # config.SAGE_HEAD_INIT: the same sums started from the compact d self through the position map
             # (mgx_spmm_copy_u_strided_init) -- no zero matrix, no copy into it, no read of it; the sequence below where it declines
             if config.SAGE_HEAD_INIT and d_self.stride(1) == 1:
-                # config.SAGE_HEAD_SLOTS: ... gathering the slots kept beside d neigh / deg -- one line per edge, nothing to add for the
-                # 92 % of the source rows that are zero, the dense row on a slot's flag (mgx_spmm_copy_u_slots_init); the same bits
+                # config.SAGE_HEAD_SLOTS: ... probing the slots kept beside d neigh / deg -- one line per edge, nothing more for the 92 %
+                # of the source rows that are zero, the dense row where the slot is not empty (mgx_spmm_copy_u_slots_init); the same bits
                 slots = _head_dn_slots(ctx.gidx.csr(), dn)
                 if slots is not None:
                     dh = be.spmm_copy_u_slots_init(ctx.gidx.csr(), "sum", dn, slots, d_self, _row_pos(rows, dn.shape[0]), torch.empty_like(dn))

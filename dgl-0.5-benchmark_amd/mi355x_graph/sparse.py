@@ -643,9 +643,9 @@ class HipBackend(object):
         return slots
 
     def spmm_copy_u_slots_init(self, csr, reduce, U2d, slots, init2d, init_pos, out2d, dst_scale=None):
-        """spmm_copy_u_strided_init with `slots` = rows_slots_pack(U2d)[0] beside U2d: the wave-per-item work items gather one 128-byte slot
-        per edge, add nothing for an empty one and read the dense row of a flagged one -- for a U2d most of whose rows are zero
-        (mgx_spmm_copy_u_slots_init).  The bits of spmm_copy_u_strided_init wherever no element of U2d / init2d is -0.0.  Returns out2d,
+        """spmm_copy_u_strided_init with `slots` = rows_slots_pack(U2d)[0] beside U2d: the wave-per-item work items probe the first word of
+        every source row's slot (one line per edge) and gather the dense row only where the slot is not empty -- for a U2d most of whose
+        rows are zero (mgx_spmm_copy_u_slots_init).  The bits of spmm_copy_u_strided_init wherever no element of U2d / init2d is -0.0.  Returns out2d,
         or None when the library has no kernel for these operands (what spmm_copy_u_strided_init declines, and D != 64)."""
         dev = self._check_dev(csr.indptr, U2d, slots, init2d, init_pos, out2d, dst_scale)
         D = int(U2d.shape[1])

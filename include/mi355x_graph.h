@@ -264,13 +264,14 @@ int32_t mgx_spmm_copy_u_slots(const mgx_csr* csr, const mgx_spmm_plan* plan /* m
 /* mgx_spmm_copy_u_slots_init is mgx_spmm_copy_u_strided_init with the slots beside the dense matrix (slots = pack(ufeat), no factor),
  * for a gathered matrix most of whose ROWS are zero -- d neigh / deg of a loss taken on 8 % of the nodes:
  *     out[v] = (init[init_pos[v]] where init_pos[v] >= 0, else +0.0f) + SUM_{u -> v} ufeat[u, :]          (`out` is write-only)
- * A wave-per-item work item gathers one 128-byte slot per edge; an empty slot adds nothing, a slot with values adds them at their
- * columns, a flagged slot adds the dense row of `ufeat`.  The additions per output element are made in the order of the dense call --
- * four accumulators, edge e of an item to accumulator e % 4, the initial value first in accumulator 0, (A0 + A1) + (A2 + A3) -- and a
- * skipped addend is an exact +0.0f, so the result is that of mgx_spmm_copy_u_strided_init on the same graph and plan
+ * A wave-per-item work item uses the slots as a per-edge PROBE: it fetches the first word of every source row's slot (one line per
+ * edge) and gathers the dense row of `ufeat` for the rows whose slot holds a value or the flag; a row whose slot is empty costs its
+ * probe only.  The additions per output element are made in the order of the dense call -- four accumulators, edge e of an item to
+ * accumulator e % 4, the initial value first in accumulator 0, (A0 + A1) + (A2 + A3); a live row is added whole -- and a skipped
+ * addend is an exact +0.0f, so the result is that of mgx_spmm_copy_u_strided_init on the same graph and plan
  *     bit for bit wherever no element of `ufeat` and `init` is -0.0f;
- *     equal as numbers otherwise (mgx_rows_slots_pack drops a -0.0f, and a skipped +0.0f would have turned a running sum of -0.0f into
- *     +0.0f): only the sign of an exactly-zero result can differ.
+ *     equal as numbers otherwise (mgx_rows_slots_pack drops a -0.0f, so a row of nothing but zeros of either sign is skipped): only the
+ *     sign of an exactly-zero result can differ.
  * The short items of a two-part plan (MGX_SPMM_SHORT_ROWS) read the dense rows, as in mgx_spmm_copy_u_slots without a factor.
  * reduce = MGX_REDUCE_SUM, dst_scale = NULL, int32 graph, D = 64, fewer than 2^25 source rows, and the alignment / stride / size
  * conditions of the two entries it combines; anything else returns MGX_ERR_UNSUPPORTED before a launch.
