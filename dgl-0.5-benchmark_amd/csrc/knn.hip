@@ -19,16 +19,14 @@
 // wave_bitonic_merge as in the wave form of segtopk.hip.  Only ranks below k are exact in either path: a skipped chunk may have held ranks
 // k .. 63.  A wave whose four segments do not meet the chunk skips the arithmetic (never the barriers).
 // Nothing is read on the host and the launch depends on N only: capture-safe.  No atomics: reruns are bitwise equal.
+// The segment search, the tile staging and the distance terms are knn_stream.h, shared with ballquery.hip.
+#include "knn_stream.h"
 #include "wave_select.h"
 
 namespace mgx {
 
 constexpr int kKnnMaxK = kWave;  // one rank per lane
 constexpr int kKnnMaxD = 256;
-constexpr int kKnnQueries = 16;  // query rows per workgroup
-constexpr int kKnnPerWave = kKnnQueries / kWavesPerBlock;
-constexpr int kKnnCols = 32;     // columns staged per pass
-constexpr int kKnnTileLd = kWave + 1;
 constexpr int kKnnInsertMax = 8;  // candidates of a chunk under the current k-th that are inserted one by one; more: sort and merge
 
 __global__ __launch_bounds__(kBlock) void segment_knn_kernel(int64_t S, const int64_t* __restrict__ offsets, int64_t N, int D, int64_t ld,
@@ -39,23 +37,9 @@ __global__ __launch_bounds__(kBlock) void segment_knn_kernel(int64_t S, const in
   const int tid = threadIdx.x, lane = tid & (kWave - 1);
   const int w = __builtin_amdgcn_readfirstlane(tid / kWave);
   const int64_t q0 = (int64_t)blockIdx.x * kKnnQueries;
-  if (tid < kKnnQueries) {  // the segment of query row q0 + tid: the last s with offsets[s] <= row, clamped to the N rows there are
-    const int64_t row = q0 + tid;
-    int64_t beg = 0, end = 0;
-    if (row < N) {
-      int64_t lo = 0, hi = S + 1;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (offsets[mid] > row) hi = mid; else lo = mid + 1;
-      }
-      if (lo >= 1 && lo <= S) {
-        beg = offsets[lo - 1];
-        end = offsets[lo];
-      }
-      end = end < N ? end : N;
-      beg = beg < 0 ? 0 : beg;
-      if (!(beg <= row && row < end)) beg = end = 0;  // a row no segment holds: k ranks of padding
-    }
+  if (tid < kKnnQueries) {  // the segment of query row q0 + tid; a row no segment holds: k ranks of padding
+    int64_t beg, end;
+    knn_segment_of(S, offsets, N, q0 + tid, beg, end);
     sbeg[tid] = beg;
     send[tid] = end;
   }
@@ -93,28 +77,10 @@ __global__ __launch_bounds__(kBlock) void segment_knn_kernel(int64_t S, const in
     for (int d0 = 0; d0 < D; d0 += kKnnCols) {
       const int dc = D - d0 < kKnnCols ? D - d0 : kKnnCols;
       __syncthreads();  // the previous tile has been read
-      if (dc == kKnnCols) {
-        const int c = tid & (kKnnCols - 1);
-#pragma unroll
-        for (int r = tid / kKnnCols; r < kWave; r += kBlock / kKnnCols)
-          tile[c * kKnnTileLd + r] = r < rows ? x[(c0 + r) * ld + d0 + c] : 0.f;
-      } else {
-        for (int e = tid; e < kWave * dc; e += kBlock) {
-          const int r = e / dc, c = e - r * dc;
-          tile[c * kKnnTileLd + r] = r < rows ? x[(c0 + r) * ld + d0 + c] : 0.f;
-        }
-      }
+      knn_stage_tile(tile, x, ld, c0, rows, d0, dc, tid);
       __syncthreads();
       if (!mine) continue;
-#pragma unroll 8
-      for (int c = 0; c < dc; ++c) {
-        const float v = tile[c * kKnnTileLd + lane];
-#pragma unroll
-        for (int q = 0; q < kKnnPerWave; ++q) {
-          const float diff = xq[q][d0 + c] - v;
-          acc[q] = __builtin_fmaf(diff, diff, acc[q]);
-        }
-      }
+      knn_tile_terms(tile, lane, d0, dc, xq, acc);
     }
     if (!mine) continue;
     const int64_t g = c0 + lane;

@@ -9,7 +9,7 @@ from mi355x_graph.transform import (to_bidirected, add_self_loop, remove_self_lo
 from mi355x_graph import function, ops, readout  # noqa: F401
 from mi355x_graph.readout import (readout_nodes, sum_nodes, mean_nodes, max_nodes, softmax_nodes, broadcast_nodes,  # noqa: F401
                                   readout_edges, sum_edges, mean_edges, max_edges, softmax_edges, broadcast_edges, topk_nodes, topk_edges)
-from . import nn, data, dataloading, utils, sampling, transform, backend  # noqa: F401
+from . import nn, data, dataloading, utils, sampling, transform, backend, geometry  # noqa: F401
 from mi355x_graph.sampling import to_block, in_subgraph, NID, EID  # noqa: F401
 from mi355x_graph.linkpred import compact_graphs  # noqa: F401
 from mi355x_graph.ops import edge_softmax  # noqa: F401

@@ -48,10 +48,15 @@ SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: seg
 # ---- segment top-k (ops.segment_topk, readout.topk_nodes / topk_edges, nn.SortPooling)
 SEGMENT_TOPK_FUSED = True  # csrc/segtopk.hip, one launch each way; False: two stable sorts and gathers in torch operators
 
-# ---- point clouds (ops.segment_knn, transform.knn_graph / segmented_knn_graph, nn.EdgeConv)
+# ---- point clouds (ops.segment_knn, transform.knn_graph / segmented_knn_graph, nn.EdgeConv; ops.segment_fps, ops.segment_ball_query,
+#      transform.fixed_radius_block, nn.PointNetConv)
 KNN_FUSED = True       # csrc/knn.hip: distances and selection in one launch; False: a stable sort of direct-form distances per segment in torch operators
 EDGECONV_FUSED = True  # EdgeConv without batch norm as theta GEMM over nodes -> copy_u / max -> + x (phi - theta)^T: no E-sized tensor; False:
                        # u_sub_v -> the two Linears over edges -> copy_e / max
+FPS_FUSED = True         # csrc/fps.hip: the whole sampling chain of a cloud in one workgroup of one launch; False: the same loop in torch operators
+BALL_QUERY_FUSED = True  # csrc/ballquery.hip: distances and first-K selection in one launch; False: per-segment distances and a cumsum in torch operators
+POINTNETCONV_FUSED = True  # PointNetConv with one layer and no batch norm as a GEMM over the points -> copy_u / max -> relu(. - centre term): no
+                           # E-sized tensor; False: u_sub_v -> relu -> copy_e / max
 
 # ---- sampled blocks and induced subgraphs (sampling.to_block, sampling.node_subgraph)
 DEVICE_BLOCKS = True    # the relabelling kernels of csrc/relabel.hip; False: look-up table -> unique -> gathers -> bincount + cumsum in torch ops

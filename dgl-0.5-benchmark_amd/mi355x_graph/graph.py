@@ -36,6 +36,8 @@ class GraphIndex(object):
         self.dst_is_src_prefix = False  # blocks: destination nodes are the first source nodes
         self.max_in_degree_hint = None
         self.ephemeral = False  # a structure used for ONE step (a sampled block): its views decide kernel forms without host reads
+        self.plain_transpose = False  # the format derived by a transpose runs WITHOUT a schedule (building one reads row lengths back): set by
+                                      # builders whose graph is differentiated inside a captured step (transform.fixed_radius_block)
 
     # -- basic facts
     def _any(self):
@@ -108,6 +110,8 @@ class GraphIndex(object):
             view = sparse.coo_to_csr(self.num_dst, self.num_src, dst, src)
         view.dst_is_src_prefix = self.dst_is_src_prefix
         self._mark_ephemeral(view)
+        if self.plain_transpose:
+            view._plan = None
         if self.allowed("csc"):
             self._csc = view
         else:
@@ -131,6 +135,8 @@ class GraphIndex(object):
             src, dst = self.coo()
             view = sparse.coo_to_csr(self.num_src, self.num_dst, src, dst)
         self._mark_ephemeral(view)
+        if self.plain_transpose:
+            view._plan = None
         if self.allowed("csr"):
             self._csr = view
         else:
@@ -198,7 +204,7 @@ class GraphIndex(object):
         g = GraphIndex(self.num_src, self.num_dst, coo, mv(self._csr), mv(self._csc), self._formats)
         g._hidden_csc, g._hidden_csr = mv(self._hidden_csc), mv(self._hidden_csr)
         g.dst_is_src_prefix = self.dst_is_src_prefix
-        g.ephemeral = self.ephemeral
+        g.ephemeral, g.plain_transpose = self.ephemeral, self.plain_transpose
         return g
 
     def astype(self, dtype):
@@ -211,7 +217,7 @@ class GraphIndex(object):
         g = GraphIndex(self.num_src, self.num_dst, coo, cv(self._csr), cv(self._csc), self._formats)
         g._hidden_csc, g._hidden_csr = cv(self._hidden_csc), cv(self._hidden_csr)
         g.dst_is_src_prefix = self.dst_is_src_prefix
-        g.ephemeral = self.ephemeral
+        g.ephemeral, g.plain_transpose = self.ephemeral, self.plain_transpose
         return g
 
     def in_degrees(self):

@@ -8,6 +8,7 @@
   GlobalAttentionPooling / Set2Set / WeightAndSum   dgl.nn.pytorch.glob (attention readouts, fused: ops.segment_attention)
   SortPooling   dgl.nn.pytorch.glob (the DGCNN readout: ops.segment_topk)
   KNNGraph / SegmentedKNNGraph   dgl.nn.pytorch.factory (ops.segment_knn);  EdgeConv   dgl.nn.pytorch.conv (point clouds)
+  FarthestPointSampler   dgl.geometry.pytorch (ops.segment_fps);  FixedRadiusNNGraph   the PointNet++ grouping (ops.segment_ball_query);  PointNetConv   its message
 Parameter names, shapes and initialisation follow DGL v0.6.x so state_dicts and the scripts'
 reset_parameters() calls (main_dgl_reddit_gat.py:57-59) line up.
 """
@@ -691,6 +692,40 @@ class SegmentedKNNGraph(nn.Module):
         return "k={k}".format(**self.__dict__)
 
 
+class FarthestPointSampler(nn.Module):
+    """dgl.geometry.FarthestPointSampler (dgl.geometry.pytorch in DGL 0.5): pos [B, n, C] -> int64 [B, npoints], the sampled points'
+    numbers inside each cloud, the start of every cloud drawn at random (transform.farthest_point_sampler: ops.segment_fps).  No
+    parameters."""
+
+    def __init__(self, npoints):
+        super(FarthestPointSampler, self).__init__()
+        self.npoints = npoints
+
+    def forward(self, pos):
+        from .transform import farthest_point_sampler
+        return farthest_point_sampler(pos, self.npoints)
+
+    def extra_repr(self):
+        return "npoints={npoints}".format(**self.__dict__)
+
+
+class FixedRadiusNNGraph(nn.Module):
+    """The PointNet++ grouping: points [N, D] in consecutive sets of segs[0], segs[1], ... points and centres int64 [M] (rows of the
+    points) -> the block whose destination i is centre i and whose predecessors are the first max_neighbors points within radius of
+    it (transform.fixed_radius_block: ops.segment_ball_query, whose padded index is the in-CSR).  No parameters."""
+
+    def __init__(self, radius, max_neighbors):
+        super(FixedRadiusNNGraph, self).__init__()
+        self.radius, self.max_neighbors = radius, max_neighbors
+
+    def forward(self, pos, centers, segs):
+        from .transform import fixed_radius_block
+        return fixed_radius_block(pos, centers, self.radius, self.max_neighbors, segs)
+
+    def extra_repr(self):
+        return "radius={radius}, max_neighbors={max_neighbors}".format(**self.__dict__)
+
+
 class EdgeConv(nn.Module):
     """dgl.nn.EdgeConv (Wang et al., Dynamic Graph CNN for Learning on Point Clouds), by upstream's documented formula:
         out_i = max_{j -> i} [ theta(x_j - x_i) + phi(x_i) ]     per column; 0 for a node without in-edges
@@ -735,6 +770,70 @@ class EdgeConv(nn.Module):
                 g.edata["e"] = self.bn(e) if self.batch_norm else e
                 g.update_all(fn.copy_e("e", "m"), fn.max("m", "x"))
                 rst = g.dstdata["x"]
+            if zero_deg:
+                has = (g.in_degrees() > 0).view((-1,) + (1,) * (rst.dim() - 1))
+                rst = torch.where(has, rst, rst.new_zeros(()))
+            return rst
+
+
+class PointNetConv(nn.Module):
+    """The PointNet++ set-abstraction message (Qi et al., PointNet++: Deep Hierarchical Feature Learning on Point Sets in a Metric Space)
+    over a block such as transform.fixed_radius_block builds:
+        out_i = max_{j -> i} MLP([h_j | pos_j - pos_i])     per column; 0 for a node without in-edges
+    with MLP = Linear(in_feats + pos_dim, sizes[0]) -> ReLU -> Linear(sizes[0], sizes[1]) -> ReLU ... (a ReLU after every layer, a
+    BatchNorm1d over the edges before it with batch_norm=True).  in_feats = 0: positions only (the first level).  Positions come from
+    srcdata["pos"] / dstdata["pos"] of the block unless given.
+    The first Linear is pulled to the nodes as EdgeConv's is: W [h_j | pos_j - pos_i] + b = (W_h h_j + W_p pos_j) - (W_p pos_i - b).
+    With one layer and no batch norm (config.POINTNETCONV_FUSED) the ReLU commutes with the max, so the layer is a GEMM over the N
+    points, the copy_u / max g-SpMM (gradient through its arg) and M-row arithmetic: no tensor of E rows exists in either direction.
+    With more layers or batch norm: the u_sub_v g-SDDMM of the two node projections, the remaining Linears over the edges, copy_e / max.
+    The repeated first point of a padded ball changes nothing under the max."""
+
+    def __init__(self, in_feats, sizes, batch_norm=False, pos_dim=3, allow_zero_in_degree=False):
+        super(PointNetConv, self).__init__()
+        sizes = [int(v) for v in sizes]
+        if in_feats < 0 or pos_dim < 1 or not sizes or min(sizes) < 1:
+            raise DGLError("PointNetConv: needs in_feats >= 0, pos_dim >= 1 and at least one layer size >= 1, got %r, %r, %r" % (in_feats, pos_dim, sizes))
+        self.in_feats, self.pos_dim, self.sizes, self.batch_norm = in_feats, pos_dim, sizes, batch_norm
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.layers = nn.ModuleList([Linear(a, b) for a, b in zip([in_feats + pos_dim] + sizes[:-1], sizes)])
+        if batch_norm:
+            self.bns = nn.ModuleList([BatchNorm1d(b) for b in sizes])
+
+    def set_allow_zero_in_degree(self, set_value):
+        self._allow_zero_in_degree = set_value
+
+    def forward(self, g, feat=None, pos=None):
+        with g.local_scope():
+            zero_deg = _has_zero_in_degree(g)
+            if zero_deg and not self._allow_zero_in_degree:
+                raise DGLError("There are 0-in-degree nodes in the graph, output for those nodes will be invalid. "
+                               "Setting ``allow_zero_in_degree`` to be `True` when constructing this module will suppress the check "
+                               "and let the code run.")
+            pos_src, pos_dst = (g.srcdata["pos"], g.dstdata["pos"]) if pos is None else expand_as_pair(pos, g)
+            if (feat is None) != (self.in_feats == 0):
+                raise DGLError("PointNetConv: in_feats = %d %s source features" % (self.in_feats, "needs" if feat is None else "takes no"))
+            if pos_src.shape[1] != self.pos_dim or (feat is not None and feat.shape[1] != self.in_feats):
+                raise DGLError("PointNetConv: expected positions [*, %d] and features [*, %d]" % (self.pos_dim, self.in_feats))
+            first = self.layers[0]
+            w_pos = first.weight[:, self.in_feats:]
+            u = F.linear(pos_src if feat is None else torch.cat([feat, pos_src], 1), first.weight)   # W_h h_j + W_p pos_j: over the N points
+            v = F.linear(pos_dst, w_pos) - first.bias                                               # W_p pos_i - b: over the M centres
+            if len(self.layers) == 1 and not self.batch_norm and config.POINTNETCONV_FUSED:
+                g.srcdata["u"] = u
+                g.update_all(fn.copy_u("u", "m"), fn.max("m", "m"))
+                rst = F.relu(g.dstdata["m"] - v)
+            else:
+                g.srcdata["u"], g.dstdata["v"] = u, v
+                g.apply_edges(fn.u_sub_v("u", "v", "e"))
+                e = g.edata["e"]
+                for i, layer in enumerate(self.layers):
+                    if i:
+                        e = layer(e)
+                    e = F.relu(self.bns[i](e) if self.batch_norm else e)
+                g.edata["e"] = e
+                g.update_all(fn.copy_e("e", "m"), fn.max("m", "m"))
+                rst = g.dstdata["m"]
             if zero_deg:
                 has = (g.in_degrees() > 0).view((-1,) + (1,) * (rst.dim() - 1))
                 rst = torch.where(has, rst, rst.new_zeros(()))

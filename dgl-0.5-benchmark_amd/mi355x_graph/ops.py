@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -2077,6 +2077,216 @@ def segment_knn(seglen, x, k, total=None, return_dist=False):
         sparse.backend_for(x)  # no CPU backend: DGLError
         index, dist = _segment_knn_composed(offsets, x.detach(), k, return_dist)
     return (index, dist) if return_dist else index
+
+
+# ----------------------------------------------------------------------------- point clouds: farthest point sampling and ball query
+def _segment_fps_composed(offsets, x, m, start, return_dist):
+    """ops.segment_fps through torch operators, by the same definition literally: per segment mind = +inf, then min(m, len) times
+    record the current row, mark it selected, lower mind of the unselected rows by the direct-form distance to it (a NaN distance
+    lowers nothing) and take the first unselected row of greatest mind.  One read-back of the offsets, a loop over segments and
+    samples; the current row stays a device tensor.  The form for CPU tensors, shapes outside mgx_segment_fps_supported, under
+    MGX_TORCH_OPS=1 and with config.FPS_FUSED off."""
+    S = int(offsets.shape[0]) - 1
+    index = torch.full((S, m), -1, dtype=torch.int64, device=x.device)
+    dist = torch.zeros((S, m), dtype=torch.float32, device=x.device)
+    with torch.no_grad():
+        ends = offsets.tolist()
+        for s, (beg, end) in enumerate(zip(ends[:-1], ends[1:])):
+            n = end - beg
+            if n <= 0:
+                continue
+            seg, mm = x[beg:end], min(m, n)
+            mind = torch.full((n,), float("inf"), dtype=torch.float32, device=x.device)
+            live = torch.ones(n, dtype=torch.bool, device=x.device)
+            cur = torch.zeros(1, dtype=torch.int64, device=x.device)
+            if start is not None:
+                st = start[s:s + 1]
+                cur = torch.where((st >= 0) & (st < n), st, cur)
+            curd = mind[:1]
+            for t in range(mm):
+                index[s, t:t + 1] = cur + beg
+                dist[s, t:t + 1] = curd
+                live.index_fill_(0, cur, False)
+                if t == mm - 1:
+                    break
+                diff = seg.index_select(0, cur) - seg
+                d = (diff * diff).sum(-1)
+                mind = torch.where(live & (d < mind), d, mind)
+                key = torch.where(live, mind, mind.new_full((), -1.0))
+                cur = torch.argmax(key).view(1)                                                 # the first maximal value: the lowest row
+                curd = key.index_select(0, cur)
+    return index, (dist if return_dist else None)
+
+
+_BALL_COMPOSED_ELEMS = 1 << 24  # the composition's [queries, len, D] difference tensor is built this many elements at a time
+
+
+def _segment_ball_query_composed(offsets, x, centers, radius2, K, pad_first):
+    """ops.segment_ball_query through torch operators, by the same definition: per segment the direct-form distances of its centres to
+    its rows, the mask d <= radius2 (a NaN distance is outside), a running count along the rows for the rank, the first K kept.
+    One read-back of the offsets and one of which centres a segment holds, a loop over segments.  The form for CPU tensors, for
+    K > 64 or D > 256, under MGX_TORCH_OPS=1 and with config.BALL_QUERY_FUSED off."""
+    M, D = int(centers.shape[0]), int(x.shape[1])
+    index = torch.full((M, K), -1, dtype=torch.int64, device=x.device)
+    count = torch.zeros((M,), dtype=torch.int32, device=x.device)
+    with torch.no_grad():
+        ends = offsets.tolist()
+        for beg, end in zip(ends[:-1], ends[1:]):
+            n = end - beg
+            if n <= 0 or M == 0:
+                continue
+            qs = ((centers >= beg) & (centers < end)).nonzero().flatten()
+            seg, step = x[beg:end], max(1, _BALL_COMPOSED_ELEMS // (n * D))
+            for q0 in range(0, int(qs.shape[0]), step):
+                q = qs[q0:q0 + step]
+                diff = x.index_select(0, centers.index_select(0, q)).unsqueeze(1) - seg.unsqueeze(0)      # [queries, n, D]
+                inside = (diff * diff).sum(-1) <= radius2                                      # radius2 is a float32 value
+                rank = torch.cumsum(inside, 1) - 1
+                qi, col = (inside & (rank < K)).nonzero(as_tuple=True)
+                index[q[qi], rank[qi, col]] = col + beg
+                count[q] = inside.sum(1).clamp(max=K).to(torch.int32)
+        if pad_first:
+            empty = torch.arange(K, device=x.device).unsqueeze(0) >= count.unsqueeze(1)
+            index = torch.where(empty, index[:, :1], index)                                    # count == 0: index[:, 0] is -1
+    return index, count
+
+
+def _segment_fps_args(seglen, x, npoints, start, total):
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise DGLError("segment_fps: expected x [N, D], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    if x.dtype != torch.float32:
+        raise DGLError("segment_fps expects float32 input, got %s" % (x.dtype,))
+    if isinstance(npoints, bool) or not isinstance(npoints, int) or npoints < 1:
+        raise DGLError("segment_fps: npoints must be an integer >= 1, got %r" % (npoints,))
+    if torch.is_tensor(seglen) and seglen.device != x.device and seglen.device.type != "cpu":  # host lengths go with any x
+        raise DGLError("segment_fps: operands on different devices: %s vs %s" % (x.device, seglen.device))
+    if x.shape[1] < 1:
+        raise DGLError("segment_fps: x has no columns")
+    offsets, n = _segment_offsets(seglen, x, total, "segment_fps")
+    S = int(seglen.shape[0])
+    if start is not None:
+        if isinstance(start, int) and not isinstance(start, bool):
+            start = torch.full((S,), start, dtype=torch.int64, device=x.device)                # filled in on the device: no copy
+        elif (not torch.is_tensor(start) or start.dtype != torch.int64 or start.dim() != 1 or start.shape[0] != S
+              or start.device != x.device):
+            raise DGLError("segment_fps: start must be None, an int or an int64 tensor [%d] on %s, got %s"
+                           % (S, x.device, (start.dtype, tuple(start.shape), start.device) if torch.is_tensor(start) else repr(start)))
+        else:
+            start = start.contiguous()
+    return offsets, n, start
+
+
+def _fps_max_len(seglen, max_len):
+    if max_len is not None:
+        if isinstance(max_len, bool) or not isinstance(max_len, int) or max_len < 0:
+            raise DGLError("segment_fps: max_len must be an integer >= 0, got %r" % (max_len,))
+        return max_len
+    return int(seglen.max()) if seglen.shape[0] else 0   # device lengths: the one read-back
+
+
+def _segment_fps_kernel_ok(seglen, x, npoints, max_len):
+    if (not config.FPS_FUSED or x.device.type not in sparse._BACKENDS or not _readout_kernels(x)
+            or not hasattr(sparse.backend_for(x), "segment_fps")):
+        return False
+    N, D, S = int(x.shape[0]), int(x.shape[1]), int(seglen.shape[0])
+    ld = int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= D else D
+    return (S > 0 and N < 2 ** 31 and S * npoints < 2 ** 31 and N * ld < 2 ** 30
+            and sparse.backend_for(x).segment_fps_supported(D, max_len))
+
+
+def segment_fps_fused(seglen, x, npoints, start=None, total=None, max_len=None, return_dist=False):
+    """True when segment_fps(...) with these operands runs csrc/fps.hip (else the same loop in torch operators)."""
+    try:
+        _segment_fps_args(seglen, x, npoints, start, total)
+        return _segment_fps_kernel_ok(seglen, x, npoints, _fps_max_len(seglen, max_len))
+    except DGLError:
+        return False
+
+
+def segment_fps(seglen, x, npoints, start=None, total=None, max_len=None, return_dist=False):
+    """Farthest point sampling inside every consecutive row segment (dgl.geometry.farthest_point_sampler): index int64 [S, npoints],
+    global row numbers of x, or (index, dist [S, npoints]) with return_dist.
+
+    x [N, D] (fp32; may be a row-strided column block), seglen [S] segment lengths.  Per segment: mind = +inf; the first sample is
+    row `start` of the segment (None: row 0 of every segment; an int; an int64 tensor [S]; a value outside the segment is taken as 0);
+    every further sample is the unselected row whose distance to the nearest sample so far, mind, is greatest -- the lowest row on
+    ties -- where mind is lowered by d = sum_c (x[cur,c] - x[j,c])^2 in fp32 (the direct form of segment_knn) whenever d < mind, so a
+    NaN distance lowers nothing.  dist is mind of the sample when it was taken (+inf at rank 0).  The samples of a segment are
+    distinct; duplicate points are taken in row order once everything else is at distance 0; a row with a NaN coordinate is taken
+    right after the start.  A segment shorter than npoints is padded with index -1 and dist 0.  Neither output is differentiable.
+    `total`: the row count when the caller knows it.  `max_len`: an upper bound of the segment lengths when the caller knows it; it
+    chooses the kernel's shape on the host, so a device `seglen` without it costs ONE read-back (its maximum), and a segment longer
+    than max_len is sampled from its first max_len rows only.  Device operands with D <= 64 and max_len <= min(16384,
+    38912 // (D | 1)) -- 12 970 points for D = 3 -- run csrc/fps.hip, the whole chain in one launch (segment_fps_fused); everything
+    else -- CPU tensors under a registered CPU backend, longer segments, config.FPS_FUSED = False -- is the same loop in torch operators."""
+    offsets, n, start = _segment_fps_args(seglen, x, npoints, start, total)
+    max_len = _fps_max_len(seglen, max_len)
+    if _segment_fps_kernel_ok(seglen, x, npoints, max_len):
+        with torch.no_grad():
+            index, dist = sparse.backend_for(x).segment_fps(offsets, x.detach(), npoints, max_len, start, return_dist)
+    else:
+        sparse.backend_for(x)  # no CPU backend: DGLError
+        index, dist = _segment_fps_composed(offsets, x.detach(), npoints, start, return_dist)
+    return (index, dist) if return_dist else index
+
+
+def _segment_ball_query_args(seglen, x, centers, radius, max_neighbors, pad, total):
+    if not torch.is_tensor(x) or x.dim() != 2:
+        raise DGLError("segment_ball_query: expected x [N, D], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
+    if x.dtype != torch.float32:
+        raise DGLError("segment_ball_query expects float32 input, got %s" % (x.dtype,))
+    if isinstance(max_neighbors, bool) or not isinstance(max_neighbors, int) or max_neighbors < 1:
+        raise DGLError("segment_ball_query: max_neighbors must be an integer >= 1, got %r" % (max_neighbors,))
+    if not torch.is_tensor(centers) or centers.dim() != 1 or centers.dtype != torch.int64 or centers.device != x.device:
+        raise DGLError("segment_ball_query: centers must be an int64 tensor [M] of rows of x on %s, got %s"
+                       % (x.device, (centers.dtype, tuple(centers.shape), centers.device) if torch.is_tensor(centers) else type(centers).__name__))
+    if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not radius >= 0:
+        raise DGLError("segment_ball_query: radius must be a number >= 0, got %r" % (radius,))
+    if pad not in ("first", None):
+        raise DGLError("segment_ball_query: pad must be 'first' or None, got %r" % (pad,))
+    if torch.is_tensor(seglen) and seglen.device != x.device and seglen.device.type != "cpu":
+        raise DGLError("segment_ball_query: operands on different devices: %s vs %s" % (x.device, seglen.device))
+    if x.shape[1] < 1:
+        raise DGLError("segment_ball_query: x has no columns")
+    offsets, n = _segment_offsets(seglen, x, total, "segment_ball_query")
+    r = torch.tensor(float(radius), dtype=torch.float32)
+    return offsets, n, float(r * r)                                                            # float32(radius) * float32(radius), once, on the host
+
+
+def segment_ball_query_fused(seglen, x, centers, radius, max_neighbors, pad="first", total=None):
+    """True when segment_ball_query(...) with these operands runs csrc/ballquery.hip (else the composition in torch operators)."""
+    if (not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not torch.is_tensor(seglen) or not torch.is_tensor(centers)
+            or centers.dtype != torch.int64 or centers.dim() != 1 or centers.device != x.device
+            or (seglen.device != x.device and seglen.device.type != "cpu") or isinstance(max_neighbors, bool)
+            or not isinstance(max_neighbors, int) or max_neighbors < 1 or not config.BALL_QUERY_FUSED
+            or x.device.type not in sparse._BACKENDS or not _readout_kernels(x) or not hasattr(sparse.backend_for(x), "segment_ball_query")):
+        return False
+    N, D = int(x.shape[0]), int(x.shape[1])
+    ld = int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= D else D
+    return (D >= 1 and N < 2 ** 31 and seglen.shape[0] < 2 ** 31 and N * ld < 2 ** 30 and centers.shape[0] < 2 ** 31
+            and sparse.backend_for(x).segment_ball_query_supported(max_neighbors, D))
+
+
+def segment_ball_query(seglen, x, centers, radius, max_neighbors, pad="first", total=None):
+    """The first max_neighbors rows within `radius` of every centre, inside the centre's own consecutive row segment (the PointNet++
+    ball query): (index int64 [M, K], count int32 [M]).
+
+    x [N, D] (fp32; may be a row-strided column block), seglen [S] segment lengths, centers int64 [M] global rows of x in any order
+    (duplicates allowed; -1: no centre).  index[q] holds, in ascending row order, the first K rows j of the segment of centers[q] with
+    d = sum_c (x[c,c'] - x[j,c'])^2 <= radius2 in fp32 (the direct form of segment_knn), radius2 = float32(radius) * float32(radius)
+    computed once on the host; a NaN distance is outside the ball.  These are the FIRST rows in the ball, not the nearest.  count[q] is
+    how many were found, at most K.  Ranks past count[q] hold index[q, 0] with pad = "first" (the PointNet++ convention: every query
+    has exactly K entries) and -1 with pad = None; a query that found nothing -- a NaN centre, a centre -1 or outside every segment --
+    holds -1 everywhere.  Neither output is differentiable.
+    `total`: the row count when the caller knows it (no read-back of device lengths).  Device operands with K <= 64 and D <= 256 run
+    csrc/ballquery.hip in one launch that writes no [M, n] matrix (segment_ball_query_fused); everything else -- CPU tensors under a
+    registered CPU backend, larger K or D, config.BALL_QUERY_FUSED = False -- is a masked running count per segment in torch operators."""
+    offsets, n, radius2 = _segment_ball_query_args(seglen, x, centers, radius, max_neighbors, pad, total)
+    if segment_ball_query_fused(seglen, x, centers, radius, max_neighbors, pad, n):
+        with torch.no_grad():
+            return sparse.backend_for(x).segment_ball_query(offsets, x.detach(), centers.contiguous(), radius2, max_neighbors, pad == "first")
+    sparse.backend_for(x)  # no CPU backend: DGLError
+    return _segment_ball_query_composed(offsets, x.detach(), centers, radius2, max_neighbors, pad == "first")
 
 
 def segment_broadcast(seglen, value, total):

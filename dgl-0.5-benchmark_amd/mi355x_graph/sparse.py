@@ -1249,6 +1249,45 @@ class HipBackend(object):
             _lib.check(_lib.lib().mgx_segment_knn(S, _ptr(offsets), N, D, ld, _ptr(x2d), int(k), _ptr(index), _ptr(dist), _stream(dev)))
         return index, dist
 
+    # ---- farthest point sampling (csrc/fps.hip) and fixed-radius ball query (csrc/ballquery.hip)
+    @classmethod
+    def segment_fps_supported(cls, D, max_len):
+        """Shapes mgx_segment_fps takes: 1 <= D <= 64, max_len <= min(16384, 38912 // (D | 1))."""
+        return bool(_lib.lib().mgx_segment_fps_supported(int(D), int(max_len)))
+
+    def segment_fps(self, offsets, x2d, m, max_len, start, return_dist):
+        """x2d [N, D] (a column block of a wider matrix is taken as it is), start int64 [S] | None -> (index int64 [S, m], dist [S, m] | None)."""
+        dev = self._check_dev(offsets, x2d, start)
+        S, N, D = offsets.shape[0] - 1, int(x2d.shape[0]), int(x2d.shape[1])
+        if not (x2d.stride(1) == 1 and x2d.stride(0) >= D) and N > 0:  # a stride the kernel cannot take becomes a dense copy
+            x2d = x2d.contiguous()
+        ld = int(x2d.stride(0)) if N > 0 else D
+        index = torch.empty((S, m), dtype=torch.int64, device=dev)
+        dist = torch.empty((S, m), dtype=torch.float32, device=dev) if return_dist else None
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_fps", m=int(m), D=D, segments=int(S), rows=N, max_len=int(max_len)):
+            _lib.check(_lib.lib().mgx_segment_fps(S, _ptr(offsets), N, D, ld, _ptr(x2d), int(m), int(max_len), _ptr(start), _ptr(index),
+                                                  _ptr(dist), _stream(dev)))
+        return index, dist
+
+    @classmethod
+    def segment_ball_query_supported(cls, K, D):
+        """Shapes mgx_segment_ball_query takes: 1 <= K <= 64, 1 <= D <= 256."""
+        return bool(_lib.lib().mgx_segment_ball_query_supported(int(K), int(D)))
+
+    def segment_ball_query(self, offsets, x2d, centers, radius2, K, pad_first):
+        """x2d [N, D], centers int64 [M] global rows (-1: none) -> (index int64 [M, K], count int32 [M])."""
+        dev = self._check_dev(offsets, x2d, centers)
+        S, N, D, M = offsets.shape[0] - 1, int(x2d.shape[0]), int(x2d.shape[1]), int(centers.shape[0])
+        if not (x2d.stride(1) == 1 and x2d.stride(0) >= D) and N > 0:
+            x2d = x2d.contiguous()
+        ld = int(x2d.stride(0)) if N > 0 else D
+        index = torch.empty((M, K), dtype=torch.int64, device=dev)
+        count = torch.empty((M,), dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_ball_query", K=int(K), D=D, segments=int(S), rows=N, queries=M):
+            _lib.check(_lib.lib().mgx_segment_ball_query(S, _ptr(offsets), N, D, ld, _ptr(x2d), M, _ptr(centers), ctypes.c_float(radius2),
+                                                         int(K), 1 if pad_first else 0, _ptr(index), _ptr(count), _stream(dev)))
+        return index, count
+
     @staticmethod
     def _row_strided(t):
         return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 4 == 0 and t.shape[1] % 4 == 0

@@ -317,6 +317,85 @@ def segmented_knn_graph(x, k, segs):
     return _knn_graph_of(x, k, list(segs), "segmented_knn_graph")
 
 
+def farthest_point_sampler(pos, npoints, start_idx=None):
+    """dgl.geometry.farthest_point_sampler: pos [B, n, C] is B clouds of n points -> int64 [B, npoints], the sampled points' numbers
+    INSIDE each cloud (DGL's contract).  start_idx None: one start per cloud drawn with torch.randint on pos's device; an int: the same
+    start in every cloud (DGL's meaning).  ops.segment_fps over B equal segments whose lengths are filled in on the device: no
+    host-to-device copy and no read-back."""
+    from . import ops
+    if not torch.is_tensor(pos) or pos.dim() != 3 or not pos.dtype.is_floating_point:
+        raise DGLError("farthest_point_sampler: expected floating-point points [B, n, C], got %s"
+                       % ((pos.dtype, tuple(pos.shape)) if torch.is_tensor(pos) else type(pos).__name__,))
+    B, n, C = (int(v) for v in pos.shape)
+    if isinstance(npoints, bool) or not isinstance(npoints, int) or npoints < 1 or npoints > n:
+        raise DGLError("farthest_point_sampler: npoints must be an integer in [1, %d] (the points of a cloud), got %r" % (n, npoints))
+    if start_idx is None:
+        start = torch.randint(0, n, (B,), dtype=torch.int64, device=pos.device)
+    elif isinstance(start_idx, int) and not isinstance(start_idx, bool) and 0 <= start_idx < n:
+        start = start_idx
+    else:
+        raise DGLError("farthest_point_sampler: start_idx must be None or an integer in [0, %d), got %r" % (n, start_idx))
+    seglen = torch.full((B,), n, dtype=torch.int64, device=pos.device)
+    index = ops.segment_fps(seglen, pos.detach().float().reshape(B * n, C), npoints, start=start, total=B * n, max_len=n)
+    return index - torch.arange(B, dtype=torch.int64, device=pos.device).unsqueeze(1) * n
+
+
+def fixed_radius_block(pos, centers, radius, max_neighbors, segs):
+    """The PointNet++ grouping as a block: pos [N, D] holds consecutive sets of segs[0], segs[1], ... points (a Python list of
+    lengths), centers int64 [M] are rows of pos (a segment's farthest point samples, say).  The block has N source nodes and M
+    destination nodes; destination i is centre centers[i], and its predecessors are the first max_neighbors points within `radius` of
+    it inside its own set (ops.segment_ball_query with pad = "first").
+
+    Every destination has exactly K = max_neighbors in-edges: a ball with fewer points repeats its first point.  The repeats are
+    harmless under a `max` reducer and DOUBLE-COUNT under `sum` / `mean`.  A query that found nothing (a NaN centre) gets its own
+    centre in every slot, so no -1 reaches a gather.  The padded index IS the in-CSR (indptr = arange(M + 1) * K, no edge-id
+    permutation), as in knn_graph: no sort or COO -> CSR pass runs, and nothing is read back.  A -1 centre cannot be told from the
+    host, so `centers` must come from a sampling that cannot pad: every set needs at least M / len(segs) points when M is a multiple
+    of len(segs) (npoints samples per set); otherwise a DGLError.  The block carries srcdata["pos"] = pos and dstdata["pos"] =
+    pos[centers]."""
+    from . import ops
+    from .sparse import CsrView
+    K = max_neighbors
+    if not torch.is_tensor(pos) or pos.dim() != 2 or not pos.dtype.is_floating_point:
+        raise DGLError("fixed_radius_block: expected floating-point points [N, D], got %s"
+                       % ((pos.dtype, tuple(pos.shape)) if torch.is_tensor(pos) else type(pos).__name__,))
+    if not torch.is_tensor(centers) or centers.dim() != 1 or centers.dtype != torch.int64 or centers.device != pos.device:
+        raise DGLError("fixed_radius_block: centers must be an int64 tensor [M] of rows of pos on %s" % (pos.device,))
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise DGLError("fixed_radius_block: max_neighbors must be an integer >= 1, got %r" % (K,))
+    lens = [int(n) for n in segs]
+    N, M = int(pos.shape[0]), int(centers.shape[0])
+    if any(n < 0 for n in lens) or sum(lens) != N:
+        raise DGLError("fixed_radius_block: segment lengths %s do not sum to the %d points" % (lens if len(lens) <= 8 else lens[:8] + ["..."], N))
+    if lens and M % len(lens) == 0 and any(n < M // len(lens) for n in lens):
+        raise DGLError("fixed_radius_block: a segment of %d points cannot hold %d sampled centres (a -1 centre)"
+                       % (min(lens), M // len(lens)))
+    if N == 0 and M > 0:
+        raise DGLError("fixed_radius_block: %d centres of no points" % M)
+    if len(lens) >= 1 and len(set(lens)) == 1:  # equal sets: the lengths are filled in on the device, no host-to-device copy
+        seglen = torch.full((len(lens),), lens[0], dtype=torch.int64, device=pos.device)
+    else:
+        seglen = torch.tensor(lens, dtype=torch.int64)
+    x = pos.detach().float()
+    index, count = ops.segment_ball_query(seglen, x, centers, radius, K, pad="first", total=N)
+    index = torch.where(count.unsqueeze(1) == 0, centers.unsqueeze(1), index)
+    idtype = torch.int32 if max(M * K, N) < 2 ** 31 else torch.int64
+    indptr = torch.arange(M + 1, dtype=idtype, device=pos.device) * K
+    csc = CsrView(M, N, indptr, index.reshape(-1).to(idtype), None)
+    if K <= 256:
+        csc._plan = None  # every row has K entries: nothing to split or balance, and no host read of the lengths
+    idx = GraphIndex(N, M, csc=csc)
+    idx.max_in_degree_hint = K
+    idx.ephemeral = True  # rebuilt before every level of every step
+    idx.plain_transpose = True  # the out-CSR a backward over the edges asks for: no schedule, so no read-back inside a captured step
+    idx._mark_ephemeral(csc)
+    idx._zero_in_deg = False
+    block = DGLGraph(idx, is_block=True)
+    block.srcdata["pos"] = pos
+    block.dstdata["pos"] = pos.index_select(0, centers.clamp(min=0))
+    return block
+
+
 def metis_partition_assignment(g, k, balance_ntypes=None, balance_edges=False):
     """k-way edge-cut node partition -> [N] part ids.  The role of dgl.transform.metis_partition_assignment
     (end_to_end/sampling/link-prediction/dgl_cluster_sampler.py:24); METIS itself is not available offline, the

@@ -763,6 +763,52 @@ int32_t mgx_segment_knn_supported(int64_t k, int64_t D);
 int32_t mgx_segment_knn(int64_t num_segments, const int64_t* offsets, int64_t N, int64_t D, int64_t ld, const float* x, int64_t k,
                         int64_t* index, float* dist /* may be NULL */, void* stream);
 
+/* ------------------------------------------------------------------ point clouds: farthest point sampling (csrc/fps.hip)
+ * dgl.geometry.farthest_point_sampler over the segments described above (x [N, ld] fp32, the first D floats of a row are the point).
+ * Per segment of length len starting at row beg:
+ *   mind[j] = +inf for every row j;  cur = start ? start[s] : 0, a value outside [0, len) is taken as 0
+ *   for t = 0 .. min(m, len) - 1:
+ *     index[s, t] = beg + cur;  dist[s, t] = mind[cur]  (rank 0 therefore has dist = +inf);  cur is selected and never chosen again
+ *     for every unselected j:  d = sum_c (x[cur,c] - x[j,c])^2  (fp32, c ascending, one fma per term: the direct form of the k-NN);
+ *                              if (d < mind[j]) mind[j] = d  -- a NaN d leaves mind[j] unchanged
+ *     cur = the unselected row with the greatest mind, the lowest row on ties
+ *   ranks t >= len: index = -1, dist = 0.
+ *   index int64 [S, m]: global row numbers in x;  dist fp32 [S, m] or NULL.  Every output element is written: no memset is needed.
+ * Consequences: the min(m, len) selected rows are distinct; duplicate points are taken in row order once everything else is at
+ * distance 0; a row with a NaN coordinate keeps mind = +inf, so it is selected right after the start (the lowest such row first), and
+ * once it is cur it changes no mind.
+ * max_len: an upper bound of the segment lengths, a HOST argument (like `total` elsewhere) that chooses the kernel's shape.  A segment
+ * that is longer on the device is a caller error the library cannot see: the kernel clamps it to its first max_len rows and reads or
+ * writes nothing out of bounds.
+ * Supported (mgx_segment_fps_supported(D, max_len); everything else is MGX_ERR_UNSUPPORTED before a launch and the caller composes
+ * the loop): 1 <= D <= 64 and max_len points of (D | 1) floats within 152 KiB of LDS and 16 384 points of registers:
+ *   max_len <= min(16384, 38912 / (D | 1)):  D = 1: 16 384;  D = 2, 3: 12 970;  D = 4: 7 782;  D = 64: 598
+ * and N, num_segments, num_segments * m < 2^31, N * ld * 4 bytes < 4 GiB.  One workgroup per segment, one launch, the whole chain
+ * on chip (coordinates in LDS, mind in registers, one barrier per selected point); the workgroup is 256 threads x 1 point
+ * (max_len * (D | 1) <= 4096 floats), 512 x 2 (<= 8192 floats), 512 x 8, 1024 x 8 or 1024 x 16 (docs/LOG_fps.md has the
+ * measurements behind these).  Nothing is read back to the host and the launch depends on num_segments, D and max_len only: capture-safe.  Deterministic: no atomics.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_segment_fps_supported(int64_t D, int64_t max_len);
+int32_t mgx_segment_fps(int64_t num_segments, const int64_t* offsets, int64_t N, int64_t D, int64_t ld, const float* x, int64_t m,
+                        int64_t max_len, const int64_t* start /* [S] or NULL */, int64_t* index /* [S, m] */,
+                        float* dist /* [S, m] or NULL */, void* stream);
+
+/* ------------------------------------------------------------------ point clouds: fixed-radius ball query (csrc/ballquery.hip)
+ * The PointNet++ grouping step: for query q with centre row c = centers[q] (a global row of x, -1 = none), inside the segment that
+ * holds c, index[q, :] holds the FIRST K rows j in ascending row order (not the nearest) with
+ *   d(c, j) = sum_c' (x[c,c'] - x[j,c'])^2 <= radius2     (the fp32 direct form above; a NaN d is outside the ball)
+ * and count[q] how many were found, at most K.  Ranks >= count[q] hold index[q, 0] when pad_first is set (the PointNet++ convention:
+ * every query then has exactly K entries), otherwise -1.  count[q] == 0 -- a NaN centre, c = -1, c in no segment -- leaves every
+ * rank -1.  index int64 [M, K], count int32 [M]; every element is written.
+ * Supported (mgx_segment_ball_query_supported(K, D); everything else is MGX_ERR_UNSUPPORTED before a launch): 1 <= K <= 64,
+ * 1 <= D <= 256, N, num_segments and M < 2^31, N * ld * 4 bytes < 4 GiB.  The streaming of the k-NN (one 256-thread workgroup per 16
+ * queries, csrc/knn_stream.h); selection is a ballot and a prefix popcount, and a workgroup stops once its 16 queries are full.
+ * Nothing is read back to the host and the launch depends on M only: capture-safe.  Deterministic: no atomics.  Purely additive:
+ * mgx_abi_version() stays 35. */
+int32_t mgx_segment_ball_query_supported(int64_t K, int64_t D);
+int32_t mgx_segment_ball_query(int64_t num_segments, const int64_t* offsets, int64_t N, int64_t D, int64_t ld, const float* x, int64_t M,
+                               const int64_t* centers /* [M] */, float radius2, int64_t K, int32_t pad_first,
+                               int64_t* index /* [M, K] */, int32_t* count /* [M] */, void* stream);
+
 /* ------------------------------------------------------------------ formats (integer, bit-exact)
  * Replace the lazy COO->CSR/CSC construction behind g.formats(...)/first kernel call
  * (main_dgl_product_sage.py:158, kernel/dgl-new.py:63) and g.in_degrees()
