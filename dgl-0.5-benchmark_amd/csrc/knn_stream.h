@@ -1,4 +1,5 @@
-// knn_stream.h -- the candidate streaming knn.hip and ballquery.hip share: which segment holds a row, one 64-candidate x 32-column tile
+// knn_stream.h -- the candidate streaming knn.hip and ballquery.hip share: which segment holds a row (and its number, from which the
+// query-set k-NN takes the rows of the OTHER matrix's segment), one 64-candidate x 32-column tile
 // staged into LDS, and the direct-form distance terms of that tile for a wave's four queries.  One 256-thread workgroup takes 16 queries,
 // four per wave; a tile is stored column-major with a row of 65 floats: the transposing stores are at most 2-way conflicted, lane j then
 // reads candidate j at consecutive addresses and that ONE LDS read feeds four queries.  The query's own coordinates come from
@@ -14,10 +15,11 @@ constexpr int kKnnCols = 32;     // columns staged per pass
 constexpr int kKnnTileLd = kWave + 1;
 
 // The segment of `row`: the last s with offsets[s] <= row, clamped to the N rows there are.  A row no segment holds: beg = end = 0.
-__device__ __forceinline__ void knn_segment_of(int64_t S, const int64_t* __restrict__ offsets, int64_t N, int64_t row, int64_t& beg,
-                                               int64_t& end) {
+// Returns the segment's number s, -1 for a row no segment holds.
+__device__ __forceinline__ int64_t knn_segment_of(int64_t S, const int64_t* __restrict__ offsets, int64_t N, int64_t row, int64_t& beg,
+                                                  int64_t& end) {
   beg = end = 0;
-  if (row < 0 || row >= N) return;
+  if (row < 0 || row >= N) return -1;
   int64_t lo = 0, hi = S + 1;
   while (lo < hi) {
     const int64_t mid = (lo + hi) >> 1;
@@ -29,7 +31,22 @@ __device__ __forceinline__ void knn_segment_of(int64_t S, const int64_t* __restr
   }
   end = end < N ? end : N;
   beg = beg < 0 ? 0 : beg;
-  if (!(beg <= row && row < end)) beg = end = 0;
+  if (!(beg <= row && row < end)) {
+    beg = end = 0;
+    return -1;
+  }
+  return lo - 1;
+}
+
+// Rows [beg, end) of segment s of a matrix of N rows, clamped to the rows there are; s < 0 or nothing left: beg = end = 0.
+__device__ __forceinline__ void knn_segment_rows(const int64_t* __restrict__ offsets, int64_t N, int64_t s, int64_t& beg, int64_t& end) {
+  beg = end = 0;
+  if (s < 0) return;
+  beg = offsets[s];
+  end = offsets[s + 1];
+  end = end < N ? end : N;
+  beg = beg < 0 ? 0 : beg;
+  if (beg >= end) beg = end = 0;
 }
 
 // tile[c][r] = x[c0 + r, d0 + c] for r < rows (0 beyond), c < dc <= kKnnCols.  The caller puts a barrier on either side.

@@ -107,6 +107,8 @@ SIGNATURES = {
     "mgx_segment_topk_bwd": (_i32, [_i64, _i64, _i32, _vp, _fp, _fp, _vp]),
     "mgx_segment_knn_supported": (_i32, [_i64, _i64]),
     "mgx_segment_knn": (_i32, [_i64, _vp, _i64, _i64, _i64, _fp, _i64, _vp, _fp, _vp]),
+    "mgx_segment_knn_query_supported": (_i32, [_i64, _i64]),
+    "mgx_segment_knn_query": (_i32, [_i64, _vp, _i64, _i64, _fp, _vp, _i64, _i64, _fp, _i64, _i64, ctypes.c_float, _vp, _fp, _fp, _vp]),
     "mgx_segment_fps_supported": (_i32, [_i64, _i64]),
     "mgx_segment_fps": (_i32, [_i64, _vp, _i64, _i64, _i64, _fp, _i64, _i64, _vp, _vp, _fp, _vp]),
     "mgx_segment_ball_query_supported": (_i32, [_i64, _i64]),

@@ -51,6 +51,8 @@ SEGMENT_TOPK_FUSED = True  # csrc/segtopk.hip, one launch each way; False: two s
 # ---- point clouds (ops.segment_knn, transform.knn_graph / segmented_knn_graph, nn.EdgeConv; ops.segment_fps, ops.segment_ball_query,
 #      transform.fixed_radius_block, nn.PointNetConv)
 KNN_FUSED = True       # csrc/knn.hip: distances and selection in one launch; False: a stable sort of direct-form distances per segment in torch operators
+KNN_QUERY_FUSED = True  # ops.segment_knn_query (queries into a reference set; transform.knn_block, nn.FeaturePropagation) through the same
+                        # kernel, weights included; False: the same composition per segment
 EDGECONV_FUSED = True  # EdgeConv without batch norm as theta GEMM over nodes -> copy_u / max -> + x (phi - theta)^T: no E-sized tensor; False:
                        # u_sub_v -> the two Linears over edges -> copy_e / max
 FPS_FUSED = True         # csrc/fps.hip: the whole sampling chain of a cloud in one workgroup of one launch; False: the same loop in torch operators

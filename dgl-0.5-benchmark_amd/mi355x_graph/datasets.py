@@ -303,3 +303,18 @@ def shapes_like(num_clouds=2048, points=1024, seed=11, noise=0.02):
     xyz *= rng.uniform(0.8, 1.25, (num_clouds, 1, 3))
     xyz += rng.normal(0, noise, xyz.shape)
     return torch.from_numpy(xyz.astype(np.float32)), torch.from_numpy(label.astype(np.int64))
+
+
+def shape_scenes_like(num_clouds=512, points=1024, seed=13, noise=0.02):
+    """Point-cloud segmentation stand-in (the role of ShapeNet-part in the PointNet++ example): every cloud is the union of three
+    POINT_SHAPES clouds of shapes_like, halved in size, each moved by a random offset in [-0.6, 0.6]^3, their points shuffled; a
+    point's label is the shape it came from.  Returns (xyz float32 [num_clouds, points, 3], label int64 [num_clouds, points]); seeded,
+    generated on the host."""
+    per = -(-points // 3)
+    parts, kind = shapes_like(3 * num_clouds, per, seed=seed, noise=noise)
+    rng = np.random.default_rng([seed, 1])
+    offset = torch.from_numpy(rng.uniform(-0.6, 0.6, (3 * num_clouds, 1, 3)).astype(np.float32))
+    xyz = (0.5 * parts + offset).reshape(num_clouds, 3 * per, 3)
+    label = kind.view(num_clouds, 3, 1).expand(num_clouds, 3, per).reshape(num_clouds, 3 * per)
+    order = torch.from_numpy(np.argsort(rng.random((num_clouds, 3 * per)), axis=1)[:, :points])
+    return xyz.gather(1, order.unsqueeze(-1).expand(-1, -1, 3)).contiguous(), label.gather(1, order).contiguous()

@@ -9,6 +9,7 @@
   SortPooling   dgl.nn.pytorch.glob (the DGCNN readout: ops.segment_topk)
   KNNGraph / SegmentedKNNGraph   dgl.nn.pytorch.factory (ops.segment_knn);  EdgeConv   dgl.nn.pytorch.conv (point clouds)
   FarthestPointSampler   dgl.geometry.pytorch (ops.segment_fps);  FixedRadiusNNGraph   the PointNet++ grouping (ops.segment_ball_query);  PointNetConv   its message
+  FeaturePropagation   the PointNet++ decoder level (ops.segment_knn_query + u_mul_e / sum: transform.knn_interpolate)
 Parameter names, shapes and initialisation follow DGL v0.6.x so state_dicts and the scripts'
 reset_parameters() calls (main_dgl_reddit_gat.py:57-59) line up.
 """
@@ -838,6 +839,47 @@ class PointNetConv(nn.Module):
                 has = (g.in_degrees() > 0).view((-1,) + (1,) * (rst.dim() - 1))
                 rst = torch.where(has, rst, rst.new_zeros(()))
             return rst
+
+
+class FeaturePropagation(nn.Module):
+    """The PointNet++ feature-propagation level (PointNet2FP of DGL's example; PyG's knn_interpolate + MLP): the features of a coarse
+    level are carried up to the M points of a finer one,
+        h_q = sum_r w[q, r] feat[index[q, r]]     over the k nearest coarse points of q's own cloud, w the normalised 1 / (d^2 + eps)
+    (transform.knn_interpolate: ops.segment_knn_query, whose index is the in-CSR, and the u_mul_e / sum g-SpMM), concatenated with the
+    finer level's own `skip` features when skip_feats > 0, then Linear -> (BatchNorm1d) -> ReLU per entry of `sizes` over the M
+    points.  The gradient reaches feat, skip and the parameters; the interpolation weights are constants."""
+
+    def __init__(self, in_feats, skip_feats, sizes, batch_norm=False, k=3):
+        super(FeaturePropagation, self).__init__()
+        sizes = [int(v) for v in sizes]
+        if in_feats < 1 or skip_feats < 0 or not sizes or min(sizes) < 1 or isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise DGLError("FeaturePropagation: needs in_feats >= 1, skip_feats >= 0, at least one layer size >= 1 and an integer k >= 1, "
+                           "got %r, %r, %r, %r" % (in_feats, skip_feats, sizes, k))
+        self.in_feats, self.skip_feats, self.sizes, self.batch_norm, self.k = in_feats, skip_feats, sizes, batch_norm, k
+        self.layers = nn.ModuleList([Linear(a, b) for a, b in zip([in_feats + skip_feats] + sizes[:-1], sizes)])
+        if batch_norm:
+            self.bns = nn.ModuleList([BatchNorm1d(b) for b in sizes])
+
+    def forward(self, feat, pos_src, pos_dst, segs_src, segs_dst, skip=None):
+        """feat [N, in_feats] on the coarse points pos_src [N, D]; pos_dst [M, D] the finer points, skip [M, skip_feats] their own
+        features; segs_src / segs_dst the clouds' lengths in either level (Python lists) -> [M, sizes[-1]]"""
+        from .transform import knn_interpolate
+        if (skip is None) != (self.skip_feats == 0):
+            raise DGLError("FeaturePropagation: skip_feats = %d %s skip features" % (self.skip_feats, "needs" if skip is None else "takes no"))
+        if feat.dim() != 2 or feat.shape[1] != self.in_feats or (skip is not None and (skip.dim() != 2 or skip.shape[1] != self.skip_feats
+                                                                                       or skip.shape[0] != pos_dst.shape[0])):
+            raise DGLError("FeaturePropagation: expected features [*, %d] and skip features [%d, %d]"
+                           % (self.in_feats, pos_dst.shape[0], self.skip_feats))
+        h = knn_interpolate(feat, pos_src, pos_dst, segs_src, segs_dst, self.k)
+        if skip is not None:
+            h = torch.cat([h, skip], 1)
+        for i, layer in enumerate(self.layers):
+            h = layer(h)
+            h = F.relu(self.bns[i](h) if self.batch_norm else h)
+        return h
+
+    def extra_repr(self):
+        return "in_feats={in_feats}, skip_feats={skip_feats}, sizes={sizes}, k={k}".format(**self.__dict__)
 
 
 class WeightAndSum(nn.Module):

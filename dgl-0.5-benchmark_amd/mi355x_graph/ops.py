@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -2077,6 +2077,111 @@ def segment_knn(seglen, x, k, total=None, return_dist=False):
         sparse.backend_for(x)  # no CPU backend: DGLError
         index, dist = _segment_knn_composed(offsets, x.detach(), k, return_dist)
     return (index, dist) if return_dist else index
+
+
+def _segment_knn_query_composed(offsets, x, q_offsets, y, k, eps, return_dist, return_weight):
+    """ops.segment_knn_query through torch operators, by the same definition: per segment the direct-form distances
+    sum_c (y_q - x_j)^2 of its queries to its references, built _KNN_COMPOSED_ELEMS elements at a time, and a stable sort of every
+    query's row of them (NaN greatest, equal distances keep the lower row); index -1 and dist +inf past the reference segment's end;
+    then the weights 1 / (d + eps) of the valid ranks over their sum.  One read-back of the two offset vectors, a loop over
+    segments.  The form for CPU tensors, for k > 64 or D > 256, under MGX_TORCH_OPS=1 and with config.KNN_QUERY_FUSED off."""
+    M, D = int(y.shape[0]), int(y.shape[1])
+    index = torch.full((M, k), -1, dtype=torch.int64, device=y.device)
+    dist = torch.full((M, k), float("inf"), dtype=torch.float32, device=y.device)
+    with torch.no_grad():
+        ends, q_ends = offsets.tolist(), q_offsets.tolist()
+        for beg, end, q_beg, q_end in zip(ends[:-1], ends[1:], q_ends[:-1], q_ends[1:]):
+            n, nq = end - beg, q_end - q_beg
+            if n <= 0 or nq <= 0:
+                continue
+            seg, m = x[beg:end], min(k, n)
+            step = max(1, _KNN_COMPOSED_ELEMS // (n * D))
+            for q in range(0, nq, step):
+                rows = slice(q_beg + q, q_beg + min(q + step, nq))
+                diff = y[rows].unsqueeze(1) - seg.unsqueeze(0)                                  # [queries, n, D]
+                d = (diff * diff).sum(-1)
+                d = torch.where(d != d, d.new_full((), float("nan")), d)
+                order = torch.sort(d, dim=1, stable=True)
+                index[rows, :m] = order.indices[:, :m] + beg
+                dist[rows, :m] = order.values[:, :m]
+        weight = None
+        if return_weight:
+            valid = index >= 0
+            inv = torch.where(valid, 1.0 / (dist + eps), dist.new_zeros(()))
+            weight = torch.where(valid, inv / inv.sum(1, keepdim=True), dist.new_zeros(()))
+    return index, (dist if return_dist else None), weight
+
+
+def _segment_knn_query_args(ref_seglen, x, query_seglen, y, k, ref_total, query_total, eps):
+    who = "segment_knn_query"
+    for name, t in (("x", x), ("y", y)):
+        if not torch.is_tensor(t) or t.dim() != 2:
+            raise DGLError("%s: expected %s [rows, D], got %s" % (who, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__,))
+        if t.dtype != torch.float32:
+            raise DGLError("%s expects float32 input, got %s for %s" % (who, t.dtype, name))
+    if x.device != y.device:
+        raise DGLError("%s: operands on different devices: %s vs %s" % (who, x.device, y.device))
+    if x.shape[1] != y.shape[1] or x.shape[1] < 1:
+        raise DGLError("%s: x and y need the same number of columns, at least one (got %d and %d)" % (who, x.shape[1], y.shape[1]))
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise DGLError("%s: k must be an integer >= 1, got %r" % (who, k))
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 <= eps < float("inf"):
+        raise DGLError("%s: eps must be a finite number >= 0, got %r" % (who, eps))
+    for seglen in (ref_seglen, query_seglen):
+        if torch.is_tensor(seglen) and seglen.device != x.device and seglen.device.type != "cpu":  # host lengths go with any x
+            raise DGLError("%s: operands on different devices: %s vs %s" % (who, x.device, seglen.device))
+    offsets, n = _segment_offsets(ref_seglen, x, ref_total, who)
+    q_offsets, m = _segment_offsets(query_seglen, y, query_total, who)
+    if ref_seglen.shape[0] != query_seglen.shape[0]:
+        raise DGLError("%s: %d reference segments but %d query segments" % (who, ref_seglen.shape[0], query_seglen.shape[0]))
+    return offsets, n, q_offsets, m
+
+
+def segment_knn_query_fused(ref_seglen, x, query_seglen, y, k, ref_total=None, query_total=None, return_dist=False, return_weight=False,
+                            eps=1e-8):
+    """True when segment_knn_query(...) with these operands runs csrc/knn.hip (else the composition of distances and a stable sort)."""
+    if (not torch.is_tensor(x) or not torch.is_tensor(y) or x.dim() != 2 or y.dim() != 2 or x.dtype != torch.float32
+            or y.dtype != torch.float32 or x.device != y.device or x.shape[1] != y.shape[1]
+            or not torch.is_tensor(ref_seglen) or not torch.is_tensor(query_seglen) or ref_seglen.dim() != 1 or query_seglen.dim() != 1
+            or ref_seglen.shape[0] != query_seglen.shape[0]
+            or any(s.device != x.device and s.device.type != "cpu" for s in (ref_seglen, query_seglen))
+            or isinstance(k, bool) or not isinstance(k, int) or k < 1
+            or not config.KNN_QUERY_FUSED or x.device.type not in sparse._BACKENDS or not _readout_kernels(x)
+            or not hasattr(sparse.backend_for(x), "segment_knn_query")):
+        return False
+    N, M, D = int(x.shape[0]), int(y.shape[0]), int(x.shape[1])
+    ld = int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= D else D
+    ldq = int(y.stride(0)) if y.stride(1) == 1 and y.stride(0) >= D else D
+    return (M > 0 and D >= 1 and N < 2 ** 31 and M < 2 ** 31 and ref_seglen.shape[0] < 2 ** 31 and N * ld < 2 ** 30 and M * ldq < 2 ** 30
+            and sparse.backend_for(x).segment_knn_query_supported(k, D))
+
+
+def segment_knn_query(ref_seglen, x, query_seglen, y, k, ref_total=None, query_total=None, return_dist=False, return_weight=False, eps=1e-8):
+    """The k nearest reference rows of every query row, segment by segment (PyG's knn(x, y, k, batch_x, batch_y); the neighbour step of
+    PointNet++'s feature propagation): index int64 [M, k], or a tuple (index[, dist][, weight]) with return_dist / return_weight.
+
+    x [N, D] the references and y [M, D] the queries (fp32; each may be a row-strided column block); ref_seglen [S] and query_seglen [S]
+    the lengths of their consecutive row segments, the same number of segments in both.  Query q of query segment s is answered from
+    reference segment s alone: d(q, j) = sum_c (y[q,c] - x[j,c])^2 in fp32, the direct difference form of segment_knn; neighbours are
+    ordered by (d, j) ascending, so equal distances keep the lower row first; a NaN distance is the greatest key.  index holds global
+    row numbers of x.  A reference segment shorter than k is padded with index -1 and dist +inf (an empty one: every rank).
+    weight [M, k] = (1 / (dist + eps)) / sum over the valid ranks of (1 / (dist + eps)), the normalised inverse squared-distance weights
+    of knn_interpolate (eps = 1e-8 is the DGL PointNet++ example's constant): 0 at a padded rank, NaN at every valid rank of a query
+    that has a NaN distance.  No output is differentiable.
+    `ref_total` / `query_total`: the row counts when the caller knows them (no read-back of device lengths).  Device operands with
+    k <= 64 and D <= 256 run csrc/knn.hip -- the kernel of segment_knn, which is the case y = x -- in one launch that writes no [M, n]
+    matrix (segment_knn_query_fused); everything else -- CPU tensors under a registered CPU backend, larger k or D,
+    config.KNN_QUERY_FUSED = False -- is a stable sort of the distances per segment in torch operators."""
+    offsets, n, q_offsets, m = _segment_knn_query_args(ref_seglen, x, query_seglen, y, k, ref_total, query_total, eps)
+    if segment_knn_query_fused(ref_seglen, x, query_seglen, y, k, n, m, return_dist, return_weight, eps):
+        with torch.no_grad():
+            index, dist, weight = sparse.backend_for(x).segment_knn_query(offsets, x.detach(), q_offsets, y.detach(), k, float(eps),
+                                                                          return_dist, return_weight)
+    else:
+        sparse.backend_for(x)  # no CPU backend: DGLError
+        index, dist, weight = _segment_knn_query_composed(offsets, x.detach(), q_offsets, y.detach(), k, float(eps), return_dist, return_weight)
+    out = (index,) + ((dist,) if return_dist else ()) + ((weight,) if return_weight else ())
+    return out if len(out) > 1 else index
 
 
 # ----------------------------------------------------------------------------- point clouds: farthest point sampling and ball query

@@ -1249,6 +1249,29 @@ class HipBackend(object):
             _lib.check(_lib.lib().mgx_segment_knn(S, _ptr(offsets), N, D, ld, _ptr(x2d), int(k), _ptr(index), _ptr(dist), _stream(dev)))
         return index, dist
 
+    @classmethod
+    def segment_knn_query_supported(cls, k, D):
+        """Shapes mgx_segment_knn_query takes: 1 <= k <= 64, 1 <= D <= 256."""
+        return bool(_lib.lib().mgx_segment_knn_query_supported(int(k), int(D)))
+
+    def segment_knn_query(self, offsets, x2d, q_offsets, y2d, k, eps, return_dist, return_weight):
+        """references x2d [N, D], queries y2d [M, D] (column blocks of wider matrices are taken as they are) ->
+        (index int64 [M, k], dist [M, k] | None, weight [M, k] | None)."""
+        dev = self._check_dev(offsets, x2d, q_offsets, y2d)
+        S, N, M, D = offsets.shape[0] - 1, int(x2d.shape[0]), int(y2d.shape[0]), int(x2d.shape[1])
+        if not (x2d.stride(1) == 1 and x2d.stride(0) >= D) and N > 0:  # a stride the kernel cannot take becomes a dense copy
+            x2d = x2d.contiguous()
+        if not (y2d.stride(1) == 1 and y2d.stride(0) >= D) and M > 0:
+            y2d = y2d.contiguous()
+        ld, ldq = int(x2d.stride(0)) if N > 0 else D, int(y2d.stride(0)) if M > 0 else D
+        index = torch.empty((M, k), dtype=torch.int64, device=dev)
+        dist = torch.empty((M, k), dtype=torch.float32, device=dev) if return_dist else None
+        weight = torch.empty((M, k), dtype=torch.float32, device=dev) if return_weight else None
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_knn_query", k=int(k), D=D, segments=int(S), rows=N, queries=M):
+            _lib.check(_lib.lib().mgx_segment_knn_query(S, _ptr(offsets), N, ld, _ptr(x2d), _ptr(q_offsets), M, ldq, _ptr(y2d), D, int(k),
+                                                        ctypes.c_float(eps), _ptr(index), _ptr(dist), _ptr(weight), _stream(dev)))
+        return index, dist, weight
+
     # ---- farthest point sampling (csrc/fps.hip) and fixed-radius ball query (csrc/ballquery.hip)
     @classmethod
     def segment_fps_supported(cls, D, max_len):

@@ -396,6 +396,77 @@ def fixed_radius_block(pos, centers, radius, max_neighbors, segs):
     return block
 
 
+def knn_block(x, x_segs, y, y_segs, k, eps=1e-8):
+    """The neighbour step of PointNet++'s feature propagation as a block: x [N, D] holds consecutive reference sets of x_segs[0],
+    x_segs[1], ... points (a coarse level's centres, say), y [M, D] the query sets of y_segs[0], y_segs[1], ... points (Python lists of
+    lengths, as many sets in both).  The block has N source nodes and M destination nodes; destination q's predecessors are the k
+    references of its own set nearest to y[q], nearest first (ops.segment_knn_query).
+
+    Every destination has exactly k in-edges and the index IS the in-CSR (indptr = arange(M + 1) * k, no edge-id permutation), as in
+    fixed_radius_block: no sort or COO -> CSR pass runs, and nothing is read back.  A reference set shorter than k would leave a -1
+    in the index, so it is a DGLError: no -1 reaches a gather.  The block carries edata["w"] [M * k], the normalised inverse
+    squared-distance weights (1 / (d + eps)) / sum (constants: no gradient flows to the positions), srcdata["pos"] = x and
+    dstdata["pos"] = y."""
+    from . import ops
+    from .sparse import CsrView
+    for name, t in (("x", x), ("y", y)):
+        if not torch.is_tensor(t) or t.dim() != 2 or not t.dtype.is_floating_point:
+            raise DGLError("knn_block: expected floating-point points %s [rows, D], got %s"
+                           % (name, (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__,))
+    if x.shape[1] != y.shape[1] or x.device != y.device:
+        raise DGLError("knn_block: x %s on %s and y %s on %s do not go together" % (tuple(x.shape), x.device, tuple(y.shape), y.device))
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise DGLError("knn_block: k must be an integer >= 1, got %r" % (k,))
+    x_lens, y_lens = [int(n) for n in x_segs], [int(n) for n in y_segs]
+    N, M = int(x.shape[0]), int(y.shape[0])
+    for lens, rows, what in ((x_lens, N, "reference"), (y_lens, M, "query")):
+        if any(n < 0 for n in lens) or sum(lens) != rows:
+            raise DGLError("knn_block: %s segment lengths %s do not sum to the %d points" % (what, lens if len(lens) <= 8 else lens[:8] + ["..."], rows))
+    if len(x_lens) != len(y_lens):
+        raise DGLError("knn_block: %d reference sets but %d query sets" % (len(x_lens), len(y_lens)))
+    short = [n for n in x_lens if n < k]
+    if short:
+        raise DGLError("knn_block: a reference set of %d points has no %d nearest neighbours (every set needs at least k points)" % (short[0], k))
+    seglens = []
+    for lens in (x_lens, y_lens):
+        if len(lens) >= 1 and len(set(lens)) == 1:  # equal sets: the lengths are filled in on the device, no host-to-device copy
+            seglens.append(torch.full((len(lens),), lens[0], dtype=torch.int64, device=x.device))
+        else:
+            seglens.append(torch.tensor(lens, dtype=torch.int64))
+    index, weight = ops.segment_knn_query(seglens[0], x.detach().float(), seglens[1], y.detach().float(), k, ref_total=N, query_total=M,
+                                          return_weight=True, eps=eps)
+    idtype = torch.int32 if max(M * k, N) < 2 ** 31 else torch.int64
+    indptr = torch.arange(M + 1, dtype=idtype, device=x.device) * k
+    csc = CsrView(M, N, indptr, index.reshape(-1).to(idtype), None)
+    if k <= 256:
+        csc._plan = None  # every row has k entries: nothing to split or balance, and no host read of the lengths
+    idx = GraphIndex(N, M, csc=csc)
+    idx.max_in_degree_hint = k
+    idx.ephemeral = True  # rebuilt before every level of every step
+    idx.plain_transpose = True  # the out-CSR the backward to the features asks for: no schedule, so no read-back inside a captured step
+    idx._mark_ephemeral(csc)
+    idx._zero_in_deg = False
+    block = DGLGraph(idx, is_block=True)
+    block.edata["w"] = weight.reshape(-1)
+    block.srcdata["pos"] = x
+    block.dstdata["pos"] = y
+    return block
+
+
+def knn_interpolate(feat, pos_src, pos_dst, segs_src, segs_dst, k=3):
+    """PyG's knn_interpolate / the interpolation of DGL's PointNet2FP: feat [N, C] on the points pos_src [N, D] -> [M, C] on the points
+    pos_dst [M, D], out[q] = sum_r w[q, r] feat[index[q, r]] over the k nearest source points of q's own set with the normalised
+    inverse squared-distance weights of knn_block: the u_mul_e / sum g-SpMM over that block.  The gradient flows to feat only (through
+    the block's plain transposed CSR); the weights are constants, as in PyG."""
+    from . import ops
+    if not torch.is_tensor(feat) or feat.dim() < 1 or not torch.is_tensor(pos_src) or feat.shape[0] != pos_src.shape[0]:
+        raise DGLError("knn_interpolate: feat must hold one row per source point, got %s for %s points"
+                       % (tuple(feat.shape) if torch.is_tensor(feat) else type(feat).__name__,
+                          pos_src.shape[0] if torch.is_tensor(pos_src) else type(pos_src).__name__))
+    block = knn_block(pos_src, segs_src, pos_dst, segs_dst, k)
+    return ops.u_mul_e_sum(block, feat, block.edata["w"])
+
+
 def metis_partition_assignment(g, k, balance_ntypes=None, balance_edges=False):
     """k-way edge-cut node partition -> [N] part ids.  The role of dgl.transform.metis_partition_assignment
     (end_to_end/sampling/link-prediction/dgl_cluster_sampler.py:24); METIS itself is not available offline, the

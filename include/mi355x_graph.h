@@ -763,6 +763,28 @@ int32_t mgx_segment_knn_supported(int64_t k, int64_t D);
 int32_t mgx_segment_knn(int64_t num_segments, const int64_t* offsets, int64_t N, int64_t D, int64_t ld, const float* x, int64_t k,
                         int64_t* index, float* dist /* may be NULL */, void* stream);
 
+/* The same search from a query set into a reference set (PyG's knn(x, y, k, batch_x, batch_y), the neighbour step of PointNet++'s
+ * feature propagation): references x [N, ld] in num_segments segments given by offsets, queries y [M, ldq] in the SAME number of
+ * segments given by q_offsets (num_segments + 1 entries each).  Query row q of query segment s gets the k rows j of reference segment
+ * s = [offsets[s], offsets[s+1]) with the smallest d(q, j) = sum_c (y[q,c] - x[j,c])^2, by the arithmetic and the order above; index
+ * holds global rows of x.  Ranks at or beyond the reference segment's length hold index -1 and dist +inf, and so does every rank of a
+ * query row that no query segment holds.  mgx_segment_knn is the case y = x, q_offsets = offsets: one kernel serves both.
+ *   weight fp32 [M, k] or NULL: weight[q, r] = (1 / (dist[q, r] + eps)) / sum_r' (1 / (dist[q, r'] + eps)) over the valid ranks r',
+ *   the normalised inverse squared-distance weights of knn_interpolate; a padded rank gets 0, a query without a valid rank k zeros; a
+ *   NaN distance makes the sum, and so every valid rank's weight of that query, NaN.  The terms are fp32 with a true division each;
+ *   the sum is a balanced binary tree over the ranks padded with zeros to 64 -- (t0 + t1) + (t2 + t3), then pairs of those, ... -- so
+ *   it is deterministic and the same whatever k.
+ * Every output element is written.  Supported (mgx_segment_knn_query_supported(k, D); everything else is MGX_ERR_UNSUPPORTED before a
+ * launch): 1 <= k <= 64, 1 <= D <= 256, N, M and num_segments < 2^31, N * ld and M * ldq * 4 bytes < 4 GiB.  One launch whose grid
+ * depends on M only; a workgroup's 16 consecutive query rows stream the union of their reference segments, one contiguous row
+ * range.  Nothing is read back to the host, no atomics: capture-safe, reruns are bitwise equal.  Purely additive:
+ * mgx_abi_version() stays 35. */
+int32_t mgx_segment_knn_query_supported(int64_t k, int64_t D);
+int32_t mgx_segment_knn_query(int64_t num_segments, const int64_t* offsets, int64_t N, int64_t ld, const float* x,
+                              const int64_t* q_offsets, int64_t M, int64_t ldq, const float* y, int64_t D, int64_t k, float eps,
+                              int64_t* index /* [M, k] */, float* dist /* [M, k] or NULL */, float* weight /* [M, k] or NULL */,
+                              void* stream);
+
 /* ------------------------------------------------------------------ point clouds: farthest point sampling (csrc/fps.hip)
  * dgl.geometry.farthest_point_sampler over the segments described above (x [N, ld] fp32, the first D floats of a row are the point).
  * Per segment of length len starting at row beg:
