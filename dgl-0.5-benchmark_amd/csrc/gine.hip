@@ -121,40 +121,13 @@ __global__ __launch_bounds__(kBlock) void gine_kernel(const GineArgs a) {
 template <bool BWD>
 static bool gine_launch(const GineArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)a.plan.nblocks), block(kBlock);
-  int G = 1;
-  while (G * 4 < a.D) G <<= 1;
-  switch (G) {
+  switch (row_walk_lanes(a.D)) {
 #define MGX_GINE_G(g) case g: hipLaunchKernelGGL((gine_kernel<g, BWD>), grid, block, 0, s, a); return true;
     MGX_GINE_G(1) MGX_GINE_G(2) MGX_GINE_G(4) MGX_GINE_G(8) MGX_GINE_G(16) MGX_GINE_G(32) MGX_GINE_G(64)
 #undef MGX_GINE_G
     default: return false;
   }
 }
-
-static bool gine_width_ok(int64_t D) { return D >= 4 && D % 4 == 0 && D <= 256; }
-
-// gathered rows are addressed by 32-bit byte offsets: x, d out [nodes, D] and w, d w [nnz, D] each stay below 4 GiB
-static bool gine_size_ok(const mgx_csr* csr, int64_t D) {
-  int64_t most = csr->num_rows > csr->num_cols ? csr->num_rows : csr->num_cols;
-  if (csr->nnz > most) most = csr->nnz;
-  return csr->nnz < (int64_t(1) << 31) && most * D * 4 < (int64_t(1) << 32);
-}
-
-static int32_t gine_check(const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t D, const char* who) {
-  MGX_CHECK_ARG(csr != nullptr, "%s: csr is NULL", who);
-  MGX_CHECK_ARG(csr->idx_bits == 32 || csr->idx_bits == 64, "%s: idx_bits must be 32 or 64 (got %d)", who, csr->idx_bits);
-  MGX_CHECK_ARG(D >= 4 && D % 4 == 0, "%s: D must be a positive multiple of 4 (got %lld)", who, (long long)D);
-  MGX_CHECK_ARG(csr->indptr && (csr->indices || csr->nnz <= 0), "%s: indptr / indices is NULL", who);
-  const int32_t st = plan_check(csr, plan, who);  // argument errors first, then what is outside the supported set
-  if (st != MGX_OK) return st;
-  if (csr->idx_bits != 32) MGX_UNSUPPORTED("%s: 32-bit graph indices only (got %d)", who, csr->idx_bits);
-  if (!gine_width_ok(D)) MGX_UNSUPPORTED("%s: needs D <= 256 (got %lld)", who, (long long)D);
-  if (csr->nnz <= 0) MGX_UNSUPPORTED("%s: graph without edges", who);
-  if (!gine_size_ok(csr, D)) MGX_UNSUPPORTED("%s: operands beyond 32-bit byte offsets", who);
-  return MGX_OK;
-}
-
-static bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 static void gine_fill(GineArgs& a, const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t D, const float* x, const float* w,
                       const float* scale, void* workspace) {
@@ -170,7 +143,7 @@ static void gine_fill(GineArgs& a, const mgx_csr* csr, const mgx_spmm_plan* plan
 
 extern "C" int32_t mgx_gine_supported(const mgx_csr* csr, int64_t D) {
   using namespace mgx;
-  return csr && csr->idx_bits == 32 && csr->nnz > 0 && gine_width_ok(D) && gine_size_ok(csr, D);
+  return row_walk_supported(csr, D);
 }
 
 extern "C" int64_t mgx_gine_workspace(const mgx_spmm_plan* plan, int64_t D) {
@@ -181,12 +154,12 @@ extern "C" int32_t mgx_gine_fwd(const mgx_csr* csc, const mgx_spmm_plan* plan, i
                                 float* out, void* workspace, void* stream) {
   using namespace mgx;
   MGX_ENTER();
-  int32_t st = gine_check(csc, plan, D, "mgx_gine_fwd");
+  int32_t st = row_walk_check(csc, plan, D, "mgx_gine_fwd");
   if (st != MGX_OK) return st;
   MGX_CHECK_ARG(x && w && out, "mgx_gine_fwd: NULL pointer");
-  MGX_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(out), "mgx_gine_fwd: x, w and out must be 16-byte aligned");
+  MGX_CHECK_ARG(row_aligned16(x) && row_aligned16(w) && row_aligned16(out), "mgx_gine_fwd: x, w and out must be 16-byte aligned");
   const bool hubs = plan && plan->num_slots > 0;
-  MGX_CHECK_ARG(!hubs || (workspace && aligned16(workspace)), "mgx_gine_fwd: plan has split rows but no 16-byte aligned workspace");
+  MGX_CHECK_ARG(!hubs || (workspace && row_aligned16(workspace)), "mgx_gine_fwd: plan has split rows but no 16-byte aligned workspace");
   hipStream_t s = (hipStream_t)stream;
   GineArgs a;
   gine_fill(a, csc, plan, D, x, w, scale, workspace);
@@ -205,13 +178,13 @@ extern "C" int32_t mgx_gine_bwd(const mgx_csr* csr, const mgx_spmm_plan* plan, i
                                 const float* d_out, float* d_x, float* d_w, void* workspace, void* stream) {
   using namespace mgx;
   MGX_ENTER();
-  int32_t st = gine_check(csr, plan, D, "mgx_gine_bwd");
+  int32_t st = row_walk_check(csr, plan, D, "mgx_gine_bwd");
   if (st != MGX_OK) return st;
   MGX_CHECK_ARG(x && w && d_out, "mgx_gine_bwd: NULL pointer");
-  MGX_CHECK_ARG(aligned16(x) && aligned16(w) && aligned16(d_out) && aligned16(d_x) && aligned16(d_w),
+  MGX_CHECK_ARG(row_aligned16(x) && row_aligned16(w) && row_aligned16(d_out) && row_aligned16(d_x) && row_aligned16(d_w),
                 "mgx_gine_bwd: x, w, d_out and the gradients must be 16-byte aligned");
   const bool hubs = d_x && plan && plan->num_slots > 0;
-  MGX_CHECK_ARG(!hubs || (workspace && aligned16(workspace)), "mgx_gine_bwd: plan has split rows but no 16-byte aligned workspace");
+  MGX_CHECK_ARG(!hubs || (workspace && row_aligned16(workspace)), "mgx_gine_bwd: plan has split rows but no 16-byte aligned workspace");
   if (!d_x && !d_w) return MGX_OK;
   hipStream_t s = (hipStream_t)stream;
   GineArgs a;

@@ -2,6 +2,7 @@
 // of an mgx_spmm_plan as kernel arguments, a block's stretch of them and one item's (row, edge range), the slot convention of a
 // split (hub) row, the two kernels that merge a hub row's chunks in slot order, and the plan's argument checks.
 // What stays with each family: its edge loop and lane-group merge, its NaN rule and its statistics layout (dotattn.hip).
+// The row walks with 16-byte lanes (gine.hip, multiagg.hip) also take their supported set and argument checks from here (row_walk_*).
 #pragma once
 #include <math.h>
 
@@ -90,6 +91,43 @@ __device__ __forceinline__ float nan_max(float a, float b) { return (a > b || a 
 
 // a lane's 16 bytes of a row product (dotattn.hip, segattn.hip); lanes_sum<LPH> completes the head's dot product
 __device__ __forceinline__ float dot4(const v4f& a, const v4f& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+
+// ---------------------------------------------------------------------------------------------- row walks with 16-byte lanes
+// What gine.hip and multiagg.hip share on the host side: G lanes of 16 bytes cover a row of D floats, the supported set and its checks.
+static inline int row_walk_lanes(int D) {  // the smallest power of two G with 4 G >= D
+  int G = 1;
+  while (G * 4 < D) G <<= 1;
+  return G;
+}
+
+static inline bool row_walk_width_ok(int64_t D) { return D >= 4 && D % 4 == 0 && D <= 256; }
+
+// gathered rows are addressed by 32-bit byte offsets: every [nodes, D] and [nnz, D] matrix stays below 4 GiB
+static inline bool row_walk_size_ok(const mgx_csr* csr, int64_t D) {
+  int64_t most = csr->num_rows > csr->num_cols ? csr->num_rows : csr->num_cols;
+  if (csr->nnz > most) most = csr->nnz;
+  return csr->nnz < (int64_t(1) << 31) && most * D * 4 < (int64_t(1) << 32);
+}
+
+static inline bool row_walk_supported(const mgx_csr* csr, int64_t D) {
+  return csr && csr->idx_bits == 32 && csr->nnz > 0 && row_walk_width_ok(D) && row_walk_size_ok(csr, D);
+}
+
+static inline int32_t row_walk_check(const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t D, const char* who) {
+  MGX_CHECK_ARG(csr != nullptr, "%s: csr is NULL", who);
+  MGX_CHECK_ARG(csr->idx_bits == 32 || csr->idx_bits == 64, "%s: idx_bits must be 32 or 64 (got %d)", who, csr->idx_bits);
+  MGX_CHECK_ARG(D >= 4 && D % 4 == 0, "%s: D must be a positive multiple of 4 (got %lld)", who, (long long)D);
+  MGX_CHECK_ARG(csr->indptr && (csr->indices || csr->nnz <= 0), "%s: indptr / indices is NULL", who);
+  const int32_t st = plan_check(csr, plan, who);  // argument errors first, then what is outside the supported set
+  if (st != MGX_OK) return st;
+  if (csr->idx_bits != 32) MGX_UNSUPPORTED("%s: 32-bit graph indices only (got %d)", who, csr->idx_bits);
+  if (!row_walk_width_ok(D)) MGX_UNSUPPORTED("%s: needs D <= 256 (got %lld)", who, (long long)D);
+  if (csr->nnz <= 0) MGX_UNSUPPORTED("%s: graph without edges", who);
+  if (!row_walk_size_ok(csr, D)) MGX_UNSUPPORTED("%s: operands beyond 32-bit byte offsets", who);
+  return MGX_OK;
+}
+
+static inline bool row_aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
 // ---------------------------------------------------------------------------------------------- hub rows
 static inline dim3 hub_grid(const mgx_spmm_plan* plan) {  // one wave per hub row

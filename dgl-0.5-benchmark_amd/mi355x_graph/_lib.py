@@ -93,6 +93,10 @@ SIGNATURES = {
     "mgx_gine_workspace": (_i64, [_vp, _i64]),
     "mgx_gine_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _vp, _vp]),
     "mgx_gine_bwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),
+    "mgx_multi_agg_supported": (_i32, [_csr_p, _i64]),
+    "mgx_multi_agg_workspace": (_i64, [_vp, _i64]),
+    "mgx_multi_agg_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _vp, _fp, _vp, _vp]),
+    "mgx_multi_agg_bwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _fp, _vp, _fp, _vp, _fp, _fp, _vp, _vp]),
     "mgx_head_dot_fwd": (_i32, [_i64, _i64, _i64, _fp, _fp, _fp, _fp, _fp, _vp]),
     "mgx_head_dot_bwd_workspace": (_i64, [_i64, _i64]),
     "mgx_head_dot_bwd": (_i32, [_i64, _i64, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),

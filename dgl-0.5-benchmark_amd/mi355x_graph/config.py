@@ -41,6 +41,17 @@ GAT_PACK = True            # one packed gather operand per node for the fused wa
 DOT_ATTENTION_FUSED = True  # the fused walks of csrc/dotattn.hip; False: u_dot_v -> edge_softmax -> u_mul_e/sum through the existing operators
 # ---- relu(x_u + w_e) messages summed per destination (ops.gine_sum, nn.GINEConv, graph_classification.py --fused-message)
 GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> relu -> mul -> copy_e/sum through the existing operators
+# ---- sum / mean / var / std / max / min of the same messages at once (ops.multi_aggregate, nn.PNAConv, graph_classification.py --model pna)
+MULTI_AGG_FUSED = True  # the fused walks of csrc/multiagg.hip; False: one g-SpMM per aggregate through the existing operators
+# ONE of sum / mean / max / min without edge features is a single g-SpMM as a composition; the fused form walks the graph once as well
+# and has the longer host path.  pna_bench.py, forward + backward, fused / composed per call (docs/LOG_pna.md):
+#   sum, mean   lose 0.75 - 0.81x at D = 64 on all four batches (3 090 ... 110 036 edges) and at D = 256 up to 73 600 edges; win 1.07x /
+#               1.14x only on the 2048-graph batch at D = 256 -- given up: a single sum or mean always takes the g-SpMM
+#   max, min    D = 64: lose 0.92x (88 against 81 us) at 3 090 and 13 266 edges, win 1.2 - 1.4x at 73 600 and 110 036; D = 256: win
+#               everywhere (1.4 - 5.2x).  Widths between 64 and 256 were not measured: the gate covers the measured losing region only.
+MULTI_AGG_SINGLE_SUM_FUSED = False  # a single sum or mean without w: the fused walk (True) or the g-SpMM
+MULTI_AGG_SINGLE_MIN_EDGES = 16384  # a single max or min without w, D <= MULTI_AGG_SINGLE_MAX_D, fewer edges than this: the g-SpMM
+MULTI_AGG_SINGLE_MAX_D = 64
 
 # ---- graph readout (ops.segment_attention, nn.GlobalAttentionPooling, nn.Set2Set)
 SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: segment max -> gather -> exp -> segment sum -> gather -> multiply -> segment sum

@@ -2,6 +2,7 @@
   GATConv    main_dgl_reddit_gat.py:10,31-55 (u_add_v SDDMM + fused edge_softmax + u_mul_e/sum SpMM)
   DotGatConv dgl.nn.pytorch.DotGatConv (u_dot_v SDDMM + edge_softmax + u_mul_e/sum SpMM, fused: ops.dot_attention)
   GINEConv   dgl.nn.pytorch.GINEConv (sum of relu(h_u + e_uv) messages, fused: ops.gine_sum)
+  PNAConv    dgl.nn.pytorch.PNAConv (mean / max / min / std ... of one message per edge, fused: ops.multi_aggregate)
   SAGEConv   main_dgl_arxiv_sage_nn.py:9,27-34
   GraphConv  main_dgl_enzymes_gcn_nn.py:12,29-36
   AvgPooling / SumPooling / MaxPooling   main_dgl_molhiv_gcn.py:75,93
@@ -499,6 +500,106 @@ class GINEConv(nn.Module):
         if self.apply_func is not None:
             rst = self.apply_func(rst)
         return rst
+
+
+class PNAConvTower(nn.Module):
+    """The parameters of one tower of PNAConv (UPSTREAM dgl.nn.pytorch.conv.pnaconv.PNAConvTower: M, U, batchnorm, dropout).  The
+    arithmetic is PNAConv.forward's: all towers share one aggregation call."""
+
+    def __init__(self, in_size, out_size, n_agg, n_scalers, dropout=0., edge_feat_size=0):
+        super(PNAConvTower, self).__init__()
+        self.M = nn.Linear(2 * in_size + edge_feat_size, in_size)
+        self.U = nn.Linear((n_agg * n_scalers + 1) * in_size, out_size)
+        self.dropout = nn.Dropout(dropout)
+        self.batchnorm = BatchNorm1d(out_size)
+
+
+class PNAConv(nn.Module):
+    """dgl.nn.pytorch.PNAConv (UPSTREAM): Principal Neighbourhood Aggregation.  Per tower t (a column block of the features)
+
+        msg_e = M_t [h_u ; h_v ; a_e],   agg = [AGG(msg) for AGG in aggregators],   h_neigh = [scaler(agg, d) for scaler in scalers]
+        h_t   = dropout(batchnorm(U_t [h_v ; h_neigh] / sqrt(nodes in v's graph)))
+
+    then mixing_layer = Linear + LeakyReLU over the towers' concatenation and the residual when in_size == out_size.
+    aggregators out of sum, mean, max, min, var, std (std = sqrt(var + 1e-30), var = relu(E[m^2] - E[m]^2) as upstream);
+    scalers out of identity, amplification (* log(d + 1) / delta), attenuation (* delta / log(d + 1), 0 where d == 0).
+    A node without in-edges has h_neigh = 0, as the mailbox UDF leaves it.
+
+    M is never applied per edge: with M.weight = [W_src | W_dst | W_e] by columns, a = h W_src^T and b = h W_dst^T + bias per NODE
+    and c = a_e W_e^T per edge give msg_e = a_u + b_v + c_e; all towers are column blocks of one matrix, so ONE
+    ops.multi_aggregate(g, a, aggregators, w=c) serves the layer (csrc/multiagg.hip: one walk forward, one backward), and b_v is
+    added afterwards: to mean / max / min as it is, d times to sum, not at all to var / std.  Without edge features no tensor of E rows
+    exists.
+
+    Knowingly different from upstream: moment3 / moment4 / moment5 are not offered; `delta` must be positive; on a block (or a pair of
+    inputs) the destination rows are used for h_v and the graph-size normalisation counts destination nodes (upstream takes
+    homogeneous graphs only); ties of max / min route their gradient to the first edge in storage order, where the mailbox's
+    torch.max picks an index of its own."""
+
+    AGGREGATORS = ("sum", "mean", "max", "min", "var", "std")
+    SCALERS = ("identity", "amplification", "attenuation")
+
+    def __init__(self, in_size, out_size, aggregators, scalers, delta, dropout=0., num_towers=1, edge_feat_size=0, residual=True):
+        super(PNAConv, self).__init__()
+        aggregators, scalers = tuple(aggregators), tuple(scalers)
+        if not aggregators or any(a not in self.AGGREGATORS for a in aggregators) or len(set(aggregators)) != len(aggregators):
+            raise DGLError("PNAConv: aggregators must be distinct names out of %s, got %r" % (", ".join(self.AGGREGATORS), aggregators))
+        if not scalers or any(s not in self.SCALERS for s in scalers):
+            raise DGLError("PNAConv: scalers must be names out of %s, got %r" % (", ".join(self.SCALERS), scalers))
+        if in_size % num_towers or out_size % num_towers:
+            raise DGLError("PNAConv: in_size %d and out_size %d must be divisible by num_towers %d" % (in_size, out_size, num_towers))
+        if not float(delta) > 0:
+            raise DGLError("PNAConv: delta must be positive, got %r" % (delta,))
+        self.in_size, self.out_size, self.num_towers = in_size, out_size, num_towers
+        self.tower_in_size, self.tower_out_size = in_size // num_towers, out_size // num_towers
+        self.aggregators, self.scalers, self.delta = aggregators, scalers, float(delta)
+        self.edge_feat_size = edge_feat_size
+        self.residual = residual and in_size == out_size
+        self.towers = nn.ModuleList([PNAConvTower(self.tower_in_size, self.tower_out_size, len(aggregators), len(scalers), dropout,
+                                                  edge_feat_size) for _ in range(num_towers)])
+        self.mixing_layer = nn.Sequential(nn.Linear(out_size, out_size), nn.LeakyReLU())
+
+    def _graph_size_norm(self, graph, n_dst, like):
+        counts = graph.batch_num_nodes() if not getattr(graph, "is_block", False) else None
+        if counts is None or int(counts.shape[0]) == 1:
+            return like.new_full((1, 1), 1.0 / math.sqrt(max(n_dst, 1)))
+        counts = counts.to(like.device)
+        return torch.repeat_interleave(counts.to(like.dtype).rsqrt(), counts, output_size=n_dst).unsqueeze(-1)
+
+    def forward(self, graph, node_feat, edge_feat=None):
+        feat_src, feat_dst = expand_as_pair(node_feat, graph)
+        T, tin = self.num_towers, self.tower_in_size
+        if (edge_feat is not None) != (self.edge_feat_size > 0):
+            raise DGLError("PNAConv: edge_feat is %s but edge_feat_size is %d" % ("given" if edge_feat is not None else "missing", self.edge_feat_size))
+        n_dst = feat_dst.shape[0]
+        a, b = [], []
+        for t, tower in enumerate(self.towers):  # per NODE: the source and destination parts of M
+            Wm = tower.M.weight
+            a.append(F.linear(feat_src[:, t * tin:(t + 1) * tin], Wm[:, :tin]))
+            b.append(F.linear(feat_dst[:, t * tin:(t + 1) * tin], Wm[:, tin:2 * tin], tower.M.bias))
+        a, b = (torch.cat(p, dim=1) if T > 1 else p[0] for p in (a, b))
+        c = None
+        if edge_feat is not None:                # per edge: one [E, in_size] product for all towers
+            c = F.linear(edge_feat, torch.cat([tower.M.weight[:, 2 * tin:] for tower in self.towers], dim=0))
+        agg = ops.multi_aggregate(graph, a, self.aggregators, w=c)   # [n_dst, A, in_size]
+        deg = graph.in_degrees().to(agg.dtype).view(-1, 1)
+        some = (deg > 0).to(agg.dtype)
+        shift = {"mean": some, "max": some, "min": some, "sum": deg}  # what b_v adds: nothing to var / std, nothing without in-edges
+        agg = agg + torch.stack([b * shift[n] if n in shift else torch.zeros_like(b) for n in self.aggregators], dim=1)
+        logd = torch.log(deg + 1)
+        scale = {"identity": None, "amplification": logd / self.delta,
+                 "attenuation": torch.where(deg > 0, self.delta / logd.clamp(min=1e-30), torch.zeros_like(logd))}
+        snorm = self._graph_size_norm(graph, n_dst, agg)
+        outs = []
+        for t, tower in enumerate(self.towers):
+            h = agg[:, :, t * tin:(t + 1) * tin].reshape(n_dst, -1)
+            h = torch.cat([h if scale[s] is None else h * scale[s] for s in self.scalers], dim=1)
+            h = tower.U(torch.cat([feat_dst[:, t * tin:(t + 1) * tin], h], dim=1)) * snorm
+            outs.append(tower.dropout(tower.batchnorm(h)))
+        h_out = self.mixing_layer(torch.cat(outs, dim=1) if T > 1 else outs[0])
+        if self.residual:
+            h_out = h_out + feat_dst
+        return h_out
 
 
 def _hetero_aggregate(name):

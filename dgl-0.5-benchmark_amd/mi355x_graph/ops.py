@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -579,6 +579,157 @@ def gine_sum(graph, x, w, scale=None):
             m = m * scale.unsqueeze(-1)
         return gspmm(gidx, "copy_rhs", "sum", None, m)
     return GineSum.apply(gidx, x, w, scale)
+
+
+class MultiAggregate(torch.autograd.Function):
+    """out[v, a, :] = aggregate a of the messages m_e = x[u] (+ w[e]) into v, a in sum | mean | var | std | max | min, all from ONE walk of
+    the in-CSR; the backward forms the per-destination rows A, B (N-sized) and returns d x and d w from ONE walk of the out-CSR
+    (csrc/multiagg.hip).  Saves x, w, the int32 args of max / min and the [N_dst, 2, D] (mean, var) statistics (save_for_backward: a later in-place
+    write to any of them is caught); nothing of size E."""
+
+    @staticmethod
+    def forward(ctx, gidx, x, w, aggregators, eps):
+        x = x.contiguous()
+        w = None if w is None else w.contiguous()
+        out, arg_max, arg_min, stats = sparse.backend_for(x).multi_agg_fwd(gidx.csc(), x, w, aggregators, eps)
+        ctx.gidx, ctx.aggregators, ctx.eps = gidx, aggregators, eps
+        ctx.save_for_backward(x, w, arg_max, arg_min, stats)  # the args and (mean, var) of this call: absent ones are None
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        x, w, arg_max, arg_min, stats = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[1], w is not None and ctx.needs_input_grad[2]
+        if not (need_x or need_w):
+            return None, None, None, None, None
+        g = {name: d_out[:, i, :] for i, name in enumerate(ctx.aggregators)}
+        deg = ctx.gidx.in_degrees().to(torch.float32).clamp(min=1).unsqueeze(-1)   # rows without in-edges are met by no edge
+        A = g["sum"] if "sum" in g else None
+        if "mean" in g:
+            A = g["mean"] / deg if A is None else A + g["mean"] / deg
+        B = None
+        if stats is not None:                                                          # the mask var > 0 from the forward's stored bits
+            mean, var = stats[:, 0, :], stats[:, 1, :]
+            gv = g["var"] if "var" in g else None
+            if "std" in g:
+                gs = g["std"] / (2 * torch.sqrt(var + ctx.eps))
+                gv = gs if gv is None else gv + gs
+            B = (2 * torch.where(var > 0, gv, torch.zeros_like(gv)) / deg).contiguous()
+            A = -(B * mean) if A is None else A - B * mean
+        A = x.new_zeros(d_out.shape[0], d_out.shape[2]) if A is None else A.contiguous()
+        g_max = g["max"].contiguous() if "max" in g else None
+        g_min = g["min"].contiguous() if "min" in g else None
+        d_x, d_w = sparse.backend_for(x).multi_agg_bwd(ctx.gidx.csr(), x, w, A, B, g_max, arg_max, g_min, arg_min, need_x, need_w)
+        return None, d_x, d_w, None, None
+
+
+MULTI_AGGREGATORS = ("sum", "mean", "max", "min", "var", "std")
+
+
+def _multi_agg_args(graph, x, aggregators, w, eps):
+    """(graph index, aggregators as a tuple, eps as a float) of a multi_aggregate call, or DGLError."""
+    gidx = _gidx(graph)
+    if not (torch.is_tensor(x) and x.dim() == 2 and (w is None or (torch.is_tensor(w) and w.dim() == 2))):
+        raise DGLError("multi_aggregate: expected x [N_src, D] and w [E, D] or None, got %s"
+                       % (", ".join(str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__ for t in (x, w)),))
+    if x.dtype != torch.float32 or (w is not None and w.dtype != torch.float32):
+        raise DGLError("multi_aggregate expects float32 inputs, got %s%s" % (x.dtype, "" if w is None else " / %s" % (w.dtype,)))
+    E = gidx.num_edges()
+    if x.shape[0] != gidx.num_src or (w is not None and (w.shape[0] != E or w.shape[1] != x.shape[1])):
+        raise DGLError("multi_aggregate: expected x [%d, D] and w [%d, D], got x %s, w %s"
+                       % (gidx.num_src, E, tuple(x.shape), None if w is None else tuple(w.shape)))
+    if isinstance(aggregators, str) or not hasattr(aggregators, "__iter__"):
+        raise DGLError("multi_aggregate: aggregators must be a sequence of names, got %r" % (aggregators,))
+    aggregators = tuple(aggregators)
+    if not aggregators:
+        raise DGLError("multi_aggregate: aggregators is empty")
+    for name in aggregators:
+        if name not in MULTI_AGGREGATORS:
+            raise DGLError("multi_aggregate: unknown aggregator %r (one of %s)" % (name, ", ".join(MULTI_AGGREGATORS)))
+    if len(set(aggregators)) != len(aggregators):
+        raise DGLError("multi_aggregate: repeated aggregator in %r" % (aggregators,))
+    try:
+        eps = float(eps)
+    except (TypeError, ValueError):
+        raise DGLError("multi_aggregate: eps must be a number, got %r" % (eps,))
+    if not (eps > 0 and eps != float("inf")):
+        raise DGLError("multi_aggregate: eps must be positive and finite, got %r" % (eps,))
+    return gidx, aggregators, eps
+
+
+def multi_aggregate_fused(graph, x, aggregators=("mean", "max", "min", "std"), w=None, eps=1e-30):
+    """True when multi_aggregate(graph, x, aggregators, w, eps) runs the fused kernels (else it is one gspmm per aggregate): device
+    operands in the kernels' supported set, the switch on, and not the one case the composition was measured to win -- a single
+    sum or mean without w, or a single max or min without w on a small batch (config.MULTI_AGG_SINGLE_*)."""
+    gidx = _gidx(graph)
+    if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == x.device for t in (x,) + (() if w is None else (w,)))
+            or x.dim() != 2 or (w is not None and w.dim() != 2) or not config.MULTI_AGG_FUSED or _torch_ops() is not None
+            or x.device.type not in sparse._BACKENDS):
+        return False
+    be = sparse.backend_for(x)
+    E = gidx.num_edges()
+    if (not hasattr(be, "multi_agg_fwd") or not hasattr(be, "multi_agg_bwd") or x.shape[0] != gidx.num_src
+            or (w is not None and tuple(w.shape) != (E, x.shape[1])) or E == 0):
+        return False
+    # the kernels read 16 bytes per lane: a contiguous view at an odd storage offset is not theirs (a strided one is copied, and a
+    # fresh allocation is aligned)
+    if any(t.is_contiguous() and t.data_ptr() % 16 for t in (x,) + (() if w is None else (w,))):
+        return False
+    # one plain aggregate without w composes to a single g-SpMM; below the measured crossover that one wins (config.py, docs/LOG_pna.md)
+    aggregators = tuple(aggregators)
+    if w is None and len(aggregators) == 1:
+        if aggregators[0] in ("sum", "mean") and not config.MULTI_AGG_SINGLE_SUM_FUSED:
+            return False
+        if aggregators[0] in ("max", "min") and x.shape[1] <= config.MULTI_AGG_SINGLE_MAX_D and E < config.MULTI_AGG_SINGLE_MIN_EDGES:
+            return False
+    return be.multi_agg_supported(gidx.csc(), int(x.shape[1]))
+
+
+def _multi_aggregate_composed(gidx, x, aggregators, w, eps):
+    """The same values through the existing operators: one g-SpMM per aggregate (two for var / std), over the [E, D] messages
+    gsddmm(copy_lhs) + w when the edges carry features."""
+    if w is None:
+        def reduce(r, square=False):
+            return gspmm(gidx, "copy_lhs", r, x * x if square else x, None)
+    else:
+        m = gsddmm(gidx, "copy_lhs", x, None, "u", "v") + w
+
+        def reduce(r, square=False):
+            return gspmm(gidx, "copy_rhs", r, None, m * m if square else m)
+    got = {}
+    if "var" in aggregators or "std" in aggregators:
+        got["mean"] = reduce("mean")
+        got["var"] = torch.relu(reduce("mean", True) - got["mean"] * got["mean"])
+        if "std" in aggregators:
+            some = (gidx.in_degrees() > 0).unsqueeze(-1)
+            got["std"] = torch.where(some, torch.sqrt(got["var"] + eps), torch.zeros_like(got["var"]))   # a row without in-edges: 0
+    for name in aggregators:
+        if name not in got:
+            got[name] = reduce(name)
+    return torch.stack([got[name] for name in aggregators], dim=1)
+
+
+def multi_aggregate(graph, x, aggregators, w=None, eps=1e-30):
+    """Several aggregates of the same messages at once (Principal Neighbourhood Aggregation): with m_e = x[u,:] (+ w[e,:], w by edge id)
+    and d the in-degree of v,
+
+        sum = S1 = sum_e m_e,  mean = S1 / d,  var = relu(sum_e m_e^2 / d - mean^2),  std = sqrt(var + eps),  max,  min
+
+    returned as [N_dst, A, D] in the order of `aggregators` (a non-empty sequence of distinct names out of sum, mean, max, min, var, std).
+    x: [N_src, D], w: [E, D] | None, fp32.  A destination without in-edges gives 0 in every aggregate, std included.  max / min follow
+    gspmm's rule (the first of equal extrema in storage order takes the whole gradient, a NaN never wins).  Gradients go to x and w.
+    Device operands (16-byte aligned) with D % 4 == 0 and 4 <= D <= 256 on an int32 graph run csrc/multiagg.hip
+    (multi_aggregate_fused): one walk forward, one backward, nothing of size E but d w; everything else -- and a single plain aggregate
+    without w where that one g-SpMM was measured to win (config.MULTI_AGG_SINGLE_*) -- is composed of gspmm
+    (copy_lhs, or copy_rhs over gsddmm(copy_lhs) + w) with a second mean over the squares -- the same values through the existing operators."""
+    gidx, aggregators, eps = _multi_agg_args(graph, x, aggregators, w, eps)
+    if gidx.num_edges() == 0:  # no message: zeros (tied to x and w so that both get a zero gradient), no kernel of this library
+        tie = x[:0].sum() if w is None else x[:0].sum() + w.sum()
+        return x.new_zeros((gidx.num_dst, len(aggregators), x.shape[1])) + tie
+    if not multi_aggregate_fused(gidx, x, aggregators, w, eps):
+        return _multi_aggregate_composed(gidx, x, aggregators, w, eps)
+    return MultiAggregate.apply(gidx, x, w, aggregators, eps)
 
 
 class HeadDot(torch.autograd.Function):

@@ -1059,6 +1059,51 @@ class HipBackend(object):
                                                _ptr(d_out2d), _ptr(d_x), _ptr(d_w), _ptr(ws), _stream(dev)))
         return d_x, d_w
 
+    # ---- sum / mean / var / std / max / min of the same messages in one walk (csrc/multiagg.hip)
+    @staticmethod
+    def multi_agg_supported(csr, D):
+        """Shapes mgx_multi_agg_* takes: those of gine_supported."""
+        return bool(_lib.lib().mgx_multi_agg_supported(ctypes.byref(csr.c_struct()), D))
+
+    def _multi_agg_ws(self, plan, D, dev):
+        need = _lib.lib().mgx_multi_agg_workspace(self._plan_ptr(plan), D)
+        return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+
+    def multi_agg_fwd(self, csc, x2d, w2d, aggregators, eps):
+        """x2d [n_src, D], w2d [E, D] by edge id | None (contiguous) -> (out [n_dst, A, D] in the order of `aggregators`,
+        arg_max | None, arg_min | None (int32 [n_dst, D], edge ids), stats [n_dst, 2, D] = (mean, var) | None)."""
+        dev = self._check_dev(csc.indptr, x2d, w2d)
+        D, A = int(x2d.shape[1]), len(aggregators)
+        out = torch.empty((csc.num_rows, A, D), dtype=torch.float32, device=dev)
+        block = {name: ctypes.c_void_p(out.data_ptr() + i * D * 4) for i, name in enumerate(aggregators)}
+        arg_max = torch.empty((csc.num_rows, D), dtype=torch.int32, device=dev) if "max" in block else None
+        arg_min = torch.empty((csc.num_rows, D), dtype=torch.int32, device=dev) if "min" in block else None
+        stats = torch.empty((csc.num_rows, 2, D), dtype=torch.float32, device=dev) if ("var" in block or "std" in block) else None
+        plan = csc.plan()
+        ws = self._multi_agg_ws(plan, D, dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="multi_agg_fwd", D=D, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
+            _lib.check(_lib.lib().mgx_multi_agg_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), D, _ptr(x2d), _ptr(w2d),
+                                                    ctypes.c_float(eps), *[block.get(n) for n in ("sum", "mean", "var", "std", "max", "min")],
+                                                    A * D, _ptr(arg_max), _ptr(arg_min), _ptr(stats), _ptr(ws), _stream(dev)))
+        return out, arg_max, arg_min, stats
+
+    def multi_agg_bwd(self, csr, x2d, w2d, A2d, B2d, g_max, arg_max, g_min, arg_min, need_x, need_w):
+        """csr: the out-CSR (rows = sources); A2d, B2d | None, g_max / g_min | None [n_dst, D] dense with their int32 args
+        -> (d_x [n_src, D] | None, d_w [E, D] by edge id | None)."""
+        dev = self._check_dev(csr.indptr, x2d, w2d, A2d, B2d, g_max, arg_max, g_min, arg_min)
+        D = int(x2d.shape[1])
+        if not (need_x or need_w):
+            return None, None
+        d_x = torch.empty((csr.num_rows, D), dtype=torch.float32, device=dev) if need_x else None
+        d_w = torch.empty((csr.nnz, D), dtype=torch.float32, device=dev) if need_w else None
+        plan = csr.plan()
+        ws = self._gine_ws(plan, D, dev) if need_x else None   # [slots, D] partial rows of d x
+        with torch.cuda.device(dev), timed_call(dev, kernel="multi_agg_bwd", D=D, nnz=csr.nnz, n_src=csr.num_rows, n_dst=csr.num_cols):
+            _lib.check(_lib.lib().mgx_multi_agg_bwd(ctypes.byref(csr.c_struct()), self._plan_ptr(plan), D, _ptr(x2d), _ptr(w2d), _ptr(A2d),
+                                                    _ptr(B2d), _ptr(g_max), _ptr(arg_max), _ptr(g_min), _ptr(arg_min), _ptr(d_x), _ptr(d_w),
+                                                    _ptr(ws), _stream(dev)))
+        return d_x, d_w
+
     @staticmethod
     def head_dot_supported(H, F):
         return H * F <= 256 and (F <= 64 or F in (128, 256))

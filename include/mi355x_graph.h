@@ -529,6 +529,52 @@ int32_t mgx_gine_bwd(const mgx_csr* csr /* transpose: rows = sources */, const m
                      const float* x, const float* w, const float* scale, const float* d_out /* [csr->num_cols, D] */,
                      float* d_x /* or NULL */, float* d_w /* or NULL */, void* workspace, void* stream);
 
+/* Several aggregates of the SAME messages in one walk (Principal Neighbourhood Aggregation, upstream's dgl.nn.PNAConv: the mailbox
+ * UDF that takes mean, max, min and std of one message per edge; csrc/multiagg.hip):
+ *   m_e = x[u(e),:] + w[e,:]  (w by EDGE ID as in mgx_gine_*: position p reads w[eid(p)]; w NULL: m_e = x[u(e),:]),  d = in-degree of v
+ *   S1 = sum_e m_e,  S2 = sum_e m_e^2;   sum = S1,  mean = S1 / d,  msq = S2 / d,
+ *   var = relu(msq - mean * mean) (a NaN stays a NaN),  std = sqrt(var + eps)
+ *   max, min, arg_max, arg_min: exactly mgx_spmm_csr's MAX / MIN rule above -- storage order, strict compare from -inf / +inf, the first
+ *   of equal extrema wins, a NaN never wins, a row that never beats the identity gives the identity with arg -1; the arg is the EDGE ID
+ *   of the winner, int32.  A destination with d == 0 gives 0 in every aggregate, std included, with arg -1.
+ *   fwd: ONE walk of the in-CSR `csc`.  One pointer per aggregate, NULL = not wanted (at least one is); each names a [num_rows, D] block
+ *        whose rows are out_ld floats apart (out_ld % 4 == 0, >= D), so the aggregates can land in one [num_rows, A, D] tensor.
+ *        arg_max / arg_min: [num_rows, D] int32, dense, optional, only with their aggregate.  When o_var or o_std is given, `stats`
+ *        [num_rows, 2, D] receives (mean, var) for the backward and eps must be positive and finite; the backward mask 1[var > 0] is
+ *        read from these stored bits, never recomputed.  Lane groups of a wave take interleaved edges and are merged on (value, CSR
+ *        position): the larger (smaller) value, on equal values the smaller position, which is the storage-order rule; the chunks of a
+ *        split row are merged in slot order by the same compare.
+ *   bwd: ONE walk of the transpose `csr` (rows = source nodes, its eids the same edge ids), where every edge is met exactly once.
+ *        The caller forms the per-destination rows (N-sized, elementwise) from the upstream gradients and `stats`:
+ *          gv = (g_var + g_std / (2 std)) * 1[var > 0],   A = g_sum + g_mean / d - 2 gv mean / d,   B = 2 gv / d
+ *        and the walk computes, per column,
+ *          d m_e = A[v] + B[v] * m_e + g_max[v] * 1[arg_max[v] == e] + g_min[v] * 1[arg_min[v] == e]
+ *          d_w[e,:] = d m_e (written exactly once per edge),   d_x[u,:] = sum_{e: u->...} d m_e (0 for a source without out-edges).
+ *        A is required; B NULL means 0 (m_e is then not formed: x and w are not read); g_max / g_min come with their args or are NULL.
+ *        The rows are SEPARATE dense [csr->num_cols, D] matrices: one 32-bit byte offset per edge addresses all of them.
+ *        d_x and d_w may each be NULL.
+ * All operands fp32 (args int32), 16-byte aligned, allocated by the caller.
+ * Supported (mgx_multi_agg_supported), the set of mgx_gine_supported: D % 4 == 0 and 4 <= D <= 256, 32-bit indices, nnz > 0, and
+ * max(num_rows, num_cols, nnz) * D * 4 below 4 GiB (every gathered matrix is addressed by 32-bit byte offsets).
+ * Errors: a D that is not a positive multiple of 4, NULL or misaligned operands, a bad out_ld or eps and a malformed plan are
+ * MGX_ERR_INVALID_ARGUMENT; D > 256, 64-bit indices, nnz == 0 and operands of 4 GiB are MGX_ERR_UNSUPPORTED (the caller composes
+ * mgx_spmm_csr and mgx_sddmm_*).  The argument checks of the graph, D and the plan come before the supported-set checks.
+ * plan: the CSR's mgx_spmm_plan or NULL; workspace: mgx_multi_agg_workspace(plan, D) bytes -- [slots, 6, D] (S1, S2, max, its
+ * position, min, its position) forward, [slots, D] of it backward (needed only for d_x); NULL when the plan splits no row.
+ * Nothing is read back to the host: every entry point can be captured in a graph.
+ * mgx_last_spmm_kernel(): "multi_agg_fwd" / "multi_agg_bwd" after the respective launch.
+ * Deterministic: no atomics, lane groups merged in a fixed order, hub chunks in slot order.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_multi_agg_supported(const mgx_csr* csr, int64_t D);
+int64_t mgx_multi_agg_workspace(const mgx_spmm_plan* plan /* may be NULL */, int64_t D);
+int32_t mgx_multi_agg_fwd(const mgx_csr* csc, const mgx_spmm_plan* plan /* may be NULL */, int64_t D, const float* x /* [num_cols, D] */,
+                          const float* w /* [nnz, D] by edge id, or NULL */, float eps, float* o_sum, float* o_mean, float* o_var,
+                          float* o_std, float* o_max, float* o_min, int64_t out_ld, int32_t* arg_max, int32_t* arg_min,
+                          float* stats /* [num_rows, 2, D] with o_var / o_std */, void* workspace, void* stream);
+int32_t mgx_multi_agg_bwd(const mgx_csr* csr /* transpose: rows = sources */, const mgx_spmm_plan* plan /* may be NULL */, int64_t D,
+                          const float* x, const float* w /* or NULL */, const float* A, const float* B /* or NULL */,
+                          const float* g_max, const int32_t* arg_max, const float* g_min, const int32_t* arg_min,
+                          float* d_x /* or NULL */, float* d_w /* or NULL */, void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ GAT attention terms
  * el[n,h] = sum_f feat[n,h,f] * attn[h,f] -- GATConv's `(feat * attn_l).sum(-1)` (main_dgl_reddit_gat.py:10, UPSTREAM
  * dgl.nn.pytorch.GATConv.forward), one pass; attn_b/out_b (may be NULL) apply a second attention vector to the same
