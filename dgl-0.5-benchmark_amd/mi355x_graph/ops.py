@@ -457,12 +457,9 @@ class DotAttention(torch.autograd.Function):
 
 
 def _dot_attention_args(graph, q, k, v):
+    """The graph index of a dot_attention call, or DGLError."""
     gidx = _gidx(graph)
-    if not all(torch.is_tensor(t) and t.dim() == 3 for t in (q, k, v)):
-        raise DGLError("dot_attention: expected q [N_dst, H, F] and k, v [N_src, H, F], got %s"
-                       % (", ".join(str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__ for t in (q, k, v)),))
-    if q.dtype != torch.float32 or k.dtype != torch.float32 or v.dtype != torch.float32:
-        raise DGLError("dot_attention expects float32 inputs, got %s / %s / %s" % (q.dtype, k.dtype, v.dtype))
+    _want_tensor("dot_attention", "q [N_dst, H, F] and k, v [N_src, H, F]", (q, k, v), 3)
     if (q.shape[0] != gidx.num_dst or k.shape[0] != gidx.num_src or v.shape[0] != gidx.num_src or q.shape[1:] != k.shape[1:]
             or k.shape[1:] != v.shape[1:]):
         raise DGLError("dot_attention: expected q [%d, H, F] and k, v [%d, H, F], got q %s, k %s, v %s"
@@ -470,17 +467,19 @@ def _dot_attention_args(graph, q, k, v):
     return gidx
 
 
+def _dot_attention_kernel_ok(gidx, q, k, v):
+    if (not _device_kernels(q, config.DOT_ATTENTION_FUSED, "dot_attention_fwd") or k.device != q.device or v.device != q.device
+            or gidx.num_edges() == 0):
+        return False
+    return sparse.backend_for(q).dot_attention_supported(gidx.csc(), int(q.shape[1]), int(q.shape[2]))
+
+
 def dot_attention_fused(graph, q, k, v):
     """True when dot_attention(graph, q, k, v) runs the fused kernels (else it is u_dot_v -> edge_softmax -> u_mul_e/sum)."""
-    gidx = _gidx(graph)
-    if (not all(torch.is_tensor(t) and t.dim() == 3 and t.is_cuda and t.dtype == torch.float32 and t.device == q.device for t in (q, k, v))
-            or not config.DOT_ATTENTION_FUSED or _torch_ops() is not None or q.device.type not in sparse._BACKENDS):
+    try:
+        return _dot_attention_kernel_ok(_dot_attention_args(graph, q, k, v), q, k, v)
+    except DGLError:
         return False
-    be = sparse.backend_for(q)
-    if (not hasattr(be, "dot_attention_fwd") or q.shape[0] != gidx.num_dst or k.shape[0] != gidx.num_src or k.shape != v.shape
-            or q.shape[1:] != k.shape[1:] or gidx.num_edges() == 0):
-        return False
-    return be.dot_attention_supported(gidx.csc(), int(q.shape[1]), int(q.shape[2]))
 
 
 def dot_attention(graph, q, k, v, scale=None):
@@ -492,7 +491,7 @@ def dot_attention(graph, q, k, v, scale=None):
     gspmm(g, "mul", "sum", v, edge_softmax(g, gsddmm(g, "dot", k, q, "u", "v") * scale)) -- the same values through the existing operators."""
     gidx = _dot_attention_args(graph, q, k, v)
     scale = float(q.shape[2]) ** -0.5 if scale is None else float(scale)
-    if not dot_attention_fused(graph, q, k, v):
+    if not _dot_attention_kernel_ok(gidx, q, k, v):
         return gspmm(gidx, "mul", "sum", v, edge_softmax(gidx, gsddmm(gidx, "dot", k, q, "u", "v") * scale))
     return DotAttention.apply(gidx, q, k, v, scale)
 
@@ -524,12 +523,7 @@ class GineSum(torch.autograd.Function):
 def _gine_args(graph, x, w, scale):
     """(graph index, scale as [E] or None) of a gine_sum call, or DGLError."""
     gidx = _gidx(graph)
-    if not (torch.is_tensor(x) and torch.is_tensor(w) and x.dim() == 2 and w.dim() == 2):
-        raise DGLError("gine_sum: expected x [N_src, D] and w [E, D], got %s"
-                       % (", ".join(str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__ for t in (x, w)),))
-    if x.dtype != torch.float32 or w.dtype != torch.float32 or (scale is not None and torch.is_tensor(scale) and scale.dtype != torch.float32):
-        raise DGLError("gine_sum expects float32 inputs, got %s / %s%s"
-                       % (x.dtype, w.dtype, "" if scale is None else " / %s" % (scale.dtype,)))
+    _want_tensor("gine_sum", "x [N_src, D] and w [E, D]", (x, w), 2)
     E = gidx.num_edges()
     if x.shape[0] != gidx.num_src or w.shape[0] != E or w.shape[1] != x.shape[1]:
         raise DGLError("gine_sum: expected x [%d, D] and w [%d, D], got x %s, w %s" % (gidx.num_src, E, tuple(x.shape), tuple(w.shape)))
@@ -537,29 +531,28 @@ def _gine_args(graph, x, w, scale):
         if not torch.is_tensor(scale) or tuple(scale.shape) not in ((E,), (E, 1)):
             raise DGLError("gine_sum: expected scale [%d] or [%d, 1], got %s"
                            % (E, E, tuple(scale.shape) if torch.is_tensor(scale) else type(scale).__name__))
+        if scale.dtype != torch.float32:
+            raise DGLError("gine_sum expects float32 inputs, got %s / %s / %s" % (x.dtype, w.dtype, scale.dtype))
         if scale.requires_grad:
             raise DGLError("gine_sum: scale gets no gradient; pass it detached")
         scale = scale.reshape(E)
     return gidx, scale
 
 
+def _gine_kernel_ok(gidx, x, w, scale):
+    if (not _device_kernels(x, config.GINE_FUSED, "gine_fwd", "gine_bwd") or w.device != x.device
+            or (scale is not None and scale.device != x.device) or gidx.num_edges() == 0 or not _aligned16(x, w)):
+        return False
+    return sparse.backend_for(x).gine_supported(gidx.csc(), int(x.shape[1]))
+
+
 def gine_sum_fused(graph, x, w, scale=None):
     """True when gine_sum(graph, x, w, scale) runs the fused kernels (else it is gather -> add -> relu -> mul -> copy_e/sum)."""
-    gidx = _gidx(graph)
-    if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == x.device
-                for t in (x, w) + (() if scale is None else (scale,)))
-            or x.dim() != 2 or w.dim() != 2 or not config.GINE_FUSED or _torch_ops() is not None or x.device.type not in sparse._BACKENDS):
+    try:
+        gidx, scale = _gine_args(graph, x, w, scale)
+        return _gine_kernel_ok(gidx, x, w, scale)
+    except DGLError:
         return False
-    be = sparse.backend_for(x)
-    E = gidx.num_edges()
-    if (not hasattr(be, "gine_fwd") or not hasattr(be, "gine_bwd") or x.shape[0] != gidx.num_src or tuple(w.shape) != (E, x.shape[1])
-            or (scale is not None and scale.numel() != E) or E == 0):
-        return False
-    # the kernels read 16 bytes per lane: a contiguous view at an odd storage offset is not theirs (a strided one is copied, and a
-    # fresh allocation is aligned)
-    if any(t.is_contiguous() and t.data_ptr() % 16 for t in (x, w)):
-        return False
-    return be.gine_supported(gidx.csc(), int(x.shape[1]))
 
 
 def gine_sum(graph, x, w, scale=None):
@@ -571,9 +564,9 @@ def gine_sum(graph, x, w, scale=None):
     gspmm(g, "copy_rhs", "sum", None, relu(gsddmm(g, "copy_lhs", x, None, "u", "v") + w) * scale) -- the same values through the existing
     operators."""
     gidx, scale = _gine_args(graph, x, w, scale)
-    if gidx.num_edges() == 0:  # no message: zeros (tied to x and w so that both get a zero gradient), no kernel of this library
-        return x.new_zeros((gidx.num_dst, x.shape[1])) + (x[:0].sum() + w.sum())
-    if not gine_sum_fused(gidx, x, w, scale):
+    if gidx.num_edges() == 0:
+        return _no_edges_zeros((gidx.num_dst, x.shape[1]), x, w)
+    if not _gine_kernel_ok(gidx, x, w, scale):
         m = torch.relu(gsddmm(gidx, "copy_lhs", x, None, "u", "v") + w)
         if scale is not None:
             m = m * scale.unsqueeze(-1)
@@ -630,11 +623,7 @@ MULTI_AGGREGATORS = ("sum", "mean", "max", "min", "var", "std")
 def _multi_agg_args(graph, x, aggregators, w, eps):
     """(graph index, aggregators as a tuple, eps as a float) of a multi_aggregate call, or DGLError."""
     gidx = _gidx(graph)
-    if not (torch.is_tensor(x) and x.dim() == 2 and (w is None or (torch.is_tensor(w) and w.dim() == 2))):
-        raise DGLError("multi_aggregate: expected x [N_src, D] and w [E, D] or None, got %s"
-                       % (", ".join(str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__ for t in (x, w)),))
-    if x.dtype != torch.float32 or (w is not None and w.dtype != torch.float32):
-        raise DGLError("multi_aggregate expects float32 inputs, got %s%s" % (x.dtype, "" if w is None else " / %s" % (w.dtype,)))
+    _want_tensor("multi_aggregate", "x [N_src, D] and w [E, D] or None", (x,) if w is None else (x, w), 2)
     E = gidx.num_edges()
     if x.shape[0] != gidx.num_src or (w is not None and (w.shape[0] != E or w.shape[1] != x.shape[1])):
         raise DGLError("multi_aggregate: expected x [%d, D] and w [%d, D], got x %s, w %s"
@@ -658,32 +647,29 @@ def _multi_agg_args(graph, x, aggregators, w, eps):
     return gidx, aggregators, eps
 
 
-def multi_aggregate_fused(graph, x, aggregators=("mean", "max", "min", "std"), w=None, eps=1e-30):
-    """True when multi_aggregate(graph, x, aggregators, w, eps) runs the fused kernels (else it is one gspmm per aggregate): device
-    operands in the kernels' supported set, the switch on, and not the one case the composition was measured to win -- a single
+def _multi_agg_kernel_ok(gidx, x, aggregators, w):
+    """Device operands in the kernels' supported set, the switch on, and not the one case the composition was measured to win -- a single
     sum or mean without w, or a single max or min without w on a small batch (config.MULTI_AGG_SINGLE_*)."""
-    gidx = _gidx(graph)
-    if (not all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.device == x.device for t in (x,) + (() if w is None else (w,)))
-            or x.dim() != 2 or (w is not None and w.dim() != 2) or not config.MULTI_AGG_FUSED or _torch_ops() is not None
-            or x.device.type not in sparse._BACKENDS):
-        return False
-    be = sparse.backend_for(x)
     E = gidx.num_edges()
-    if (not hasattr(be, "multi_agg_fwd") or not hasattr(be, "multi_agg_bwd") or x.shape[0] != gidx.num_src
-            or (w is not None and tuple(w.shape) != (E, x.shape[1])) or E == 0):
-        return False
-    # the kernels read 16 bytes per lane: a contiguous view at an odd storage offset is not theirs (a strided one is copied, and a
-    # fresh allocation is aligned)
-    if any(t.is_contiguous() and t.data_ptr() % 16 for t in (x,) + (() if w is None else (w,))):
+    if (not _device_kernels(x, config.MULTI_AGG_FUSED, "multi_agg_fwd", "multi_agg_bwd") or (w is not None and w.device != x.device)
+            or E == 0 or not _aligned16(x, w)):
         return False
     # one plain aggregate without w composes to a single g-SpMM; below the measured crossover that one wins (config.py, docs/LOG_pna.md)
-    aggregators = tuple(aggregators)
     if w is None and len(aggregators) == 1:
         if aggregators[0] in ("sum", "mean") and not config.MULTI_AGG_SINGLE_SUM_FUSED:
             return False
         if aggregators[0] in ("max", "min") and x.shape[1] <= config.MULTI_AGG_SINGLE_MAX_D and E < config.MULTI_AGG_SINGLE_MIN_EDGES:
             return False
-    return be.multi_agg_supported(gidx.csc(), int(x.shape[1]))
+    return sparse.backend_for(x).multi_agg_supported(gidx.csc(), int(x.shape[1]))
+
+
+def multi_aggregate_fused(graph, x, aggregators=("mean", "max", "min", "std"), w=None, eps=1e-30):
+    """True when multi_aggregate(graph, x, aggregators, w, eps) runs the fused kernels (else it is one gspmm per aggregate)."""
+    try:
+        gidx, aggregators, _ = _multi_agg_args(graph, x, aggregators, w, eps)
+        return _multi_agg_kernel_ok(gidx, x, aggregators, w)
+    except DGLError:
+        return False
 
 
 def _multi_aggregate_composed(gidx, x, aggregators, w, eps):
@@ -724,10 +710,9 @@ def multi_aggregate(graph, x, aggregators, w=None, eps=1e-30):
     without w where that one g-SpMM was measured to win (config.MULTI_AGG_SINGLE_*) -- is composed of gspmm
     (copy_lhs, or copy_rhs over gsddmm(copy_lhs) + w) with a second mean over the squares -- the same values through the existing operators."""
     gidx, aggregators, eps = _multi_agg_args(graph, x, aggregators, w, eps)
-    if gidx.num_edges() == 0:  # no message: zeros (tied to x and w so that both get a zero gradient), no kernel of this library
-        tie = x[:0].sum() if w is None else x[:0].sum() + w.sum()
-        return x.new_zeros((gidx.num_dst, len(aggregators), x.shape[1])) + tie
-    if not multi_aggregate_fused(gidx, x, aggregators, w, eps):
+    if gidx.num_edges() == 0:
+        return _no_edges_zeros((gidx.num_dst, len(aggregators), x.shape[1]), x, w)
+    if not _multi_agg_kernel_ok(gidx, x, aggregators, w):
         return _multi_aggregate_composed(gidx, x, aggregators, w, eps)
     return MultiAggregate.apply(gidx, x, w, aggregators, eps)
 
@@ -1962,21 +1947,74 @@ def _offsets_of(seglen, device):
     return offsets
 
 
-def _segment_offsets(seglen, value, total, who):
-    """(offsets on value's device, number of rows): as segment_reduce builds them -- a cumsum on the device, the row count from the caller
-    or from host lengths, read back once otherwise."""
+def _want_seglen(who, seglen, value, total):
+    """seglen is a 1-D tensor and `total`, where it is known, is value's row count, or DGLError: the part that reads no tensor value."""
     if not torch.is_tensor(seglen) or seglen.dim() != 1:
         raise DGLError("%s: seglen must be a 1-D tensor of segment lengths" % who)
-    if total is None:
-        total = int(seglen.sum())
-    if int(total) != value.shape[0]:
+    if total is not None and int(total) != value.shape[0]:
         raise DGLError("%s: segment lengths sum to %d, value has %d rows" % (who, total, value.shape[0]))
-    return _offsets_of(seglen, value.device), int(total)
 
 
-def _readout_kernels(t):
-    """The backend of `t` has csrc/segattn.hip (device tensors outside the MGX_TORCH_OPS=1 test mode); CPU backends compose."""
-    return t.is_cuda and _torch_ops() is None and hasattr(sparse.backend_for(t), "segment_attention_fwd")
+def _segment_offsets(seglen, value, total, who):
+    """(offsets on value's device, number of rows) after _want_seglen: as segment_reduce builds them -- a cumsum on the device, the row
+    count from the caller or from host lengths, read back once otherwise."""
+    if total is None:
+        _want_seglen(who, seglen, value, int(seglen.sum()))
+    return _offsets_of(seglen, value.device), int(value.shape[0])
+
+
+# What the operand checks (_X_args: everything an operator rejects, DGLError) and the kernel predicates (_X_kernel_ok: what sends a valid
+# call to the composed form) of the fused operators share.  X_fused is `_X_args` then `_X_kernel_ok`, False where the operator raises;
+# the checks of a segment operator read no tensor value, so a predicate never waits for the device (its operator builds the offsets after).
+def _want_tensor(who, name, t, dims, dtype=torch.float32):
+    """`t` -- one operand or a tuple of them, named `name` in the message -- are tensors of `dims` dimensions and of `dtype`, or DGLError."""
+    ts, dims = t if type(t) is tuple else (t,), dims if type(dims) is tuple else (dims,)
+    for x in ts:  # (plain loops: this runs in every call of every operator)
+        if not torch.is_tensor(x) or x.dim() not in dims:
+            raise DGLError("%s: expected %s, got %s"
+                           % (who, name, ", ".join(str(tuple(x.shape)) if torch.is_tensor(x) else type(x).__name__ for x in ts)))
+    for x in ts:
+        if x.dtype != dtype:
+            raise DGLError("%s expects %s input%s, got %s"
+                           % (who, str(dtype).replace("torch.", ""), "s" if len(ts) > 1 else "", " / ".join(str(x.dtype) for x in ts)))
+
+
+def _want_count(who, name, k):
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise DGLError("%s: %s must be an integer >= 1, got %r" % (who, name, k))
+
+
+def _want_seglen_device(who, seglen, x):
+    if seglen.device != x.device and seglen.device.type != "cpu":  # host lengths go with any x
+        raise DGLError("%s: operands on different devices: %s vs %s" % (who, x.device, seglen.device))
+
+
+def _row_ld(x):
+    """The row stride of a [N, D] operand as the kernels get it: its own for a row-strided column block, D after a copy."""
+    return int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= x.shape[1] else int(x.shape[1])
+
+
+def _rows_fit(x):
+    return x.shape[0] * _row_ld(x) < 2 ** 30  # 32-bit element indices in the kernels
+
+
+def _aligned16(*tensors):
+    # the kernels read 16 bytes per lane: a contiguous view at an odd storage offset is not theirs (a strided one is copied, and a
+    # fresh allocation is aligned)
+    return not any(t is not None and t.is_contiguous() and t.data_ptr() % 16 for t in tensors)
+
+
+def _device_kernels(t, switch, *methods):
+    """`switch` is on and the backend of device tensor `t` has every wrapper in `methods` (not under MGX_TORCH_OPS=1); CPU backends compose."""
+    if not (switch and _torch_ops() is None and t.is_cuda and t.device.type in sparse._BACKENDS):
+        return False
+    be = sparse.backend_for(t)
+    return all(hasattr(be, m) for m in methods)
+
+
+def _no_edges_zeros(shape, x, w):
+    """No message: zeros, tied to x and w so that both get a zero gradient; no kernel of this library."""
+    return x.new_zeros(shape) + (x[:0].sum() if w is None else x[:0].sum() + w.sum())
 
 
 def segment_softmax(seglen, value, total=None):
@@ -1987,10 +2025,11 @@ def segment_softmax(seglen, value, total=None):
         raise DGLError("segment_softmax: expected a tensor [N, ...], got %s" % (type(value).__name__,))
     if value.dtype != torch.float32:
         raise DGLError("segment_softmax expects float32 input, got %s" % (value.dtype,))
+    _want_seglen("segment_softmax", seglen, value, total)
     offsets, n = _segment_offsets(seglen, value, total, "segment_softmax")
     if value.numel() == 0:
         return value.clone()
-    if _readout_kernels(value):
+    if _device_kernels(value, True, "segment_attention_fwd"):  # csrc/segattn.hip holds both
         return SegmentSoftmax.apply(value, offsets)
     sparse.backend_for(value)  # no CPU backend: DGLError
     return _segment_softmax_composed(offsets, value, n)
@@ -2008,24 +2047,27 @@ def _segment_attention_args(seglen, feat, logits, query, total):
                        % (feat.dtype, other.dtype if torch.is_tensor(other) else type(other).__name__))
     if other.device != feat.device:
         raise DGLError("segment_attention: operands on different devices: %s vs %s" % (feat.device, other.device))
-    offsets, n = _segment_offsets(seglen, feat, total, "segment_attention")
+    _want_seglen("segment_attention", seglen, feat, total)
     N, H, F = feat.shape
     if logits is not None and tuple(logits.shape) != (N, H):
         raise DGLError("segment_attention: expected logits [%d, %d] for feat %s, got %s" % (N, H, tuple(feat.shape), tuple(logits.shape)))
     if query is not None and tuple(query.shape) != (seglen.shape[0], H, F):
         raise DGLError("segment_attention: expected query [%d, %d, %d] for %d segments and feat %s, got %s"
                        % (seglen.shape[0], H, F, seglen.shape[0], tuple(feat.shape), tuple(query.shape)))
-    return offsets, n
+
+
+def _segment_attention_kernel_ok(seglen, feat):
+    return (_device_kernels(feat, config.SEGMENT_ATTENTION_FUSED, "segment_attention_fwd") and feat.shape[0] > 0 and seglen.shape[0] > 0
+            and sparse.backend_for(feat).segment_attention_supported(feat))
 
 
 def segment_attention_fused(seglen, feat, logits=None, query=None, scale=1.0, total=None):
     """True when segment_attention(...) with these operands runs the fused pair of csrc/segattn.hip (else the composition)."""
-    other = logits if logits is not None else query
-    if (not torch.is_tensor(feat) or feat.dim() != 3 or not torch.is_tensor(other) or (logits is None) == (query is None)
-            or feat.dtype != torch.float32 or other.dtype != torch.float32 or other.device != feat.device
-            or not config.SEGMENT_ATTENTION_FUSED or feat.device.type not in sparse._BACKENDS or not _readout_kernels(feat)):
+    try:
+        _segment_attention_args(seglen, feat, logits, query, total)
+        return _segment_attention_kernel_ok(seglen, feat)
+    except DGLError:
         return False
-    return feat.shape[0] > 0 and seglen.shape[0] > 0 and sparse.backend_for(feat).segment_attention_supported(feat)
 
 
 def segment_attention(seglen, feat, logits=None, query=None, scale=1.0, total=None):
@@ -2037,9 +2079,10 @@ def segment_attention(seglen, feat, logits=None, query=None, scale=1.0, total=No
     Device operands with F % 4 == 0, H*F <= 256 and (H == 1 or F in {4, 8, 16, 32, 64}) run csrc/segattn.hip (segment_attention_fused);
     everything else -- CPU tensors under a registered CPU backend, other shapes, config.SEGMENT_ATTENTION_FUSED = False -- is segment
     max -> gather -> exp -> segment sum -> gather -> multiply -> segment sum through segment_reduce and row gathers."""
-    offsets, n = _segment_attention_args(seglen, feat, logits, query, total)
+    _segment_attention_args(seglen, feat, logits, query, total)
+    offsets, n = _segment_offsets(seglen, feat, total, "segment_attention")
     scale = float(scale)
-    if segment_attention_fused(seglen, feat, logits, query, scale, n):
+    if _segment_attention_kernel_ok(seglen, feat):
         return SegmentAttention.apply(feat, logits, query, offsets, scale)
     sparse.backend_for(feat)  # no CPU backend: DGLError
     if feat.shape[0] == 0 or seglen.shape[0] == 0:
@@ -2096,15 +2139,13 @@ def _segment_topk_composed(offsets, feat, k, sortby, descending, n):
 
 
 def _segment_topk_args(seglen, feat, k, sortby, total):
-    if not torch.is_tensor(feat) or feat.dim() not in (1, 2):
-        raise DGLError("segment_topk: expected feat [N] or [N, D], got %s" % (tuple(feat.shape) if torch.is_tensor(feat) else type(feat).__name__,))
-    if feat.dtype != torch.float32:
-        raise DGLError("segment_topk expects float32 input, got %s" % (feat.dtype,))
-    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
-        raise DGLError("segment_topk: k must be an integer >= 1, got %r" % (k,))
-    if torch.is_tensor(seglen) and seglen.device != feat.device and seglen.device.type != "cpu":  # host lengths go with any feat
-        raise DGLError("segment_topk: operands on different devices: %s vs %s" % (feat.device, seglen.device))
+    """(feat as [N, D], sortby as a column >= 0 or None) of a segment_topk call, or DGLError."""
+    who = "segment_topk"
+    _want_tensor(who, "feat [N] or [N, D]", feat, (1, 2))
+    _want_count(who, "k", k)
     feat2d = feat if feat.dim() == 2 else feat.unsqueeze(1)
+    _want_seglen(who, seglen, feat2d, total)
+    _want_seglen_device(who, seglen, feat)
     D = int(feat2d.shape[1])
     if D < 1:
         raise DGLError("segment_topk: feat has no columns")
@@ -2112,20 +2153,22 @@ def _segment_topk_args(seglen, feat, k, sortby, total):
         if isinstance(sortby, bool) or not isinstance(sortby, int) or not -D <= sortby < D:
             raise DGLError("segment_topk: sortby must be None or a column in [%d, %d), got %r" % (-D, D, sortby))
         sortby = sortby % D
-    offsets, n = _segment_offsets(seglen, feat2d, total, "segment_topk")
-    return offsets, n, feat2d, sortby
+    return feat2d, sortby
+
+
+def _segment_topk_kernel_ok(seglen, feat2d, k, sortby):
+    N, D, S = int(feat2d.shape[0]), int(feat2d.shape[1]), int(seglen.shape[0])
+    return (_device_kernels(feat2d, config.SEGMENT_TOPK_FUSED, "segment_topk_fwd") and N > 0 and S > 0 and N < 2 ** 31 and S * k < 2 ** 31
+            and (sortby is not None or S * D < 2 ** 31) and sparse.backend_for(feat2d).segment_topk_supported(k, D, sortby is None))
 
 
 def segment_topk_fused(seglen, feat, k, sortby=None, descending=True, total=None):
     """True when segment_topk(...) with these operands runs csrc/segtopk.hip (else the composition of sorts and gathers)."""
-    if (not torch.is_tensor(feat) or feat.dim() not in (1, 2) or feat.dtype != torch.float32 or not torch.is_tensor(seglen)
-            or (seglen.device != feat.device and seglen.device.type != "cpu") or isinstance(k, bool) or not isinstance(k, int) or k < 1
-            or not config.SEGMENT_TOPK_FUSED or feat.device.type not in sparse._BACKENDS or not _readout_kernels(feat)
-            or not hasattr(sparse.backend_for(feat), "segment_topk_fwd")):
+    try:
+        feat2d, sortby = _segment_topk_args(seglen, feat, k, sortby, total)
+        return _segment_topk_kernel_ok(seglen, feat2d, k, sortby)
+    except DGLError:
         return False
-    D = 1 if feat.dim() == 1 else int(feat.shape[1])
-    return (feat.shape[0] > 0 and seglen.shape[0] > 0 and D >= 1 and feat.shape[0] < 2 ** 31 and seglen.shape[0] * k < 2 ** 31
-            and (sortby is not None or seglen.shape[0] * D < 2 ** 31) and sparse.backend_for(feat).segment_topk_supported(k, D, sortby is None))
 
 
 def segment_topk(seglen, feat, k, sortby=None, descending=True, total=None):
@@ -2142,8 +2185,9 @@ def segment_topk(seglen, feat, k, sortby=None, descending=True, total=None):
     `total`: the row count when the caller knows it (no read-back of device lengths).  Device operands with k <= 1024 run
     csrc/segtopk.hip, one launch each way (segment_topk_fused); everything else -- CPU tensors under a registered CPU backend, larger k,
     config.SEGMENT_TOPK_FUSED = False -- is two stable sorts and gathers in torch operators."""
-    offsets, n, feat2d, sortby = _segment_topk_args(seglen, feat, k, sortby, total)
-    if segment_topk_fused(seglen, feat, k, sortby, descending, n):
+    feat2d, sortby = _segment_topk_args(seglen, feat, k, sortby, total)
+    offsets, n = _segment_offsets(seglen, feat2d, total, "segment_topk")
+    if _segment_topk_kernel_ok(seglen, feat2d, k, sortby):
         return SegmentTopk.apply(feat2d, offsets, k, sortby, bool(descending))
     sparse.backend_for(feat)  # no CPU backend: DGLError
     return _segment_topk_composed(offsets, feat2d, k, sortby, descending, n)
@@ -2181,31 +2225,32 @@ def _segment_knn_composed(offsets, x, k, return_dist):
     return index, dist
 
 
-def _segment_knn_args(seglen, x, k, total):
-    if not torch.is_tensor(x) or x.dim() != 2:
-        raise DGLError("segment_knn: expected x [N, D], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
-    if x.dtype != torch.float32:
-        raise DGLError("segment_knn expects float32 input, got %s" % (x.dtype,))
-    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
-        raise DGLError("segment_knn: k must be an integer >= 1, got %r" % (k,))
-    if torch.is_tensor(seglen) and seglen.device != x.device and seglen.device.type != "cpu":  # host lengths go with any x
-        raise DGLError("segment_knn: operands on different devices: %s vs %s" % (x.device, seglen.device))
+def _segment_rows_args(who, seglen, x, total):
+    """What the point-cloud operators ask of their rows: x [N, D] fp32 with D >= 1 in segments of seglen, or DGLError."""
+    _want_tensor(who, "x [N, D]", x, 2)
+    _want_seglen(who, seglen, x, total)
+    _want_seglen_device(who, seglen, x)
     if x.shape[1] < 1:
-        raise DGLError("segment_knn: x has no columns")
-    return _segment_offsets(seglen, x, total, "segment_knn")
+        raise DGLError("%s: x has no columns" % who)
+
+
+def _segment_knn_args(seglen, x, k, total):
+    _segment_rows_args("segment_knn", seglen, x, total)
+    _want_count("segment_knn", "k", k)
+
+
+def _segment_knn_kernel_ok(seglen, x, k):
+    return (_device_kernels(x, config.KNN_FUSED, "segment_knn") and x.shape[0] > 0 and seglen.shape[0] < 2 ** 31 and _rows_fit(x)
+            and sparse.backend_for(x).segment_knn_supported(k, int(x.shape[1])))
 
 
 def segment_knn_fused(seglen, x, k, total=None, return_dist=False):
     """True when segment_knn(...) with these operands runs csrc/knn.hip (else the composition of distances and a stable sort)."""
-    if (not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not torch.is_tensor(seglen)
-            or (seglen.device != x.device and seglen.device.type != "cpu") or isinstance(k, bool) or not isinstance(k, int) or k < 1
-            or not config.KNN_FUSED or x.device.type not in sparse._BACKENDS or not _readout_kernels(x)
-            or not hasattr(sparse.backend_for(x), "segment_knn")):
+    try:
+        _segment_knn_args(seglen, x, k, total)
+        return _segment_knn_kernel_ok(seglen, x, k)
+    except DGLError:
         return False
-    N, D = int(x.shape[0]), int(x.shape[1])
-    ld = int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= D else D
-    return (N > 0 and D >= 1 and N < 2 ** 31 and seglen.shape[0] < 2 ** 31 and N * ld < 2 ** 30
-            and sparse.backend_for(x).segment_knn_supported(k, D))
 
 
 def segment_knn(seglen, x, k, total=None, return_dist=False):
@@ -2220,8 +2265,9 @@ def segment_knn(seglen, x, k, total=None, return_dist=False):
     `total`: the row count when the caller knows it (no read-back of device lengths).  Device operands with k <= 64 and D <= 256 run
     csrc/knn.hip in one launch that writes no [n, n] matrix (segment_knn_fused); everything else -- CPU tensors under a registered CPU
     backend, larger k or D, config.KNN_FUSED = False -- is a stable sort of the distances per segment in torch operators."""
-    offsets, n = _segment_knn_args(seglen, x, k, total)
-    if segment_knn_fused(seglen, x, k, n, return_dist):
+    _segment_knn_args(seglen, x, k, total)
+    offsets, _ = _segment_offsets(seglen, x, total, "segment_knn")
+    if _segment_knn_kernel_ok(seglen, x, k):
         with torch.no_grad():
             index, dist = sparse.backend_for(x).segment_knn(offsets, x.detach(), k, return_dist)
     else:
@@ -2265,7 +2311,7 @@ def _segment_knn_query_composed(offsets, x, q_offsets, y, k, eps, return_dist, r
 
 def _segment_knn_query_args(ref_seglen, x, query_seglen, y, k, ref_total, query_total, eps):
     who = "segment_knn_query"
-    for name, t in (("x", x), ("y", y)):
+    for name, t in (("x", x), ("y", y)):  # one operand per message, and its name in the dtype one
         if not torch.is_tensor(t) or t.dim() != 2:
             raise DGLError("%s: expected %s [rows, D], got %s" % (who, name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__,))
         if t.dtype != torch.float32:
@@ -2274,37 +2320,29 @@ def _segment_knn_query_args(ref_seglen, x, query_seglen, y, k, ref_total, query_
         raise DGLError("%s: operands on different devices: %s vs %s" % (who, x.device, y.device))
     if x.shape[1] != y.shape[1] or x.shape[1] < 1:
         raise DGLError("%s: x and y need the same number of columns, at least one (got %d and %d)" % (who, x.shape[1], y.shape[1]))
-    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
-        raise DGLError("%s: k must be an integer >= 1, got %r" % (who, k))
+    _want_count(who, "k", k)
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 <= eps < float("inf"):
         raise DGLError("%s: eps must be a finite number >= 0, got %r" % (who, eps))
-    for seglen in (ref_seglen, query_seglen):
-        if torch.is_tensor(seglen) and seglen.device != x.device and seglen.device.type != "cpu":  # host lengths go with any x
-            raise DGLError("%s: operands on different devices: %s vs %s" % (who, x.device, seglen.device))
-    offsets, n = _segment_offsets(ref_seglen, x, ref_total, who)
-    q_offsets, m = _segment_offsets(query_seglen, y, query_total, who)
+    for seglen, rows, total in ((ref_seglen, x, ref_total), (query_seglen, y, query_total)):
+        _want_seglen(who, seglen, rows, total)
+        _want_seglen_device(who, seglen, x)
     if ref_seglen.shape[0] != query_seglen.shape[0]:
         raise DGLError("%s: %d reference segments but %d query segments" % (who, ref_seglen.shape[0], query_seglen.shape[0]))
-    return offsets, n, q_offsets, m
+
+
+def _segment_knn_query_kernel_ok(ref_seglen, x, y, k):
+    return (_device_kernels(x, config.KNN_QUERY_FUSED, "segment_knn_query") and y.shape[0] > 0 and ref_seglen.shape[0] < 2 ** 31
+            and _rows_fit(x) and _rows_fit(y) and sparse.backend_for(x).segment_knn_query_supported(k, int(x.shape[1])))
 
 
 def segment_knn_query_fused(ref_seglen, x, query_seglen, y, k, ref_total=None, query_total=None, return_dist=False, return_weight=False,
                             eps=1e-8):
     """True when segment_knn_query(...) with these operands runs csrc/knn.hip (else the composition of distances and a stable sort)."""
-    if (not torch.is_tensor(x) or not torch.is_tensor(y) or x.dim() != 2 or y.dim() != 2 or x.dtype != torch.float32
-            or y.dtype != torch.float32 or x.device != y.device or x.shape[1] != y.shape[1]
-            or not torch.is_tensor(ref_seglen) or not torch.is_tensor(query_seglen) or ref_seglen.dim() != 1 or query_seglen.dim() != 1
-            or ref_seglen.shape[0] != query_seglen.shape[0]
-            or any(s.device != x.device and s.device.type != "cpu" for s in (ref_seglen, query_seglen))
-            or isinstance(k, bool) or not isinstance(k, int) or k < 1
-            or not config.KNN_QUERY_FUSED or x.device.type not in sparse._BACKENDS or not _readout_kernels(x)
-            or not hasattr(sparse.backend_for(x), "segment_knn_query")):
+    try:
+        _segment_knn_query_args(ref_seglen, x, query_seglen, y, k, ref_total, query_total, eps)
+        return _segment_knn_query_kernel_ok(ref_seglen, x, y, k)
+    except DGLError:
         return False
-    N, M, D = int(x.shape[0]), int(y.shape[0]), int(x.shape[1])
-    ld = int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= D else D
-    ldq = int(y.stride(0)) if y.stride(1) == 1 and y.stride(0) >= D else D
-    return (M > 0 and D >= 1 and N < 2 ** 31 and M < 2 ** 31 and ref_seglen.shape[0] < 2 ** 31 and N * ld < 2 ** 30 and M * ldq < 2 ** 30
-            and sparse.backend_for(x).segment_knn_query_supported(k, D))
 
 
 def segment_knn_query(ref_seglen, x, query_seglen, y, k, ref_total=None, query_total=None, return_dist=False, return_weight=False, eps=1e-8):
@@ -2323,8 +2361,10 @@ def segment_knn_query(ref_seglen, x, query_seglen, y, k, ref_total=None, query_t
     k <= 64 and D <= 256 run csrc/knn.hip -- the kernel of segment_knn, which is the case y = x -- in one launch that writes no [M, n]
     matrix (segment_knn_query_fused); everything else -- CPU tensors under a registered CPU backend, larger k or D,
     config.KNN_QUERY_FUSED = False -- is a stable sort of the distances per segment in torch operators."""
-    offsets, n, q_offsets, m = _segment_knn_query_args(ref_seglen, x, query_seglen, y, k, ref_total, query_total, eps)
-    if segment_knn_query_fused(ref_seglen, x, query_seglen, y, k, n, m, return_dist, return_weight, eps):
+    _segment_knn_query_args(ref_seglen, x, query_seglen, y, k, ref_total, query_total, eps)
+    offsets, _ = _segment_offsets(ref_seglen, x, ref_total, "segment_knn_query")
+    q_offsets, _ = _segment_offsets(query_seglen, y, query_total, "segment_knn_query")
+    if _segment_knn_query_kernel_ok(ref_seglen, x, y, k):
         with torch.no_grad():
             index, dist, weight = sparse.backend_for(x).segment_knn_query(offsets, x.detach(), q_offsets, y.detach(), k, float(eps),
                                                                           return_dist, return_weight)
@@ -2408,17 +2448,9 @@ def _segment_ball_query_composed(offsets, x, centers, radius2, K, pad_first):
 
 
 def _segment_fps_args(seglen, x, npoints, start, total):
-    if not torch.is_tensor(x) or x.dim() != 2:
-        raise DGLError("segment_fps: expected x [N, D], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
-    if x.dtype != torch.float32:
-        raise DGLError("segment_fps expects float32 input, got %s" % (x.dtype,))
-    if isinstance(npoints, bool) or not isinstance(npoints, int) or npoints < 1:
-        raise DGLError("segment_fps: npoints must be an integer >= 1, got %r" % (npoints,))
-    if torch.is_tensor(seglen) and seglen.device != x.device and seglen.device.type != "cpu":  # host lengths go with any x
-        raise DGLError("segment_fps: operands on different devices: %s vs %s" % (x.device, seglen.device))
-    if x.shape[1] < 1:
-        raise DGLError("segment_fps: x has no columns")
-    offsets, n = _segment_offsets(seglen, x, total, "segment_fps")
+    """`start` as a contiguous int64 tensor [S] or None of a segment_fps call, or DGLError."""
+    _segment_rows_args("segment_fps", seglen, x, total)
+    _want_count("segment_fps", "npoints", npoints)
     S = int(seglen.shape[0])
     if start is not None:
         if isinstance(start, int) and not isinstance(start, bool):
@@ -2429,7 +2461,7 @@ def _segment_fps_args(seglen, x, npoints, start, total):
                            % (S, x.device, (start.dtype, tuple(start.shape), start.device) if torch.is_tensor(start) else repr(start)))
         else:
             start = start.contiguous()
-    return offsets, n, start
+    return start
 
 
 def _fps_max_len(seglen, max_len):
@@ -2441,13 +2473,9 @@ def _fps_max_len(seglen, max_len):
 
 
 def _segment_fps_kernel_ok(seglen, x, npoints, max_len):
-    if (not config.FPS_FUSED or x.device.type not in sparse._BACKENDS or not _readout_kernels(x)
-            or not hasattr(sparse.backend_for(x), "segment_fps")):
-        return False
-    N, D, S = int(x.shape[0]), int(x.shape[1]), int(seglen.shape[0])
-    ld = int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= D else D
-    return (S > 0 and N < 2 ** 31 and S * npoints < 2 ** 31 and N * ld < 2 ** 30
-            and sparse.backend_for(x).segment_fps_supported(D, max_len))
+    S = int(seglen.shape[0])
+    return (_device_kernels(x, config.FPS_FUSED, "segment_fps") and S > 0 and S * npoints < 2 ** 31 and _rows_fit(x)
+            and sparse.backend_for(x).segment_fps_supported(int(x.shape[1]), max_len))
 
 
 def segment_fps_fused(seglen, x, npoints, start=None, total=None, max_len=None, return_dist=False):
@@ -2475,7 +2503,8 @@ def segment_fps(seglen, x, npoints, start=None, total=None, max_len=None, return
     than max_len is sampled from its first max_len rows only.  Device operands with D <= 64 and max_len <= min(16384,
     38912 // (D | 1)) -- 12 970 points for D = 3 -- run csrc/fps.hip, the whole chain in one launch (segment_fps_fused); everything
     else -- CPU tensors under a registered CPU backend, longer segments, config.FPS_FUSED = False -- is the same loop in torch operators."""
-    offsets, n, start = _segment_fps_args(seglen, x, npoints, start, total)
+    start = _segment_fps_args(seglen, x, npoints, start, total)
+    offsets, _ = _segment_offsets(seglen, x, total, "segment_fps")
     max_len = _fps_max_len(seglen, max_len)
     if _segment_fps_kernel_ok(seglen, x, npoints, max_len):
         with torch.no_grad():
@@ -2487,12 +2516,9 @@ def segment_fps(seglen, x, npoints, start=None, total=None, max_len=None, return
 
 
 def _segment_ball_query_args(seglen, x, centers, radius, max_neighbors, pad, total):
-    if not torch.is_tensor(x) or x.dim() != 2:
-        raise DGLError("segment_ball_query: expected x [N, D], got %s" % (tuple(x.shape) if torch.is_tensor(x) else type(x).__name__,))
-    if x.dtype != torch.float32:
-        raise DGLError("segment_ball_query expects float32 input, got %s" % (x.dtype,))
-    if isinstance(max_neighbors, bool) or not isinstance(max_neighbors, int) or max_neighbors < 1:
-        raise DGLError("segment_ball_query: max_neighbors must be an integer >= 1, got %r" % (max_neighbors,))
+    """radius2 = float32(radius) * float32(radius) of a segment_ball_query call, or DGLError."""
+    _segment_rows_args("segment_ball_query", seglen, x, total)
+    _want_count("segment_ball_query", "max_neighbors", max_neighbors)
     if not torch.is_tensor(centers) or centers.dim() != 1 or centers.dtype != torch.int64 or centers.device != x.device:
         raise DGLError("segment_ball_query: centers must be an int64 tensor [M] of rows of x on %s, got %s"
                        % (x.device, (centers.dtype, tuple(centers.shape), centers.device) if torch.is_tensor(centers) else type(centers).__name__))
@@ -2500,27 +2526,22 @@ def _segment_ball_query_args(seglen, x, centers, radius, max_neighbors, pad, tot
         raise DGLError("segment_ball_query: radius must be a number >= 0, got %r" % (radius,))
     if pad not in ("first", None):
         raise DGLError("segment_ball_query: pad must be 'first' or None, got %r" % (pad,))
-    if torch.is_tensor(seglen) and seglen.device != x.device and seglen.device.type != "cpu":
-        raise DGLError("segment_ball_query: operands on different devices: %s vs %s" % (x.device, seglen.device))
-    if x.shape[1] < 1:
-        raise DGLError("segment_ball_query: x has no columns")
-    offsets, n = _segment_offsets(seglen, x, total, "segment_ball_query")
     r = torch.tensor(float(radius), dtype=torch.float32)
-    return offsets, n, float(r * r)                                                            # float32(radius) * float32(radius), once, on the host
+    return float(r * r)                                                                        # once, on the host
+
+
+def _segment_ball_query_kernel_ok(seglen, x, centers, max_neighbors):
+    return (_device_kernels(x, config.BALL_QUERY_FUSED, "segment_ball_query") and seglen.shape[0] < 2 ** 31 and _rows_fit(x)
+            and centers.shape[0] < 2 ** 31 and sparse.backend_for(x).segment_ball_query_supported(max_neighbors, int(x.shape[1])))
 
 
 def segment_ball_query_fused(seglen, x, centers, radius, max_neighbors, pad="first", total=None):
     """True when segment_ball_query(...) with these operands runs csrc/ballquery.hip (else the composition in torch operators)."""
-    if (not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not torch.is_tensor(seglen) or not torch.is_tensor(centers)
-            or centers.dtype != torch.int64 or centers.dim() != 1 or centers.device != x.device
-            or (seglen.device != x.device and seglen.device.type != "cpu") or isinstance(max_neighbors, bool)
-            or not isinstance(max_neighbors, int) or max_neighbors < 1 or not config.BALL_QUERY_FUSED
-            or x.device.type not in sparse._BACKENDS or not _readout_kernels(x) or not hasattr(sparse.backend_for(x), "segment_ball_query")):
+    try:
+        _segment_ball_query_args(seglen, x, centers, radius, max_neighbors, pad, total)
+        return _segment_ball_query_kernel_ok(seglen, x, centers, max_neighbors)
+    except DGLError:
         return False
-    N, D = int(x.shape[0]), int(x.shape[1])
-    ld = int(x.stride(0)) if x.stride(1) == 1 and x.stride(0) >= D else D
-    return (D >= 1 and N < 2 ** 31 and seglen.shape[0] < 2 ** 31 and N * ld < 2 ** 30 and centers.shape[0] < 2 ** 31
-            and sparse.backend_for(x).segment_ball_query_supported(max_neighbors, D))
 
 
 def segment_ball_query(seglen, x, centers, radius, max_neighbors, pad="first", total=None):
@@ -2537,8 +2558,9 @@ def segment_ball_query(seglen, x, centers, radius, max_neighbors, pad="first", t
     `total`: the row count when the caller knows it (no read-back of device lengths).  Device operands with K <= 64 and D <= 256 run
     csrc/ballquery.hip in one launch that writes no [M, n] matrix (segment_ball_query_fused); everything else -- CPU tensors under a
     registered CPU backend, larger K or D, config.BALL_QUERY_FUSED = False -- is a masked running count per segment in torch operators."""
-    offsets, n, radius2 = _segment_ball_query_args(seglen, x, centers, radius, max_neighbors, pad, total)
-    if segment_ball_query_fused(seglen, x, centers, radius, max_neighbors, pad, n):
+    radius2 = _segment_ball_query_args(seglen, x, centers, radius, max_neighbors, pad, total)
+    offsets, _ = _segment_offsets(seglen, x, total, "segment_ball_query")
+    if _segment_ball_query_kernel_ok(seglen, x, centers, max_neighbors):
         with torch.no_grad():
             return sparse.backend_for(x).segment_ball_query(offsets, x.detach(), centers.contiguous(), radius2, max_neighbors, pad == "first")
     sparse.backend_for(x)  # no CPU backend: DGLError
@@ -2686,17 +2708,31 @@ def rel_weight_matrix(g, edge_weights):
     return held[2]
 
 
+def _rel_gspmm_args(g, x, w, reduce):
+    """The graph index of a rel_gspmm call, or DGLError.  Row counts and dtypes are gspmm's to judge: the broadcast form takes them."""
+    gidx = _gidx(g)
+    if reduce not in ("sum", "mean"):
+        raise DGLError("rel_gspmm: reduce must be 'sum' or 'mean', got %r" % (reduce,))
+    if not (torch.is_tensor(x) and torch.is_tensor(w) and x.dim() == 2 and w.dim() == 2):
+        raise DGLError("rel_gspmm: expected x [N_src, D] and w [E, R], got shapes %s and %s"
+                       % tuple(tuple(t.shape) if torch.is_tensor(t) else type(t).__name__ for t in (x, w)))
+    return gidx
+
+
+def _rel_gspmm_kernel_ok(gidx, x, w):
+    E = gidx.num_edges()
+    if (not _device_kernels(x, True, "spmm_rel") or w.device != x.device or w.requires_grad or x.dtype != torch.float32
+            or w.dtype != torch.float32 or capture_path() or x.shape[0] != gidx.num_src or w.shape[0] != E or E == 0):
+        return False
+    return sparse.backend_for(x).spmm_rel_supported(gidx.csc(), x, int(w.shape[1]))
+
+
 def rel_gspmm_fused(g, x, w):
     """True when rel_gspmm(g, x, w) runs the one-pass kernels (else it is gspmm's (N, 1, D) x (E, R, 1) broadcast)."""
-    gidx = _gidx(g)
-    if (not torch.is_tensor(x) or not torch.is_tensor(w) or x.dim() != 2 or w.dim() != 2 or w.requires_grad or not x.is_cuda or not w.is_cuda
-            or x.dtype != torch.float32 or w.dtype != torch.float32 or x.device != w.device or x.device.type not in sparse._BACKENDS
-            or _torch_ops() is not None or capture_path()):
+    try:
+        return _rel_gspmm_kernel_ok(_rel_gspmm_args(g, x, w, "mean"), x, w)
+    except DGLError:
         return False
-    be = sparse.backend_for(x)
-    if not hasattr(be, "spmm_rel") or x.shape[0] != gidx.num_src or w.shape[0] != gidx.num_edges() or gidx.num_edges() == 0:
-        return False
-    return be.spmm_rel_supported(gidx.csc(), x, int(w.shape[1]))
 
 
 def rel_gspmm(g, x, w, reduce="mean", cache=None):
@@ -2707,15 +2743,12 @@ def rel_gspmm(g, x, w, reduce="mean", cache=None):
     operands with 1 <= R <= 16 and D a power of two up to 128 run csrc/spmm_rel.hip (forward and the gradient with respect to x);
     weights that need a gradient, and every other operand, take gspmm(g, "mul", reduce, x[:, None, :], w[:, :, None]) -- the same values
     through the broadcast kernels.  cache: a RelWeightCache for the permuted weights (default: the one kept on the graph; False: none)."""
-    if reduce not in ("sum", "mean"):
-        raise DGLError("rel_gspmm: reduce must be 'sum' or 'mean', got %r" % (reduce,))
-    if x.dim() != 2 or w.dim() != 2:
-        raise DGLError("rel_gspmm: expected x [N_src, D] and w [E, R], got shapes %s and %s" % (tuple(x.shape), tuple(w.shape)))
-    if not rel_gspmm_fused(g, x, w):
-        return gspmm(g, "mul", reduce, x.unsqueeze(1), w.unsqueeze(-1))
+    gidx = _rel_gspmm_args(g, x, w, reduce)
+    if not _rel_gspmm_kernel_ok(gidx, x, w):
+        return gspmm(gidx, "mul", reduce, x.unsqueeze(1), w.unsqueeze(-1))
     if cache is None:
-        cache = rel_weight_cache_for(g)
-    return RelGSpMM.apply(_gidx(g), reduce, x, w, cache if cache is not False else None)
+        cache = rel_weight_cache_for(gidx)
+    return RelGSpMM.apply(gidx, reduce, x, w, cache if cache is not False else None)
 
 
 def gsddmm(g, op, lhs_data, rhs_data, lhs_target="u", rhs_target="v"):
