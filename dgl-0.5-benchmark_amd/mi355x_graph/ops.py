@@ -892,13 +892,15 @@ def relu_dropout(x, p=0.5, training=True, out=None):
     """dropout(relu(x), p) in one pass each way (float32 HIP tensors with numel % 4 == 0; anything else and evaluation mode
     take the two PyTorch ops).  Under HIP-graph capture the mask's position in the random stream is read from a device
     counter that the captured step advances, so replays draw new masks.  `out`: a [rows, cols] view with
-    unit column stride to write the result into (a column block of a wider matrix); ignored on the PyTorch path."""
+    unit column stride, a row stride that is a multiple of 4 and a 16-byte aligned base to write the result into (a column block of a
+    wider matrix); any other `out`, and the PyTorch path, ignore it.  x itself may lie anywhere: what the kernels cannot read in
+    place the backend copies (sparse.dense16)."""
     if (not training or p <= 0.0 or p >= 1.0 or x.dtype != torch.float32 or x.device.type != "cuda" or x.numel() % 4
             or x.device.type not in sparse._BACKENDS
             or (capture_path() and (x.dim() != 2 or x.shape[1] % 4 or x.stride(1) != 1 or x.stride(0) % 4))):
         return _structural_zeros(torch.nn.functional.dropout(torch.relu(x), p, training))
     if out is not None and (x.dim() != 2 or x.shape[1] % 4 or out.shape != x.shape or out.stride(1) != 1 or out.stride(0) % 4
-                            or out.requires_grad):
+                            or out.stride(0) < out.shape[1] or out.data_ptr() % 16 or out.requires_grad):
         out = None
     return _structural_zeros(ReluDropout.apply(x, p, None if out is None else _Into(out)))
 
@@ -1998,10 +2000,8 @@ def _rows_fit(x):
     return x.shape[0] * _row_ld(x) < 2 ** 30  # 32-bit element indices in the kernels
 
 
-def _aligned16(*tensors):
-    # the kernels read 16 bytes per lane: a contiguous view at an odd storage offset is not theirs (a strided one is copied, and a
-    # fresh allocation is aligned)
-    return not any(t is not None and t.is_contiguous() and t.data_ptr() % 16 for t in tensors)
+_aligned16 = sparse.aligned16  # the kernels read 16 bytes per lane: a contiguous view at an odd storage offset is not theirs.  The backend
+# wrappers would copy it (sparse.dense16); the operators that have a composition send it there instead, which reads it in place
 
 
 def _device_kernels(t, switch, *methods):

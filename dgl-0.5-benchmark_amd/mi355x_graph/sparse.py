@@ -62,6 +62,50 @@ def _prod(shape):
     return p
 
 
+# ----------------------------------------------------------------------------- operand layouts
+# The C entry points take raw pointers; the kernels behind many of them read 16 bytes per lane.  What a wrapper may hand such an entry
+# is decided here, once (docs/LOG_operand_layouts.md lists every entry point and which of these it needs):
+#   aligned16  the predicate: no operand is contiguous at an odd storage offset
+#   dense16    a dense operand: contiguous, base 16-byte aligned -- the tensor itself when it already is, else a copy
+#   rows16     an operand of an entry that takes a row stride: the view itself when the kernels can walk it, else dense16
+def _off16(t):
+    """the one statement of the rule: the base of `t` is not on a 16-byte boundary"""
+    return t.data_ptr() % 16 != 0
+
+
+def aligned16(*tensors):
+    """False when one of `tensors` is contiguous at a base that is not 16-byte aligned (a slice of a flattened buffer, a gradient cut
+    out of a `cat`): the 16-byte lanes cannot read it where it lies.  None entries pass; a strided tensor is copied by its wrapper and
+    a fresh allocation is aligned."""
+    return not any(t is not None and t.is_contiguous() and _off16(t) for t in tensors)
+
+
+def dense16(t):
+    """`t` as the kernels take a dense operand: contiguous with a 16-byte aligned base.  An aligned contiguous tensor is returned as
+    it is (no copy); a strided or expanded view is made contiguous; a contiguous tensor at an odd storage offset is copied into a
+    fresh allocation: the entry points refuse such a base."""
+    if t is None:
+        return None
+    t = t.contiguous()
+    return t if aligned16(t) else t.clone(memory_format=torch.contiguous_format)
+
+
+def rows16(t, max_bytes=None):
+    """(tensor, row stride in floats) of a [N, ...] operand as an entry point with a row-stride argument takes it: the floats of a row
+    contiguous, the row stride a multiple of 4 floats and at least the row length, the base 16-byte aligned (a column block of a wider
+    matrix whose first column is a multiple of 4 qualifies; max_bytes: rows * stride * 4 stays below it) -- else a dense16 copy."""
+    W, want = _prod(t.shape[1:]), 1
+    for size, stride in zip(reversed(t.shape[1:]), reversed(t.stride()[1:])):
+        if size != 1 and stride != want:
+            return dense16(t), W
+        want *= int(size)
+    ld = int(t.stride(0))
+    if (t.dim() >= 2 and t.shape[0] > 0 and ld >= W and ld % 4 == 0 and not _off16(t)
+            and (max_bytes is None or t.shape[0] * ld * 4 < max_bytes)):
+        return t, ld
+    return dense16(t), W
+
+
 class CsrView(object):
     """An immutable CSR over torch tensors (in-CSR: rows = destination nodes)."""
 
@@ -739,12 +783,12 @@ class HipBackend(object):
 
     def spmm_rel_grad(self, csr_t, w_pos_t, dz3d, dst_scale=None, src_scale=None):
         """dx[u, :] = src_scale[u] * sum_{p in row u} sum_r w_pos_t[p, r] * dst_scale[v_p] * dz3d[v_p, r, :] (mgx_spmm_rel_grad) over the
-        TRANSPOSED CSR (rows = source nodes) with the weights in its position order; dz3d: [num_cols, R, D] contiguous."""
+        TRANSPOSED CSR (rows = source nodes) with the weights in its position order; dz3d: [num_cols, R, D] in any layout (dense16)."""
         dev = self._check_dev(csr_t.indptr, w_pos_t, dz3d, src_scale, dst_scale)
         R, D = int(dz3d.shape[1]), int(dz3d.shape[2])
-        if (w_pos_t.shape[0] != csr_t.nnz or int(w_pos_t.shape[1]) != R or dz3d.shape[0] != csr_t.num_cols or not w_pos_t.is_contiguous()
-                or not dz3d.is_contiguous()):
-            raise DGLError("spmm_rel_grad: expected contiguous [nnz, R] weights and a contiguous [num_cols, R, D] gradient")
+        if w_pos_t.shape[0] != csr_t.nnz or int(w_pos_t.shape[1]) != R or dz3d.shape[0] != csr_t.num_cols or not w_pos_t.is_contiguous():
+            raise DGLError("spmm_rel_grad: expected contiguous [nnz, R] weights and a [num_cols, R, D] gradient")
+        dz3d = dense16(dz3d)
         dx = torch.empty((csr_t.num_rows, D), dtype=torch.float32, device=dev)
         plan = csr_t.plan()
         partial = None
@@ -896,6 +940,7 @@ class HipBackend(object):
         kernel family that ran: with p > 0 it fixes how the dropout mask is keyed, and the backward must be given it back."""
         dev = self._check_dev(csc.indptr, feat3d, el2d, er2d)
         H, F = int(feat3d.shape[1]), int(feat3d.shape[2])
+        feat3d, el2d, er2d = dense16(feat3d), el2d.contiguous(), er2d.contiguous()  # (el / er: 4-byte accesses, any base)
         out = torch.empty((csc.num_rows, H, F), dtype=torch.float32, device=dev)
         nstat = torch.empty((csc.num_rows, H, 4), dtype=torch.float32, device=dev)
         tiles = self._gat_tile_plans(csc, csr, H, F, p)
@@ -931,6 +976,7 @@ class HipBackend(object):
         switch flipped, a plan that failed to build in between) would silently apply another mask."""
         dev = self._check_dev(csc.indptr, csr.indptr, feat3d, el2d, out3d, d_out3d, nstat)
         H, F = int(feat3d.shape[1]), int(feat3d.shape[2])
+        feat3d, el2d, out3d, d_out3d = dense16(feat3d), el2d.contiguous(), dense16(out3d), dense16(d_out3d)
         d_er = torch.empty((csc.num_rows, H), dtype=torch.float32, device=dev)
         d_feat = torch.empty_like(feat3d) if need_src else None
         d_el = torch.empty((csc.num_cols, H), dtype=torch.float32, device=dev) if need_src else None
@@ -976,13 +1022,8 @@ class HipBackend(object):
     def _dot_operand(x3d):
         """(tensor, row stride in floats) of a [N, H, F] operand as the kernels take it: the H*F floats of a node contiguous, the row
         stride a multiple of 4 floats, the base 16-byte aligned, rows * stride below 4 GiB (a column block of a wider projection qualifies);
-        else a dense copy."""
-        H, F = int(x3d.shape[1]), int(x3d.shape[2])
-        if (x3d.shape[0] > 0 and x3d.stride(2) == 1 and x3d.stride(1) == F and x3d.stride(0) >= H * F and x3d.stride(0) % 4 == 0
-                and x3d.data_ptr() % 16 == 0 and x3d.shape[0] * x3d.stride(0) * 4 < 2 ** 32):  # 32-bit byte offsets: a dense copy fits
-            return x3d, int(x3d.stride(0))
-        x3d = x3d.contiguous()
-        return x3d, H * F
+        else an aligned dense copy (rows16)."""
+        return rows16(x3d, max_bytes=2 ** 32)  # 32-bit byte offsets: a dense copy fits
 
     def dot_attention_fwd(self, csc, q3d, k3d, v3d, scale):
         """q3d [n_dst, H, F], k3d / v3d [n_src, H, F] (row-strided views are taken as they are) -> (out [n_dst, H, F],
@@ -1010,6 +1051,7 @@ class HipBackend(object):
         same = k3d is v3d
         (q, q_ld), (k, k_ld) = self._dot_operand(q3d), self._dot_operand(k3d)
         v, v_ld = (k, k_ld) if same else self._dot_operand(v3d)
+        out3d, d_out3d = dense16(out3d), dense16(d_out3d)
         dq = torch.empty((csc.num_rows, H, F), dtype=torch.float32, device=dev) if need_q else None
         dk = torch.empty((csc.num_cols, H, F), dtype=torch.float32, device=dev) if need_k else None
         dv = torch.empty((csc.num_cols, H, F), dtype=torch.float32, device=dev) if need_v else None
@@ -1033,8 +1075,10 @@ class HipBackend(object):
         return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
 
     def gine_fwd(self, csc, x2d, w2d, scale1d):
-        """x2d [n_src, D], w2d [E, D] and scale1d [E] | None by edge id (all contiguous) -> out [n_dst, D]."""
+        """x2d [n_src, D], w2d [E, D] and scale1d [E] | None by edge id (any layout: what the kernels cannot read in place is copied,
+        dense16) -> out [n_dst, D]."""
         dev = self._check_dev(csc.indptr, x2d, w2d, scale1d)
+        x2d, w2d, scale1d = dense16(x2d), dense16(w2d), None if scale1d is None else scale1d.contiguous()
         D = int(x2d.shape[1])
         out = torch.empty((csc.num_rows, D), dtype=torch.float32, device=dev)
         plan = csc.plan()
@@ -1045,11 +1089,14 @@ class HipBackend(object):
         return out
 
     def gine_bwd(self, csr, x2d, w2d, scale1d, d_out2d, need_x, need_w):
-        """csr: the out-CSR (rows = sources) -> (d_x [n_src, D] | None, d_w [E, D] by edge id | None)."""
+        """csr: the out-CSR (rows = sources); operands and the gradient d_out2d [n_dst, D] in any layout (dense16)
+        -> (d_x [n_src, D] | None, d_w [E, D] by edge id | None)."""
         dev = self._check_dev(csr.indptr, x2d, w2d, scale1d, d_out2d)
         D = int(x2d.shape[1])
         if not (need_x or need_w):
             return None, None
+        x2d, w2d, d_out2d = dense16(x2d), dense16(w2d), dense16(d_out2d)
+        scale1d = None if scale1d is None else scale1d.contiguous()
         d_x = torch.empty((csr.num_rows, D), dtype=torch.float32, device=dev) if need_x else None
         d_w = torch.empty((csr.nnz, D), dtype=torch.float32, device=dev) if need_w else None
         plan = csr.plan()
@@ -1070,9 +1117,11 @@ class HipBackend(object):
         return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
 
     def multi_agg_fwd(self, csc, x2d, w2d, aggregators, eps):
-        """x2d [n_src, D], w2d [E, D] by edge id | None (contiguous) -> (out [n_dst, A, D] in the order of `aggregators`,
-        arg_max | None, arg_min | None (int32 [n_dst, D], edge ids), stats [n_dst, 2, D] = (mean, var) | None)."""
+        """x2d [n_src, D], w2d [E, D] by edge id | None (any layout: what the kernels cannot read in place is copied, dense16) ->
+        (out [n_dst, A, D] in the order of `aggregators`, arg_max | None, arg_min | None (int32 [n_dst, D], edge ids),
+        stats [n_dst, 2, D] = (mean, var) | None)."""
         dev = self._check_dev(csc.indptr, x2d, w2d)
+        x2d, w2d = dense16(x2d), dense16(w2d)
         D, A = int(x2d.shape[1]), len(aggregators)
         out = torch.empty((csc.num_rows, A, D), dtype=torch.float32, device=dev)
         block = {name: ctypes.c_void_p(out.data_ptr() + i * D * 4) for i, name in enumerate(aggregators)}
@@ -1088,12 +1137,13 @@ class HipBackend(object):
         return out, arg_max, arg_min, stats
 
     def multi_agg_bwd(self, csr, x2d, w2d, A2d, B2d, g_max, arg_max, g_min, arg_min, need_x, need_w):
-        """csr: the out-CSR (rows = sources); A2d, B2d | None, g_max / g_min | None [n_dst, D] dense with their int32 args
-        -> (d_x [n_src, D] | None, d_w [E, D] by edge id | None)."""
+        """csr: the out-CSR (rows = sources); A2d, B2d | None, g_max / g_min | None [n_dst, D] (any layout, dense16) with their
+        int32 args -> (d_x [n_src, D] | None, d_w [E, D] by edge id | None)."""
         dev = self._check_dev(csr.indptr, x2d, w2d, A2d, B2d, g_max, arg_max, g_min, arg_min)
         D = int(x2d.shape[1])
         if not (need_x or need_w):
             return None, None
+        x2d, w2d, A2d, B2d, g_max, g_min = (dense16(t) for t in (x2d, w2d, A2d, B2d, g_max, g_min))
         d_x = torch.empty((csr.num_rows, D), dtype=torch.float32, device=dev) if need_x else None
         d_w = torch.empty((csr.nnz, D), dtype=torch.float32, device=dev) if need_w else None
         plan = csr.plan()
@@ -1112,6 +1162,7 @@ class HipBackend(object):
         """feat3d [n, H, F], attn_a/attn_b [H, F] (attn_b may be None) -> (out_a [n, H], out_b [n, H] | None)."""
         dev = self._check_dev(feat3d, attn_a, attn_b)
         n, H, F = feat3d.shape
+        feat3d, attn_a, attn_b = dense16(feat3d), dense16(attn_a), dense16(attn_b)  # the 16-byte lanes of F % 4 == 0 refuse any other base
         out_a = torch.empty((n, H), dtype=torch.float32, device=dev)
         out_b = torch.empty((n, H), dtype=torch.float32, device=dev) if attn_b is not None else None
         with torch.cuda.device(dev):
@@ -1122,6 +1173,8 @@ class HipBackend(object):
     def head_dot_bwd(self, feat3d, attn_a, attn_b, d_a, d_b, need_feat_grad):
         dev = self._check_dev(feat3d, attn_a, attn_b, d_a, d_b)
         n, H, F = feat3d.shape
+        feat3d, attn_a, d_a = feat3d.contiguous(), attn_a.contiguous(), d_a.contiguous()  # (4-byte accesses only: any base)
+        attn_b, d_b = (None, None) if attn_b is None else (attn_b.contiguous(), d_b.contiguous())
         d_feat = torch.empty_like(feat3d) if need_feat_grad else None
         g_a = torch.empty_like(attn_a)
         g_b = torch.empty_like(attn_b) if attn_b is not None else None
@@ -1179,21 +1232,11 @@ class HipBackend(object):
     @staticmethod
     def _seg_operand(x3d):
         """(tensor, row stride in floats) of a [N, H, F] feature operand as the kernels take it: the H*F floats of a row contiguous, the
-        row stride a multiple of 4 floats, the base 16-byte aligned (a column block of a wider matrix qualifies); else a dense copy."""
-        H, F = int(x3d.shape[1]), int(x3d.shape[2])
-        if (x3d.shape[0] > 0 and x3d.stride(2) == 1 and x3d.stride(1) == F and x3d.stride(0) >= H * F and x3d.stride(0) % 4 == 0
-                and x3d.data_ptr() % 16 == 0):
-            return x3d, int(x3d.stride(0))
-        return HipBackend._dense16(x3d), H * F
+        row stride a multiple of 4 floats, the base 16-byte aligned (a column block of a wider matrix qualifies); else an aligned dense
+        copy (rows16)."""
+        return rows16(x3d)
 
-    @staticmethod
-    def _dense16(t):
-        """`t` as the kernels take a dense operand: contiguous with a 16-byte aligned base.  A contiguous tensor at an odd storage offset
-        (a slice of a flattened buffer, an upstream gradient cut out of a `cat`) is copied: the entry points refuse such a base."""
-        if t is None:
-            return None
-        t = t.contiguous()
-        return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+    _dense16 = staticmethod(dense16)  # the module's rule under the name the segment-attention wrappers came with
 
     @classmethod
     def segment_attention_supported(cls, feat3d):
@@ -1362,8 +1405,11 @@ class HipBackend(object):
 
     def relu_dropout_fwd(self, x, p, seed, offset, out=None, counter=None):
         """`out`: a row-strided [rows, cols] view to write into (x then 2-D, possibly row-strided itself).  `counter`: a
-        1-element int64 device tensor read by the launch when it RUNS instead of the host-side `offset` (HIP-graph replays)."""
+        1-element int64 device tensor read by the launch when it RUNS instead of the host-side `offset` (HIP-graph replays).
+        An x whose base is not 16-byte aligned is copied first (dense16): every kernel here reads 16 bytes per lane."""
         dev = self._check_dev(x, out, counter)
+        if _off16(x):
+            x = dense16(x)
         mask = torch.empty(x.numel() // 4, dtype=torch.uint8, device=dev)
         if counter is not None:
             y = out if out is not None else torch.empty(x.shape, dtype=torch.float32, device=dev)
@@ -1391,8 +1437,10 @@ class HipBackend(object):
 
     def relu_dropout_bwd(self, dy, mask, p, out=None):
         """dy: contiguous, or a row-strided [rows, cols] view (the gradient's column block); dx is dense, or `out`: a row-strided [rows, cols]
-        view to write into (the left half of a wider matrix)."""
+        view to write into (the left half of a wider matrix).  A dy whose base is not 16-byte aligned is copied first (dense16)."""
         dev = self._check_dev(dy, mask, out)
+        if _off16(dy):
+            dy = dense16(dy)
         if out is not None:
             if dy.dim() != 2 or out.shape != dy.shape or not self._row_strided(out) or not (dy.is_contiguous() or self._row_strided(dy)):
                 raise DGLError("relu_dropout_bwd: `out` must be a [rows, cols] view with unit column stride of the gradient's shape")
@@ -1415,6 +1463,8 @@ class HipBackend(object):
         """relu_dropout_bwd into `out` (a row-strided [rows, 64] view) + (slots, overflow) of row_scale * result, as rows_slots_pack would
         give them -- one pass (mgx_relu_dropout_bwd_slots)."""
         dev = self._check_dev(dy, mask, out, row_scale)
+        if _off16(dy):  # as relu_dropout_bwd: a gradient off a 16-byte boundary is copied, not refused
+            dy = dense16(dy)
         if (dy.dim() != 2 or dy.shape[1] != 64 or out.shape != dy.shape or not self._row_strided(out) or out.data_ptr() % 16
                 or not (dy.is_contiguous() or self._row_strided(dy)) or dy.data_ptr() % 16):
             raise DGLError("relu_dropout_bwd_slots: [rows, 64] operands with unit column stride, 16-byte aligned")
@@ -1431,6 +1481,7 @@ class HipBackend(object):
         the squared / second operand -- (sum (a-p), sum (a-p)^2) with p = a[0], or (sum a, sum a*(b-p)) with p = b[0]."""
         dev = self._check_dev(a2d, b2d)
         n, C = a2d.shape
+        a2d, b2d = a2d.contiguous(), None if b2d is None else b2d.contiguous()  # (4-byte accesses only: any base)
         out = torch.empty((2, C), dtype=torch.float32, device=dev)
         ws = torch.empty(2 * _lib.lib().mgx_column_sum_workspace(C) // 4, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
@@ -1439,8 +1490,9 @@ class HipBackend(object):
         return out[0], out[1]
 
     def column_affine(self, a2d, A, Cc, b2d=None, B=None):
-        """a*A[c] + b*B[c] + Cc[c] with per-column coefficient vectors."""
+        """a*A[c] + b*B[c] + Cc[c] with per-column coefficient vectors; operands in any layout (16-byte lanes: dense16)."""
         dev = self._check_dev(a2d, b2d, A, B, Cc)
+        a2d, b2d, A, B, Cc = (dense16(t) for t in (a2d, b2d, A, B, Cc))
         out = torch.empty_like(a2d)
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().mgx_column_affine(a2d.shape[0], a2d.shape[1], _ptr(a2d), _ptr(b2d), _ptr(A), _ptr(B), _ptr(Cc),
@@ -1451,6 +1503,13 @@ class HipBackend(object):
     XTY_TILE = (64, 128)      # one tile of mgx_xty
     XTY_MAX = (256, 1024)     # the grid of tiles in one launch goes up to this output shape
     XTY_MIN_ROWS = 1 << 16    # shorter reductions stay with the GEMM library
+
+    @staticmethod
+    def _row_walkable(t):
+        """Can the mgx_xty* kernels walk t [n, W] by its row stride?  Unit column stride and rows that do not overlap: the wrappers pass
+        max(stride(0), W), which is right for the free stride of a one-row tensor only -- an expanded view (stride 0 along the rows, what
+        `row.expand(n, W)` gives) would be read W floats per row past its single row."""
+        return t.stride(1) == 1 and (t.stride(0) >= t.shape[1] or t.shape[0] < 2)
 
     def _xty_call(self, dev, M, K, colsum, call, out=None):
         """One call of an mgx_xty* entry point: allocates out [M, K] (unless the caller hands in the tile of a larger output), sums [M]
@@ -1474,7 +1533,8 @@ class HipBackend(object):
         n, M = a2d.shape
         K = b2d.shape[1]
         tm, tk = self.XTY_TILE
-        if (M > tm or K > tk or a2d.stride(1) != 1 or b2d.stride(1) != 1 or a2d.dtype != torch.float32 or b2d.dtype != torch.float32):
+        if (M > tm or K > tk or not self._row_walkable(a2d) or not self._row_walkable(b2d) or a2d.dtype != torch.float32
+                or b2d.dtype != torch.float32):
             return None
         head = (n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(b2d), max(b2d.stride(0), K), _ptr(rows))
         if colsum:
@@ -1490,8 +1550,8 @@ class HipBackend(object):
         n, K = b2d.shape
         M = a2d.shape[1]
         tm, tk = self.XTY_TILE
-        if (a_pos.dtype != torch.int64 or a_pos.shape != (n,) or not a_pos.is_contiguous() or a2d.shape[0] == 0 or M > tm or K > tk or a2d.stride(1) != 1
-                or b2d.stride(1) != 1 or a2d.dtype != torch.float32 or b2d.dtype != torch.float32):
+        if (a_pos.dtype != torch.int64 or a_pos.shape != (n,) or not a_pos.is_contiguous() or a2d.shape[0] == 0 or M > tm or K > tk or not self._row_walkable(a2d)
+                or not self._row_walkable(b2d) or a2d.dtype != torch.float32 or b2d.dtype != torch.float32):
             return None
         res = self._xty_call(dev, M, K, colsum, lambda L, *tail: L.mgx_xty_colsum_pos(
             n, M, K, _ptr(a2d), max(a2d.stride(0), M), _ptr(a_pos), _ptr(b2d), max(b2d.stride(0), K), *tail))
@@ -1507,7 +1567,7 @@ class HipBackend(object):
                 or b2d.dtype != torch.float32 or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.numel() != dy.shape[0] * 16):
             return None
         n, K = b2d.shape
-        if (K < 64 or K > 256 or K % 4 or dy.stride(1) != 1 or b2d.stride(1) != 1 or max(dy.stride(0), 64) % 4 or max(b2d.stride(0), K) % 4
+        if (K < 64 or K > 256 or K % 4 or not self._row_walkable(dy) or not self._row_walkable(b2d) or max(dy.stride(0), 64) % 4 or max(b2d.stride(0), K) % 4
                 or dy.data_ptr() % 16 or b2d.data_ptr() % 16):
             return None
         L = _lib.lib()
@@ -1535,6 +1595,7 @@ class HipBackend(object):
                 return res
             b2d = b2d.index_select(0, rows)
         dev = self._check_dev(a2d, b2d)
+        a2d, b2d = (t if self._row_walkable(t) else t.contiguous() for t in (a2d, b2d))
         n, M = a2d.shape
         K = b2d.shape[1]
         if M > self.XTY_MAX[0] or K > self.XTY_MAX[1]:
@@ -1679,6 +1740,7 @@ class HipBackend(object):
     def column_sum(self, x2d):
         dev = self._check_dev(x2d)
         n, C = x2d.shape
+        x2d = x2d.contiguous()  # (4-byte accesses only: any base)
         out = torch.empty(C, dtype=torch.float32, device=dev)
         ws = torch.empty(_lib.lib().mgx_column_sum_workspace(C) // 4, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
