@@ -139,6 +139,10 @@ SIGNATURES = {
     "mgx_rows_gemm_sweep_rows": (_i64, [_i64, _i64, _i64, _i32]),
     "mgx_rows_gemm_relu_dropout": (_i32, [_i64, _i64, _i64, _fp, _i64, _fp, _i64, _i32, _fp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
                                           _fp, _i64, _vp, _vp, _vp, _vp]),
+    "mgx_segment_mm_supported": (_i32, [_i64, _i64]),
+    "mgx_segment_mm_workspace": (_i64, [_i64, _i64, _i64, _i64, _i32]),
+    "mgx_segment_mm": (_i32, [_i64, _i64, _i64, _i64, _fp, _i64, _vp, _fp, _i32, _vp, _fp, _i64, _vp, _i64, _vp, _vp]),
+    "mgx_segment_mm_grad_b": (_i32, [_i64, _i64, _i64, _i64, _fp, _i64, _vp, _fp, _i64, _vp, _vp, _fp, _vp, _vp]),
     "mgx_column_sum_workspace": (_i64, [_i64]),
     "mgx_column_sum": (_i32, [_i64, _i64, _fp, _fp, _vp, _vp]),
     "mgx_coo_to_csr_workspace": (_i64, [_i64, _i64, _i32]),

@@ -59,6 +59,12 @@ SEGMENT_ATTENTION_FUSED = True  # the fused pair of csrc/segattn.hip; False: seg
 # ---- segment top-k (ops.segment_topk, readout.topk_nodes / topk_edges, nn.SortPooling)
 SEGMENT_TOPK_FUSED = True  # csrc/segtopk.hip, one launch each way; False: two stable sorts and gathers in torch operators
 
+# ---- typed linear layers (ops.segment_mm / gather_mm, nn.TypedLinear, nn.TypedRelGraphConv)
+SEGMENT_MM = True            # the grouped GEMM over row segments of csrc/segmm.hip; False: one torch.matmul per segment
+SEGMENT_MM_ITEM_ROWS = 512   # rows of a segment that share one staging of their weight in LDS (a multiple of 16).  Forward, 64 x 64, us:
+                             # 133 Zipf segments over 1 M rows 153 / 145 / 158 / 172 / 184 at 256 / 512 / 1024 / 2048 / 4096; 8 equal segments
+                             # 149 / 141 / 134 / 134 / 154; 133 equal segments over 6 M rows 746 / 682 / 660 / 654 / 778 (docs/LOG_segment_mm.md)
+
 # ---- point clouds (ops.segment_knn, transform.knn_graph / segmented_knn_graph, nn.EdgeConv; ops.segment_fps, ops.segment_ball_query,
 #      transform.fixed_radius_block, nn.PointNetConv)
 KNN_FUSED = True       # csrc/knn.hip: distances and selection in one launch; False: a stable sort of direct-form distances per segment in torch operators

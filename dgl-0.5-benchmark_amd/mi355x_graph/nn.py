@@ -3,6 +3,7 @@
   DotGatConv dgl.nn.pytorch.DotGatConv (u_dot_v SDDMM + edge_softmax + u_mul_e/sum SpMM, fused: ops.dot_attention)
   GINEConv   dgl.nn.pytorch.GINEConv (sum of relu(h_u + e_uv) messages, fused: ops.gine_sum)
   PNAConv    dgl.nn.pytorch.PNAConv (mean / max / min / std ... of one message per edge, fused: ops.multi_aggregate)
+  TypedLinear / TypedRelGraphConv   dgl.nn.pytorch.TypedLinear and DGL >= 0.8's RelGraphConv (one weight per type: ops.segment_mm / gather_mm)
   SAGEConv   main_dgl_arxiv_sage_nn.py:9,27-34
   GraphConv  main_dgl_enzymes_gcn_nn.py:12,29-36
   AvgPooling / SumPooling / MaxPooling   main_dgl_molhiv_gcn.py:75,93
@@ -382,6 +383,83 @@ class RelGraphConv(nn.Module):
         if self._activation:
             h = self._activation(h)
         return self._dropout(h)
+
+
+class TypedLinear(nn.Module):
+    """dgl.nn.pytorch.TypedLinear (UPSTREAM): y_i = x_i W[type_i], one [in_size, out_size] weight per type.  regularizer None: `W`
+    [num_types, in, out]; 'basis': `W` [num_bases, in, out] and `coeff` [num_types, num_bases], the weights are coeff @ W -- a small
+    matmul in front of the operator.  Names and initialisation are DGL's, so a state_dict moves across.  The product is ONE
+    ops.segment_mm (sorted_by_type) or ops.gather_mm call: csrc/segmm.hip where it takes the shape."""
+
+    def __init__(self, in_size, out_size, num_types, regularizer=None, num_bases=None):
+        super(TypedLinear, self).__init__()
+        if regularizer not in (None, "basis"):
+            raise DGLError("TypedLinear: regularizer must be None or 'basis', got %r%s"
+                           % (regularizer, " ('bdd' is not built on this backend)" if regularizer == "bdd" else ""))
+        if regularizer == "basis" and (isinstance(num_bases, bool) or not isinstance(num_bases, int) or num_bases < 1):
+            raise DGLError("TypedLinear: the basis regularizer needs num_bases >= 1, got %r" % (num_bases,))
+        self.in_size, self.out_size, self.num_types, self.regularizer, self.num_bases = in_size, out_size, num_types, regularizer, num_bases
+        if regularizer is None:
+            self.W = nn.Parameter(torch.empty(num_types, in_size, out_size))
+        else:
+            self.W = nn.Parameter(torch.empty(num_bases, in_size, out_size))
+            self.coeff = nn.Parameter(torch.empty(num_types, num_bases))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        with torch.no_grad():
+            bound = 1.0 / math.sqrt(self.in_size)
+            nn.init.uniform_(self.W, -bound, bound)
+            if self.regularizer == "basis":
+                nn.init.xavier_uniform_(self.coeff, gain=nn.init.calculate_gain("relu"))
+
+    def get_weight(self):
+        if self.regularizer is None:
+            return self.W
+        return torch.matmul(self.coeff, self.W.view(self.num_bases, -1)).view(self.num_types, self.in_size, self.out_size)
+
+    def forward(self, x, x_type, sorted_by_type=False):
+        w = self.get_weight()
+        if sorted_by_type:
+            return ops.segment_mm(x, w, torch.bincount(x_type, minlength=self.num_types), total=x.shape[0])
+        return ops.gather_mm(x, w, idx_b=x_type)
+
+
+class TypedRelGraphConv(nn.Module):
+    """dgl.nn.pytorch.RelGraphConv of DGL >= 0.8 (UPSTREAM): every edge has exactly ONE of num_rels types,
+
+        h_v = act( sum_{e: u -> v} norm_e * x_u W_{etype(e)}  +  x_v W_loop  +  bias ),  then dropout.
+
+    It has a name of its own because RelGraphConv here is the layer of the proteins script (every relation on every edge, the relations
+    the K dimension of one GEMM) and stays exactly as it is.  Parameters are DGL's: `linear_r` (a TypedLinear: `linear_r.W`, `linear_r.coeff`),
+    `h_bias`, `loop_weight`.  The message is ops.gather_mm(feat, W, idx_b=etypes, idx_a=src): the kernel reads the source rows through
+    its row list, no [E, in] gather exists; norm is multiplied into the [E, out] message, the sum is the copy_e / sum g-SpMM."""
+
+    def __init__(self, in_feat, out_feat, num_rels, regularizer=None, num_bases=None, bias=True, activation=None, self_loop=True, dropout=0.0):
+        super(TypedRelGraphConv, self).__init__()
+        self.linear_r = TypedLinear(in_feat, out_feat, num_rels, regularizer, num_bases)
+        self.bias, self.activation, self.self_loop = bias, activation, self_loop
+        if bias:
+            self.h_bias = nn.Parameter(torch.zeros(out_feat))
+        if self_loop:
+            self.loop_weight = nn.Parameter(torch.empty(in_feat, out_feat))
+            nn.init.xavier_uniform_(self.loop_weight, gain=nn.init.calculate_gain("relu"))
+        self.dropout = nn.Dropout(dropout)
+
+    def forward(self, g, feat, etypes, norm=None, presorted=False):
+        """feat [N_src, in]; etypes [E] integer ids in edge-id order; norm [E, 1] or None; presorted: etypes is ascending."""
+        src = g.edges()[0]
+        m = ops.gather_mm(feat, self.linear_r.get_weight(), idx_b=etypes, idx_a=src, sorted_by_type=presorted)
+        if norm is not None:
+            m = m * norm.view(-1, 1)
+        h = ops.copy_e_sum(g, m)
+        if self.bias:
+            h = h + self.h_bias
+        if self.self_loop:
+            h = h + torch.matmul(feat[:g.number_of_dst_nodes()], self.loop_weight)
+        if self.activation:
+            h = self.activation(h)
+        return self.dropout(h)
 
 
 class GraphConv(nn.Module):

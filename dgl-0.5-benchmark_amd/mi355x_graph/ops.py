@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -2791,6 +2791,156 @@ def segment_reduce(seglen, value, reducer="sum", total=None):
     offsets = torch.zeros(seglen.shape[0] + 1, dtype=torch.int64, device=value.device)
     torch.cumsum(seglen.to(value.device).long(), 0, out=offsets[1:])
     return SegmentReduce.apply(reducer, value, offsets, total)
+
+
+# ----------------------------------------------------------------------------- typed linear layers: one weight per row segment
+class SegmentMM(torch.autograd.Function):
+    """out[c_rows[p]] = a[a_rows[p]] x b[seg(p)] over the positions p < n (csrc/segmm.hip).  d a is the same kernel with b transposed,
+    in out's order; `idx_a` (gather_mm: out[i] reads a[idx_a[i]]) then sums it onto a's rows with the stable sort -> row gather ->
+    segment sum of the existing kernels.  d b is the segment form of the tall-skinny weight gradient."""
+
+    @staticmethod
+    def forward(ctx, a, b, offsets, a_rows, c_rows, idx_a, n):
+        out = sparse.backend_for(a).segment_mm(a, b, offsets, n, False, a_rows, c_rows)
+        ctx.save_for_backward(a, b, offsets, a_rows, c_rows, idx_a)
+        ctx.n = n
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        a, b, offsets, a_rows, c_rows, idx_a = ctx.saved_tensors
+        be, d_a, d_b = sparse.backend_for(a), None, None
+        if ctx.needs_input_grad[0]:
+            d_a = be.segment_mm(d_out, b, offsets, ctx.n, True, c_rows, c_rows)
+            if idx_a is not None:
+                order = torch.sort(idx_a, stable=True).indices
+                onto = _offsets_of(torch.bincount(idx_a, minlength=a.shape[0]), a.device)
+                d_a = sparse.segment_reduce_raw(onto, sparse.gather_rows_raw(d_a, order), "sum", total=ctx.n)[0]
+        if ctx.needs_input_grad[1]:
+            d_b = be.segment_mm_grad_b(a, d_out, offsets, ctx.n, int(b.shape[0]), a_rows, c_rows)
+        return d_a, d_b, None, None, None, None, None
+
+
+def _segment_mm_composed(a, b, offsets):
+    """One torch.matmul per segment: the form of segment_mm and gather_mm for CPU tensors, under MGX_TORCH_OPS=1, with
+    config.SEGMENT_MM off and for the operands the kernel declines.  One read-back of the offsets."""
+    ends = offsets.tolist()
+    parts = [torch.matmul(a[beg:end], b[r]) for r, (beg, end) in enumerate(zip(ends[:-1], ends[1:])) if end > beg]
+    return torch.cat(parts, 0) if parts else torch.matmul(a[:0], b.sum(0))  # no rows: [0, M], tied to both operands
+
+
+def _typed_mm_args(who, a, b):
+    _want_tensor(who, "a [n, K]", a, 2)
+    _want_tensor(who, "b [R, K, M]", b, 3)
+    if b.shape[1] != a.shape[1]:
+        raise DGLError("%s: a has %d columns, the matrices of b have %d rows" % (who, a.shape[1], b.shape[1]))
+    if b.device != a.device:
+        raise DGLError("%s: operands on different devices: %s vs %s" % (who, a.device, b.device))
+
+
+def _want_index(who, name, idx, n, device):
+    if not torch.is_tensor(idx) or idx.dim() != 1 or idx.dtype not in (torch.int32, torch.int64) or idx.shape[0] != n:
+        raise DGLError("%s: %s must be a 1-D int32 / int64 tensor of %d entries" % (who, name, n))
+    if idx.device != device:
+        raise DGLError("%s: operands on different devices: %s vs %s" % (who, device, idx.device))
+
+
+def _segment_mm_args(a, b, seglen_a, total):
+    who = "segment_mm"
+    _typed_mm_args(who, a, b)
+    if torch.is_tensor(seglen_a) and seglen_a.dim() == 1 and seglen_a.device.type == "cpu":
+        total = int(seglen_a.sum())  # host lengths: the sum costs no wait
+    _want_seglen(who, seglen_a, a, total)
+    if seglen_a.dtype.is_floating_point or seglen_a.dtype == torch.bool or seglen_a.shape[0] != b.shape[0]:
+        raise DGLError("segment_mm: seglen_a must hold one integer length per matrix of b (%d), got %s %s"
+                       % (b.shape[0], seglen_a.dtype, tuple(seglen_a.shape)))
+    _want_seglen_device(who, seglen_a, a)
+
+
+def _segment_mm_kernel_ok(a, b, idx_a=None):
+    """The kernel's side of segment_mm / gather_mm: its shapes both ways, 32-bit element indices, operands it can read where they lie."""
+    n, K, M = int(a.shape[0] if idx_a is None else idx_a.shape[0]), int(a.shape[1]), int(b.shape[2])
+    return (_device_kernels(a, config.SEGMENT_MM, "segment_mm") and n > 0 and b.shape[0] > 0 and _rows_fit(a) and n * max(K, M) < 2 ** 30
+            and a.stride(1) == 1 and a.stride(0) >= K and _aligned16(a, b) and sparse.backend_for(a).segment_mm_supported(K, M))
+
+
+def segment_mm_fused(a, b, seglen_a, total=None):
+    """True when segment_mm(...) with these operands runs csrc/segmm.hip (else one matmul per segment)."""
+    try:
+        _segment_mm_args(a, b, seglen_a, total)
+        return _segment_mm_kernel_ok(a, b)
+    except DGLError:
+        return False
+
+
+def segment_mm(a, b, seglen_a, total=None):
+    """dgl.ops.segment_mm: out[p] = a[p] x b[r] for the rows p of segment r -- consecutive row segments of the lengths seglen_a, one
+    weight matrix each (the sorted-by-type form of a typed linear layer).
+
+    a [n, K] and b [R, K, M] fp32 (a may be a row-strided column block), seglen_a [R] integer lengths that sum to n, on the host or on
+    a's device; `total`: the row count when the caller knows it (no read-back of device lengths).  Result [n, M]; gradients flow to a
+    and b.  Device operands with M <= 256 and K x M within one 64 KB stage both ways run csrc/segmm.hip (segment_mm_fused): one launch
+    for any R, the segment of every work item found on the device.  Everything else -- CPU tensors under a registered CPU backend,
+    MGX_TORCH_OPS=1, larger shapes, an operand at an odd storage offset, config.SEGMENT_MM = False -- is one torch.matmul per segment."""
+    _segment_mm_args(a, b, seglen_a, total)
+    if seglen_a.device.type == "cpu":
+        total = int(a.shape[0])  # (compared above)
+    offsets, n = _segment_offsets(seglen_a, a, total, "segment_mm")
+    if _segment_mm_kernel_ok(a, b):
+        return SegmentMM.apply(a, b, offsets, None, None, None, n)
+    sparse.backend_for(a)  # no CPU backend: DGLError
+    return _segment_mm_composed(a, b, offsets)
+
+
+def _gather_mm_args(a, b, idx_b, idx_a, num_types_checked):
+    who = "gather_mm"
+    _typed_mm_args(who, a, b)
+    n = int(a.shape[0]) if idx_a is None else (int(idx_a.shape[0]) if torch.is_tensor(idx_a) and idx_a.dim() == 1 else -1)
+    if idx_a is not None:
+        _want_index(who, "idx_a", idx_a, n, a.device)
+    _want_index(who, "idx_b", idx_b, n, a.device)
+    if not num_types_checked and n > 0:  # one host read: an id out of range would index past b (or a)
+        if int(idx_b.min()) < 0 or int(idx_b.max()) >= b.shape[0]:
+            raise DGLError("gather_mm: idx_b must lie in [0, %d)" % b.shape[0])
+        if idx_a is not None and (int(idx_a.min()) < 0 or int(idx_a.max()) >= a.shape[0]):
+            raise DGLError("gather_mm: idx_a must lie in [0, %d)" % a.shape[0])
+
+
+def gather_mm_fused(a, b, idx_b, idx_a=None, num_types_checked=False):
+    """True when gather_mm(...) with these operands runs csrc/segmm.hip (else one matmul per type around row gathers)."""
+    try:
+        _gather_mm_args(a, b, idx_b, idx_a, num_types_checked)
+        return _segment_mm_kernel_ok(a, b, idx_a)
+    except DGLError:
+        return False
+
+
+def gather_mm(a, b, idx_b, idx_a=None, num_types_checked=False, sorted_by_type=False):
+    """dgl.ops.gather_mm: out[i] = a[idx_a[i] if idx_a is given else i] x b[idx_b[i]] -- one weight matrix per row, chosen by id (the
+    unsorted form of a typed linear layer; with idx_a = the source node of an edge, the message of a relational graph convolution).
+
+    a [n_a, K], b [R, K, M] fp32; idx_b (and idx_a) 1-D integer tensors on a's device, one entry per output row.  A stable sort of idx_b
+    and a bincount give the segments; the kernel of segment_mm then reads a[idx_a[perm[p]]] and writes out[perm[p]] through its two row
+    lists, so neither a permuted copy of a nor of the output exists.  sorted_by_type: idx_b is already ascending (no sort).
+    num_types_checked: the caller vouches that the ids lie in [0, R) (and idx_a in [0, n_a)); otherwise they are read back once and an
+    id out of range raises.  The composed form (see segment_mm) gathers, multiplies per type and puts the rows back."""
+    _gather_mm_args(a, b, idx_b, idx_a, num_types_checked)
+    n, R = int(idx_b.shape[0]), int(b.shape[0])
+    idx_b = idx_b.long()
+    idx_a = None if idx_a is None else idx_a.long()
+    perm = None if sorted_by_type else torch.sort(idx_b, stable=True).indices
+    offsets = _offsets_of(torch.bincount(idx_b, minlength=R) if n else idx_b.new_zeros(R), a.device)
+    if _segment_mm_kernel_ok(a, b, idx_a):
+        a_rows = idx_a if perm is None else perm if idx_a is None else idx_a[perm]
+        return SegmentMM.apply(a, b, offsets, a_rows, perm, idx_a, n)
+    sparse.backend_for(a)  # no CPU backend: DGLError
+    rows = a if idx_a is None else a[idx_a]
+    if perm is None:
+        return _segment_mm_composed(rows, b, offsets)
+    inverse = torch.empty_like(perm)
+    inverse[perm] = torch.arange(n, device=perm.device)
+    return _segment_mm_composed(rows[perm], b, offsets)[inverse]
 
 
 # named shortcuts (dgl.ops.copy_u_sum, ...)

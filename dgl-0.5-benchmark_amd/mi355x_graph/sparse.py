@@ -1632,6 +1632,51 @@ class HipBackend(object):
             return out
         return out, (sums if sums is not None else self.column_sum(a2d if a2d.is_contiguous() else a2d.contiguous()))
 
+    # ---- typed linear layers (csrc/segmm.hip): one weight per row segment; nothing here reads `offsets` on the host
+    @classmethod
+    def segment_mm_supported(cls, K, M):
+        """Shapes mgx_segment_mm takes forward ([., K] x [K, M]) and for the input gradient ([., M] x [M, K]); the weight gradient has
+        the forward's limits."""
+        L = _lib.lib()
+        return bool(L.mgx_segment_mm_supported(int(K), int(M)) and L.mgx_segment_mm_supported(int(M), int(K)))
+
+    def _segment_mm_workspace(self, dev, n, R, K, M, grad_b):
+        size = _lib.lib().mgx_segment_mm_workspace(n, R, K, M, 1 if grad_b else 0)
+        if size < 0:
+            _lib.check(_lib.ERR_UNSUPPORTED)
+        return torch.empty(max(size, 8) // 8, dtype=torch.int64, device=dev)
+
+    def segment_mm(self, a2d, b3d, offsets, n, b_transposed=False, a_rows=None, c_rows=None):
+        """out[c_rows[p]] = a2d[a_rows[p]] x b3d[seg(p)] for the positions p < n, seg by offsets [R + 1]; a NULL list is the position itself.
+        b3d [R, K, M], or [R, M, K] with b_transposed.  a2d may be a row-strided column block; lists: contiguous int64 [n], in range and
+        c_rows distinct (not checked).  -> [n, M]."""
+        dev = self._check_dev(a2d, b3d, offsets, a_rows, c_rows)
+        R, K = int(b3d.shape[0]), int(a2d.shape[1])
+        M = int(b3d.shape[1] if b_transposed else b3d.shape[2])
+        if not self._row_walkable(a2d):
+            a2d = a2d.contiguous()
+        b3d = b3d.contiguous()
+        out = torch.empty((n, M), dtype=torch.float32, device=dev)
+        ws = self._segment_mm_workspace(dev, n, R, K, M, False)
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_mm", K=K, M=M, segments=R, rows=int(n), transposed=bool(b_transposed)):
+            _lib.check(_lib.lib().mgx_segment_mm(n, R, K, M, _ptr(a2d), max(int(a2d.stride(0)), K), _ptr(a_rows), _ptr(b3d),
+                                                 1 if b_transposed else 0, _ptr(offsets), _ptr(out), M, _ptr(c_rows),
+                                                 int(config.SEGMENT_MM_ITEM_ROWS), _ptr(ws), _stream(dev)))
+        return out
+
+    def segment_mm_grad_b(self, a2d, d2d, offsets, n, R, a_rows=None, c_rows=None):
+        """[R, K, M]: the sum over the positions p of every segment of a2d[a_rows[p]]^T d2d[c_rows[p]]; zeros for an empty segment."""
+        dev = self._check_dev(a2d, d2d, offsets, a_rows, c_rows)
+        K, M = int(a2d.shape[1]), int(d2d.shape[1])
+        a2d, d2d = (t if self._row_walkable(t) else t.contiguous() for t in (a2d, d2d))
+        out = torch.empty((R, K, M), dtype=torch.float32, device=dev)
+        ws = self._segment_mm_workspace(dev, n, R, K, M, True)
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_mm_grad_b", K=K, M=M, segments=int(R), rows=int(n)):
+            _lib.check(_lib.lib().mgx_segment_mm_grad_b(n, R, K, M, _ptr(a2d), max(int(a2d.stride(0)), K), _ptr(a_rows), _ptr(d2d),
+                                                        max(int(d2d.stride(0)), M), _ptr(c_rows), _ptr(offsets), _ptr(out), _ptr(ws),
+                                                        _stream(dev)))
+        return out
+
     def _rows_gemm_lists(self, a2d, b2d, b_transposed, bias, row_scale, scale_from, split_col, rows, scatter_rows, out2):
         """rows_gemm with a row list in the kernel (mgx_rows_gemm_rows); None when the library has no kernel for the shape."""
         dev = self._check_dev(a2d, b2d, bias, row_scale, rows, scatter_rows, out2)

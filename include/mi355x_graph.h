@@ -694,6 +694,31 @@ int32_t mgx_rows_gemm_relu_dropout(int64_t n, int64_t K, int64_t M, const float*
                                    float* y, int64_t ldy, uint8_t* mask, void* slots /* [n, 128 bytes] or NULL */,
                                    int64_t* overflow_rows /* or NULL */, void* stream);
 
+/* Typed linear layers (dgl.ops.segment_mm / gather_mm, TypedLinear, the per-edge-type RelGraphConv; csrc/segmm.hip): a grouped GEMM
+ * over row segments.  b: R matrices [K, M], contiguous ([R, K, M]); with b_transposed each is read as [M, K] ([R, M, K]: the input
+ * gradient is the same call).  offsets: int64 [R + 1] on the device; the positions offsets[r] .. offsets[r + 1] - 1 of 0 .. n - 1 use b[r].
+ * A segment whose offsets do not satisfy 0 <= offsets[r] <= offsets[r + 1] <= n is skipped.  Row lists (int64 [n] on the device, either
+ * may be NULL = the position itself): position p reads a[a_rows[p]] and writes c[c_rows[p]].
+ *   mgx_segment_mm         c[c_rows[p]] = a[a_rows[p]] x b[seg(p)].  fp32 MFMA; a in 16-byte loads when K % 4 == 0, lda % 4 == 0 and a is
+ *                          16-byte aligned, in dwords otherwise.  item_rows (a positive multiple of 16): the rows of a segment that share
+ *                          one staging of b[r] in LDS.  workspace: mgx_segment_mm_workspace(n, R, K, M, 0) bytes.
+ *   mgx_segment_mm_grad_b  db[r] = sum over the positions p of segment r of a[a_rows[p]]^T dc[c_rows[p]] ([R, K, M], contiguous): every
+ *                          db[r] is written, zeros for a segment without rows.  workspace: mgx_segment_mm_workspace(n, R, K, M, 1) bytes.
+ * PRECONDITIONS, not checked on the device: every list entry lies inside the matrix it indexes and the entries of c_rows of
+ * mgx_segment_mm are distinct.
+ * Supported (mgx_segment_mm_supported(K, M); else MGX_ERR_UNSUPPORTED): M <= 256 and K padded to 16 times M padded to 64 within 16384
+ * floats (one b[r] in 64 KB of LDS); n x max(row strides) < 2^30.  n == 0 or R == 0 launches nothing.  The map from work item to
+ * segment is built on the device from offsets; nothing is read back and the launches depend on n, R, K, M only: capture-safe.
+ * Deterministic: no atomics, partial sums added in item order.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_segment_mm_supported(int64_t K, int64_t M);
+int64_t mgx_segment_mm_workspace(int64_t n, int64_t R, int64_t K, int64_t M, int32_t grad_b);  /* bytes; -1: bad or unsupported sizes */
+int32_t mgx_segment_mm(int64_t n, int64_t R, int64_t K, int64_t M, const float* a, int64_t lda, const int64_t* a_rows /* or NULL */,
+                       const float* b, int32_t b_transposed, const int64_t* offsets, float* c, int64_t ldc,
+                       const int64_t* c_rows /* or NULL */, int64_t item_rows, void* workspace, void* stream);
+int32_t mgx_segment_mm_grad_b(int64_t n, int64_t R, int64_t K, int64_t M, const float* a, int64_t lda, const int64_t* a_rows /* or NULL */,
+                              const float* dc, int64_t lddc, const int64_t* c_rows /* or NULL */, const int64_t* offsets, float* db,
+                              void* workspace, void* stream);
+
 /* y = dropout_p(relu(x)) in one pass (inverted dropout: kept values scaled by 1/(1-p)); the activation between two
  * aggregations (main_dgl_product_sage.py:93-95).  n elements, n % 4 == 0, 16-byte aligned; mask: n/4 bytes, 4 bits per
  * float4 = (x > 0 AND kept), all that backward needs: dx = mask ? dy/(1-p) : 0.  Random bits are a counter-based function
