@@ -77,12 +77,28 @@ class GCNConv(nn.Module):
         return {"m": norm * F.relu(edges.src["x"] + edges.data["w"])}
 
 
+class SetTransformerReadout(nn.Module):
+    """--readout settrans: one SAB encoder layer over the nodes of every graph, then the PMA decoder with one seed vector per graph
+    (dgl.nn.SetTransformerEncoder / SetTransformerDecoder, 4 heads).  Both run ops.segment_mha (csrc/segmha.hip), whose launches depend
+    on the static shapes only: the padded batches of --hipgraph capture it (the ghost nodes are one more segment of their own)."""
+
+    def __init__(self, emb_dim, heads=4):
+        super(SetTransformerReadout, self).__init__()
+        d_head = min(64, max(4, emb_dim // heads // 4 * 4))  # (the kernel of ops.segment_mha takes 4 .. 64 in steps of 4)
+        self.encoder = dgl.nn.SetTransformerEncoder(emb_dim, heads, d_head, 2 * emb_dim, n_layers=1, block_type="sab")
+        self.decoder = dgl.nn.SetTransformerDecoder(emb_dim, heads, d_head, 2 * emb_dim, n_layers=0, k=1)
+
+    def forward(self, graph, feat):
+        return self.decoder(graph, self.encoder(graph, feat))
+
+
 def make_readout(kind, emb_dim, sortpool_k=30):
     """(readout module, width of its output) for --readout: `mean` is the reference's AvgPooling (main_dgl_molhiv_gcn.py:75); `attention`
     is dgl.nn.GlobalAttentionPooling with a Linear(emb_dim, 1) gate; `set2set` is dgl.nn.Set2Set(emb_dim, 3 iterations, 1 LSTM layer),
     whose output is twice as wide.  Both attention readouts run ops.segment_attention (csrc/segattn.hip): one launch each way.
     `sortpool` is dgl.nn.SortPooling(sortpool_k): the k nodes with the largest last (sorted) feature, flattened to k * emb_dim columns
-    (ops.segment_topk, csrc/segtopk.hip); its output shape is static, so the padded batches of --hipgraph capture it as it is."""
+    (ops.segment_topk, csrc/segtopk.hip); its output shape is static, so the padded batches of --hipgraph capture it as it is.
+    `settrans` is SetTransformerReadout: a SAB encoder layer and the PMA decoder with k = 1 (ops.segment_mha, csrc/segmha.hip)."""
     if kind == "mean":
         return dgl.nn.AvgPooling(), emb_dim
     if kind == "attention":
@@ -91,6 +107,8 @@ def make_readout(kind, emb_dim, sortpool_k=30):
         return dgl.nn.Set2Set(emb_dim, n_iters=3, n_layers=1), 2 * emb_dim
     if kind == "sortpool":
         return dgl.nn.SortPooling(sortpool_k), sortpool_k * emb_dim
+    if kind == "settrans":
+        return SetTransformerReadout(emb_dim), emb_dim
     raise ValueError("unknown readout %r" % (kind,))
 
 
@@ -451,9 +469,10 @@ def make_parser():
     p.add_argument("--model", default="gcn", choices=["gcn", "gin", "pna"],
                    help="gcn: the reference's main_dgl_molhiv_gcn.py model; gin: BASELINE.json's wording of config 5; pna: Principal "
                         "Neighbourhood Aggregation (dgl.nn.PNAConv with bond features; eager only)")
-    p.add_argument("--readout", default="mean", choices=["mean", "attention", "set2set", "sortpool"],
+    p.add_argument("--readout", default="mean", choices=["mean", "attention", "set2set", "sortpool", "settrans"],
                    help="mean: the reference's AvgPooling; attention: GlobalAttentionPooling; set2set: Set2Set (3 iterations); "
-                        "sortpool: SortPooling (--sortpool-k nodes per graph)")
+                        "sortpool: SortPooling (--sortpool-k nodes per graph); settrans: SetTransformerEncoder (1 SAB layer) + "
+                        "SetTransformerDecoder (k = 1)")
     p.add_argument("--sortpool-k", type=int, default=30, help="--readout sortpool: nodes kept per graph")
     p.add_argument("--fused-message", action="store_true",
                    help="gcn: run every layer's norm * relu(x_u + w_e) message and its sum as ONE operator (dgl.ops.gine_sum) instead "

@@ -143,6 +143,11 @@ SIGNATURES = {
     "mgx_segment_mm_workspace": (_i64, [_i64, _i64, _i64, _i64, _i32]),
     "mgx_segment_mm": (_i32, [_i64, _i64, _i64, _i64, _fp, _i64, _vp, _fp, _i32, _vp, _fp, _i64, _vp, _i64, _vp, _vp]),
     "mgx_segment_mm_grad_b": (_i32, [_i64, _i64, _i64, _i64, _fp, _i64, _vp, _fp, _i64, _vp, _vp, _fp, _vp, _vp]),
+    "mgx_segment_mha_supported": (_i32, [_i64, _i64, _i64, _i64]),
+    "mgx_segment_mha_workspace": (_i64, [_i64, _i64, _i64, _i64]),
+    "mgx_segment_mha_fwd": (_i32, [_i64, _vp, _vp, _i64, _i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, ctypes.c_float, _fp, _fp, _vp, _vp]),
+    "mgx_segment_mha_bwd": (_i32, [_i64, _vp, _vp, _i64, _i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, ctypes.c_float, _fp, _fp, _fp,
+                                   _fp, _fp, _fp, _vp, _vp]),
     "mgx_column_sum_workspace": (_i64, [_i64]),
     "mgx_column_sum": (_i32, [_i64, _i64, _fp, _fp, _vp, _vp]),
     "mgx_coo_to_csr_workspace": (_i64, [_i64, _i64, _i32]),

@@ -65,6 +65,9 @@ SEGMENT_MM_ITEM_ROWS = 512   # rows of a segment that share one staging of their
                              # 133 Zipf segments over 1 M rows 153 / 145 / 158 / 172 / 184 at 256 / 512 / 1024 / 2048 / 4096; 8 equal segments
                              # 149 / 141 / 134 / 134 / 154; 133 equal segments over 6 M rows 746 / 682 / 660 / 654 / 778 (docs/LOG_segment_mm.md)
 
+# ---- multi-head attention inside row segments (ops.segment_mha, nn.SetTransformerEncoder / SetTransformerDecoder)
+SEGMENT_MHA_FUSED = True  # the varlen attention of csrc/segmha.hip; False: the padded [S, max_len, H, F] composition with torch.softmax
+
 # ---- point clouds (ops.segment_knn, transform.knn_graph / segmented_knn_graph, nn.EdgeConv; ops.segment_fps, ops.segment_ball_query,
 #      transform.fixed_radius_block, nn.PointNetConv)
 KNN_FUSED = True       # csrc/knn.hip: distances and selection in one launch; False: a stable sort of direct-form distances per segment in torch operators

@@ -9,6 +9,7 @@
   AvgPooling / SumPooling / MaxPooling   main_dgl_molhiv_gcn.py:75,93
   GlobalAttentionPooling / Set2Set / WeightAndSum   dgl.nn.pytorch.glob (attention readouts, fused: ops.segment_attention)
   SortPooling   dgl.nn.pytorch.glob (the DGCNN readout: ops.segment_topk)
+  SetTransformerEncoder / SetTransformerDecoder   dgl.nn.pytorch.glob (SAB / ISAB / PMA blocks: ops.segment_mha, csrc/segmha.hip)
   KNNGraph / SegmentedKNNGraph   dgl.nn.pytorch.factory (ops.segment_knn);  EdgeConv   dgl.nn.pytorch.conv (point clouds)
   FarthestPointSampler   dgl.geometry.pytorch (ops.segment_fps);  FixedRadiusNNGraph   the PointNet++ grouping (ops.segment_ball_query);  PointNetConv   its message
   FeaturePropagation   the PointNet++ decoder level (ops.segment_knn_query + u_mul_e / sum: transform.knn_interpolate)
@@ -820,6 +821,163 @@ class Set2Set(nn.Module):
 
     def extra_repr(self):
         return "n_iters={n_iters}".format(**self.__dict__)
+
+
+class MultiHeadAttention(nn.Module):
+    """The attention block of dgl.nn.pytorch.glob's Set Transformer (Lee et al.): bias-free q / k / v projections, multi-head attention of
+    every row of x over the rows of mem IN THE SAME GRAPH (ONE ops.segment_mha call, csrc/segmha.hip), the output projection, then
+    x = LayerNorm(x + out); x = LayerNorm(x + FFN(x)).  Parameters are DGL's: proj_q / proj_k / proj_v / proj_o, ffn, norm_in,
+    norm_inter.  dropouta > 0 in training mode is attention-weight dropout, which the kernel does not have: that call takes the padded
+    composition of ops.segment_mha; in eval mode or with dropouta == 0 it takes the kernel."""
+
+    def __init__(self, d_model, num_heads, d_head, d_ff, dropouth=0., dropouta=0.):
+        super(MultiHeadAttention, self).__init__()
+        self.d_model, self.num_heads, self.d_head, self.d_ff = d_model, num_heads, d_head, d_ff
+        self.proj_q = nn.Linear(d_model, num_heads * d_head, bias=False)
+        self.proj_k = nn.Linear(d_model, num_heads * d_head, bias=False)
+        self.proj_v = nn.Linear(d_model, num_heads * d_head, bias=False)
+        self.proj_o = nn.Linear(num_heads * d_head, d_model, bias=False)
+        self.ffn = nn.Sequential(nn.Linear(d_model, d_ff), nn.ReLU(), nn.Dropout(dropouth), nn.Linear(d_ff, d_model))
+        self.droph = nn.Dropout(dropouth)
+        self.dropa = nn.Dropout(dropouta)
+        self.norm_in = nn.LayerNorm(d_model)
+        self.norm_inter = nn.LayerNorm(d_model)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for p in self.parameters():
+            if p.dim() > 1:
+                nn.init.xavier_uniform_(p)
+
+    def attend(self, q, k, v, lengths_x, lengths_mem, total_x, total_mem):
+        """the call a numerical restatement of this block replaces"""
+        return ops.segment_mha(q, k, v, lengths_x, lengths_mem, q_total=total_x, kv_total=total_mem,
+                               dropout=self.dropa.p if self.training else 0.0)
+
+    def forward(self, x, mem, lengths_x, lengths_mem, total_x=None, total_mem=None):
+        """x [Nx, d_model] in segments of lengths_x, mem [Nm, d_model] in segments of lengths_mem (None: mem is x) -> [Nx, d_model]"""
+        H, D = self.num_heads, self.d_head
+        if lengths_mem is None:  # self-attention: one projection GEMM, its three column blocks read in place by the kernel
+            qkv = F.linear(x, torch.cat([self.proj_q.weight, self.proj_k.weight, self.proj_v.weight], 0))
+            q, k, v = (qkv[:, i * H * D:(i + 1) * H * D].unflatten(1, (H, D)) for i in range(3))
+        else:
+            q = self.proj_q(x).view(-1, H, D)
+            kv = F.linear(mem, torch.cat([self.proj_k.weight, self.proj_v.weight], 0))
+            k, v = (kv[:, i * H * D:(i + 1) * H * D].unflatten(1, (H, D)) for i in range(2))
+        out = self.attend(q, k, v, lengths_x, lengths_mem, total_x, total_mem)
+        x = self.norm_in(x + self.proj_o(out.reshape(-1, H * D)))
+        return self.norm_inter(x + self.ffn(x))
+
+
+class SetAttentionBlock(nn.Module):
+    """SAB(X) = MAB(X, X): every node attends to every node of its graph."""
+
+    def __init__(self, d_model, num_heads, d_head, d_ff, dropouth=0., dropouta=0.):
+        super(SetAttentionBlock, self).__init__()
+        self.mha = MultiHeadAttention(d_model, num_heads, d_head, d_ff, dropouth=dropouth, dropouta=dropouta)
+
+    def forward(self, feat, lengths, total=None):
+        return self.mha(feat, feat, lengths, None, total, total)
+
+
+def _constant_lengths(lengths, count):
+    """`count` rows for every segment of `lengths`, on its device: built without a host read"""
+    return torch.full((lengths.shape[0],), count, dtype=torch.int64, device=lengths.device)
+
+
+class InducedSetAttentionBlock(nn.Module):
+    """ISAB(X) = MAB(X, MAB(I, X)) with m inducing points I per graph: two cross attentions instead of one n^2 self-attention."""
+
+    def __init__(self, m, d_model, num_heads, d_head, d_ff, dropouth=0., dropouta=0.):
+        super(InducedSetAttentionBlock, self).__init__()
+        self.m, self.d_model = m, d_model
+        self.inducing_points = nn.Parameter(torch.empty(m, d_model))
+        self.mha = nn.ModuleList([MultiHeadAttention(d_model, num_heads, d_head, d_ff, dropouth=dropouth, dropouta=dropouta)
+                                  for _ in range(2)])
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.xavier_uniform_(self.inducing_points)
+
+    def forward(self, feat, lengths, total=None):
+        B = lengths.shape[0]
+        query, fixed = self.inducing_points.repeat(B, 1), _constant_lengths(lengths, self.m)
+        memory = self.mha[0](query, feat, fixed, lengths, B * self.m, total)
+        return self.mha[1](feat, memory, lengths, fixed, total, B * self.m)
+
+    def extra_repr(self):
+        return "m={m}".format(**self.__dict__)
+
+
+class PMALayer(nn.Module):
+    """PMA_k(X) = MAB(S, FFN(X)) with k seed vectors S per graph: pooling by multi-head attention."""
+
+    def __init__(self, k, d_model, num_heads, d_head, d_ff, dropouth=0., dropouta=0.):
+        super(PMALayer, self).__init__()
+        self.k, self.d_model = k, d_model
+        self.seed_vectors = nn.Parameter(torch.empty(k, d_model))
+        self.mha = MultiHeadAttention(d_model, num_heads, d_head, d_ff, dropouth=dropouth, dropouta=dropouta)
+        self.ffn = nn.Sequential(nn.Linear(d_model, d_ff), nn.ReLU(), nn.Dropout(dropouth), nn.Linear(d_ff, d_model))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.xavier_uniform_(self.seed_vectors)
+
+    def forward(self, feat, lengths, total=None):
+        B = lengths.shape[0]
+        query = self.seed_vectors.repeat(B, 1)
+        return self.mha(query, self.ffn(feat), _constant_lengths(lengths, self.k), lengths, B * self.k, total)
+
+    def extra_repr(self):
+        return "k={k}".format(**self.__dict__)
+
+
+class SetTransformerEncoder(nn.Module):
+    """dgl.nn.SetTransformerEncoder (Lee et al., Set Transformer): n_layers blocks of `sab` (every node attends to every node of its
+    graph) or `isab` (through m inducing points) over the nodes of a batched graph, [N, d_model] -> [N, d_model].  The attention of
+    every block is ops.segment_mha over the graph's batch_num_nodes: no padded [B, max_n, ...] tensor.  dropouta > 0 in training mode
+    takes that operator's padded composition (attention-weight dropout is not in the kernel, and the composition reads the lengths on
+    the host); eval mode and dropouta == 0 take the kernel."""
+
+    def __init__(self, d_model, n_heads, d_head, d_ff, n_layers=1, block_type='sab', m=None, dropouth=0., dropouta=0.):
+        super(SetTransformerEncoder, self).__init__()
+        self.n_layers, self.block_type, self.m = n_layers, block_type, m
+        if block_type == 'sab':
+            blocks = [SetAttentionBlock(d_model, n_heads, d_head, d_ff, dropouth=dropouth, dropouta=dropouta) for _ in range(n_layers)]
+        elif block_type == 'isab':
+            if m is None:
+                raise KeyError('The number of inducing points is not specified in ISAB block.')
+            blocks = [InducedSetAttentionBlock(m, d_model, n_heads, d_head, d_ff, dropouth=dropouth, dropouta=dropouta)
+                      for _ in range(n_layers)]
+        else:
+            raise KeyError("Unrecognized block type {}: we only support sab/isab".format(block_type))
+        self.layers = nn.ModuleList(blocks)
+
+    def forward(self, graph, feat):
+        lengths, n = graph.batch_num_nodes(), graph.number_of_nodes()
+        for layer in self.layers:
+            feat = layer(feat, lengths, n)
+        return feat
+
+
+class SetTransformerDecoder(nn.Module):
+    """dgl.nn.SetTransformerDecoder: PMA with k seed vectors per graph, then n_layers SAB blocks over the k pooled rows of every graph,
+    [N, d_model] -> [B, k * d_model].  Attention as in SetTransformerEncoder (ops.segment_mha; the same rule for dropouta)."""
+
+    def __init__(self, d_model, num_heads, d_head, d_ff, n_layers, k, dropouth=0., dropouta=0.):
+        super(SetTransformerDecoder, self).__init__()
+        self.n_layers, self.k, self.d_model = n_layers, k, d_model
+        self.pma = PMALayer(k, d_model, num_heads, d_head, d_ff, dropouth=dropouth, dropouta=dropouta)
+        self.layers = nn.ModuleList([SetAttentionBlock(d_model, num_heads, d_head, d_ff, dropouth=dropouth, dropouta=dropouta)
+                                     for _ in range(n_layers)])
+
+    def forward(self, graph, feat):
+        lengths, B = graph.batch_num_nodes(), graph.batch_size
+        feat = self.pma(feat, lengths, graph.number_of_nodes())
+        fixed = _constant_lengths(lengths, self.k)
+        for layer in self.layers:
+            feat = layer(feat, fixed, B * self.k)
+        return feat.view(B, self.k * self.d_model)
 
 
 class SortPooling(nn.Module):

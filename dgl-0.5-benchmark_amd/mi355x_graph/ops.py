@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -2941,6 +2941,129 @@ def gather_mm(a, b, idx_b, idx_a=None, num_types_checked=False, sorted_by_type=F
     inverse = torch.empty_like(perm)
     inverse[perm] = torch.arange(n, device=perm.device)
     return _segment_mm_composed(rows[perm], b, offsets)[inverse]
+
+
+# ----------------------------------------------------------------------------- multi-head attention inside row segments
+class SegmentMHA(torch.autograd.Function):
+    """out[i,h,:] = sum_{j in kv-segment g} softmax_j(scale <q[i,h,:], k[j,h,:]>) v[j,h,:] for the query rows i of segment g: the varlen
+    attention of csrc/segmha.hip, forward in two launches (item scan, kernel) and backward in five (the <out, d_out> pre-pass, then scan + kernel for d_q and for
+    d_k / d_v), the weights rebuilt from lse where they are needed."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_offsets, kv_offsets, scale):
+        out, lse = sparse.backend_for(q).segment_mha_fwd(q_offsets, kv_offsets, q, k, v, scale)
+        ctx.scale = scale
+        ctx.save_for_backward(q, k, v, out, lse, q_offsets, kv_offsets)
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        q, k, v, out, lse, q_offsets, kv_offsets = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_q, d_k, d_v = sparse.backend_for(q).segment_mha_bwd(q_offsets, kv_offsets, q, k, v, ctx.scale, out, lse, d_out.contiguous(),
+                                                              need[0], need[1], need[2])
+        return d_q, d_k, d_v, None, None, None
+
+
+def _segment_mha_composed(q, k, v, q_offsets, kv_offsets, scale, dropout=0.0):
+    """ops.segment_mha as upstream's SetTransformer computes it: queries, keys and values padded to [S, max_len, H, F], a key mask,
+    torch.softmax.  Reads the lengths on the host (not capturable).  dropout: applied to the padded weights (training)."""
+    S, dev = q_offsets.shape[0] - 1, q.device
+    qlen, klen = q_offsets[1:] - q_offsets[:-1], kv_offsets[1:] - kv_offsets[:-1]
+    Lq, Lk = (int(x) for x in torch.stack([qlen.max(), klen.max()]).tolist())
+    seg = torch.arange(S, device=dev)
+
+    def pad(x, offsets, lens, L):
+        sid = torch.repeat_interleave(seg, lens, output_size=x.shape[0])
+        pos = torch.arange(x.shape[0], device=dev) - offsets[sid]
+        return x.new_zeros((S, L) + tuple(x.shape[1:])).index_put((sid, pos), x), sid, pos
+
+    (qp, sid, pos), (kp, _, _), (vp, _, _) = pad(q, q_offsets, qlen, Lq), pad(k, kv_offsets, klen, Lk), pad(v, kv_offsets, klen, Lk)
+    mask = torch.arange(Lk, device=dev)[None, :] < klen[:, None]  # [S, Lk]
+    z = torch.einsum("sqhf,skhf->shqk", qp, kp) * scale
+    # (a segment without keys keeps its finite padded logits: a softmax over -inf alone would put NaN into the gradients)
+    z = z.masked_fill((~mask & (klen > 0)[:, None])[:, None, None, :], float("-inf"))
+    a = torch.where(mask[:, None, None, :], torch.softmax(z, -1), z.new_zeros(()))
+    if dropout > 0.0:
+        a = torch.nn.functional.dropout(a, dropout, True)
+    return torch.einsum("shqk,skhf->sqhf", a, vp)[sid, pos]
+
+
+def _segment_mha_args(q, k, v, q_seglen, kv_seglen, q_total, kv_total):
+    who = "segment_mha"
+    _want_tensor(who, "q [Nq, H, F] and k, v [Nk, H, F]", (q, k, v), 3)
+    if k.device != q.device or v.device != q.device:
+        raise DGLError("%s: operands on different devices: %s vs %s" % (who, q.device, v.device if k.device == q.device else k.device))
+    if k.shape != v.shape or q.shape[1:] != k.shape[1:]:
+        raise DGLError("%s: expected q [Nq, H, F] and k, v [Nk, H, F], got q %s, k %s, v %s" % (who, tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    for name, seglen, x, total in (("q_seglen", q_seglen, q, q_total), ("kv_seglen", kv_seglen, k, kv_total)):
+        if seglen is None and name == "kv_seglen":  # self-attention: the keys are segmented as the queries are
+            if k.shape[0] != q.shape[0]:
+                raise DGLError("%s: without kv_seglen k and v need q's %d rows, got %d" % (who, q.shape[0], k.shape[0]))
+            continue
+        if torch.is_tensor(seglen) and seglen.dim() == 1 and seglen.device.type == "cpu":
+            total = int(seglen.sum())  # host lengths: the sum costs no wait
+        _want_seglen(who, seglen, x, total)
+        if seglen.dtype.is_floating_point or seglen.dtype == torch.bool or seglen.shape[0] != q_seglen.shape[0]:
+            raise DGLError("%s: %s must hold one integer length per segment (%d), got %s %s"
+                           % (who, name, q_seglen.shape[0], seglen.dtype, tuple(seglen.shape)))
+        _want_seglen_device(who, seglen, x)
+
+
+def _segment_mha_kernel_ok(q, k, v, q_seglen):
+    """The kernel's side of segment_mha: F % 4 == 0 within 4 .. 64, operands it can read where they lie (unit inner stride, heads packed,
+    row stride a multiple of 4 floats, 16-byte aligned base), 32-bit element indices."""
+    H, F = int(q.shape[1]), int(q.shape[2])
+    if not _device_kernels(q, config.SEGMENT_MHA_FUSED, "segment_mha_fwd") or q.shape[0] == 0 or q_seglen.shape[0] == 0:
+        return False
+    lds = []
+    for x in (q, k, v):
+        ld = int(x.stride(0)) if x.shape[0] > 1 else H * F
+        if x.shape[0] > 0 and (x.stride(2) != 1 or (H > 1 and x.stride(1) != F) or x.data_ptr() % 16 or x.shape[0] * ld >= 2 ** 30):
+            return False
+        lds.append(ld)
+    return (sparse.backend_for(q).segment_mha_supported(H, F, lds[0], lds[1]) and sparse.backend_for(q).segment_mha_supported(H, F, lds[0], lds[2])
+            and (q.shape[0] // 32 + q_seglen.shape[0] + k.shape[0] // 32 + 1) * H < 2 ** 31)
+
+
+def segment_mha_fused(q, k, v, q_seglen, kv_seglen=None, scale=None, q_total=None, kv_total=None, dropout=0.0):
+    """True when segment_mha(...) with these operands runs csrc/segmha.hip (else the padded composition).  `scale` is accepted for the
+    operator's signature and does not bear on the path."""
+    try:
+        _segment_mha_args(q, k, v, q_seglen, kv_seglen, q_total, kv_total)
+        return dropout == 0.0 and _segment_mha_kernel_ok(q, k, v, q_seglen)
+    except DGLError:
+        return False
+
+
+def segment_mha(q, k, v, q_seglen, kv_seglen=None, scale=None, q_total=None, kv_total=None, dropout=0.0):
+    """Dense multi-head attention inside every segment of a batch: out[i,h,:] = sum_j a[i,j,h] v[j,h,:] over the keys j of the segment
+    of query i, a[i,:,h] = softmax_j(scale * <q[i,h,:], k[j,h,:]>) -- the attention of SetTransformerEncoder / SetTransformerDecoder.
+
+    q [Nq, H, F], k and v [Nk, H, F] fp32 (row-strided views such as the column blocks of one fused QKV projection are taken without a
+    copy); q_seglen [S] integer lengths that sum to Nq and kv_seglen [S] that sum to Nk, on the host or on q's device; kv_seglen=None:
+    self-attention (the keys are segmented as the queries).  Segment g of the queries meets segment g of the keys only.  scale: default
+    F ** -0.5.  q_total / kv_total: the row counts when the caller knows them (no read-back of device lengths).  Result [Nq, H, F];
+    gradients flow to q, k and v.  A query whose key segment is empty gets exactly 0 and passes no gradient; keys whose query segment is
+    empty get zero gradients.
+    Device operands with F % 4 == 0, 4 <= F <= 64, any H, heads packed (stride F), row strides that are multiples of 4 floats and
+    16-byte aligned bases run csrc/segmha.hip (segment_mha_fused): no padded tensor, no [n, n] tensor, capturable.  Everything else -- CPU
+    tensors under a registered CPU backend, MGX_TORCH_OPS=1, other F, an operand at an odd storage offset or with other strides,
+    config.SEGMENT_MHA_FUSED = False, dropout > 0 (attention-weight dropout, training) -- pads to [S, max_len, H, F] with a key mask and
+    uses torch.softmax as upstream does; that form reads the lengths on the host."""
+    _segment_mha_args(q, k, v, q_seglen, kv_seglen, q_total, kv_total)
+    scale = float(q.shape[2]) ** -0.5 if scale is None else float(scale)
+    q_offsets, _ = _segment_offsets(q_seglen, q, q.shape[0] if q_seglen.device.type == "cpu" else q_total, "segment_mha")
+    kv_offsets = q_offsets
+    if kv_seglen is not None:
+        kv_offsets, _ = _segment_offsets(kv_seglen, k, k.shape[0] if kv_seglen.device.type == "cpu" else kv_total, "segment_mha")
+    if dropout == 0.0 and _segment_mha_kernel_ok(q, k, v, q_seglen):
+        return SegmentMHA.apply(q, k, v, q_offsets, kv_offsets, scale)
+    sparse.backend_for(q)  # no CPU backend: DGLError
+    if q.shape[0] == 0 or q_seglen.shape[0] == 0:
+        return q.new_zeros(q.shape) + (q[:0].sum() + k[:0].sum() + v[:0].sum())
+    return _segment_mha_composed(q, k, v, q_offsets, kv_offsets, scale, float(dropout))
 
 
 # named shortcuts (dgl.ops.copy_u_sum, ...)

@@ -1677,6 +1677,49 @@ class HipBackend(object):
                                                         _stream(dev)))
         return out
 
+    # ---- multi-head attention inside row segments (csrc/segmha.hip): nothing here reads the offsets on the host
+    @staticmethod
+    def segment_mha_supported(H, F, ld_q, ld_kv):
+        """Shapes mgx_segment_mha_* takes: F % 4 == 0, 4 <= F <= 64, any H >= 1, row strides % 4 == 0 and >= H * F."""
+        return bool(_lib.lib().mgx_segment_mha_supported(int(H), int(F), int(ld_q), int(ld_kv)))
+
+    def _segment_mha_workspace(self, dev, Nq, Nk, S, H):
+        size = _lib.lib().mgx_segment_mha_workspace(Nq, Nk, S, H)
+        if size < 0:
+            _lib.check(_lib.ERR_UNSUPPORTED)
+        return torch.empty(max(size, 8) // 8, dtype=torch.int64, device=dev)
+
+    def segment_mha_fwd(self, q_offsets, kv_offsets, q3d, k3d, v3d, scale):
+        """q3d [Nq, H, F], k3d / v3d [Nk, H, F] (row-strided views are taken as they are, rows16) -> (out [Nq, H, F], lse [Nq, H])."""
+        dev = self._check_dev(q_offsets, kv_offsets, q3d, k3d, v3d)
+        S, (Nq, H, F), Nk = int(q_offsets.shape[0]) - 1, (int(x) for x in q3d.shape), int(k3d.shape[0])
+        (q, ld_q), (k, ld_k), (v, ld_v) = rows16(q3d), rows16(k3d), rows16(v3d)
+        out = torch.empty((Nq, H, F), dtype=torch.float32, device=dev)
+        lse = torch.empty((Nq, H), dtype=torch.float32, device=dev)
+        ws = self._segment_mha_workspace(dev, Nq, Nk, S, H)
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_mha_fwd", H=H, F=F, segments=S, queries=Nq, keys=Nk):
+            _lib.check(_lib.lib().mgx_segment_mha_fwd(S, _ptr(q_offsets), _ptr(kv_offsets), Nq, Nk, H, F, _ptr(q), ld_q, _ptr(k), ld_k,
+                                                      _ptr(v), ld_v, ctypes.c_float(scale), _ptr(out), _ptr(lse), _ptr(ws), _stream(dev)))
+        return out, lse
+
+    def segment_mha_bwd(self, q_offsets, kv_offsets, q3d, k3d, v3d, scale, out3d, lse2d, d_out3d, need_q=True, need_k=True, need_v=True):
+        """-> (d_q | None, d_k | None, d_v | None), each dense."""
+        dev = self._check_dev(q_offsets, kv_offsets, q3d, k3d, v3d, out3d, lse2d, d_out3d)
+        S, (Nq, H, F), Nk = int(q_offsets.shape[0]) - 1, (int(x) for x in q3d.shape), int(k3d.shape[0])
+        if not (need_q or need_k or need_v):
+            return None, None, None
+        (q, ld_q), (k, ld_k), (v, ld_v) = rows16(q3d), rows16(k3d), rows16(v3d)
+        out3d, d_out3d, lse2d = dense16(out3d), dense16(d_out3d), lse2d.contiguous()
+        d_q = torch.empty((Nq, H, F), dtype=torch.float32, device=dev) if need_q else None
+        d_k = torch.empty((Nk, H, F), dtype=torch.float32, device=dev) if need_k else None
+        d_v = torch.empty((Nk, H, F), dtype=torch.float32, device=dev) if need_v else None
+        ws = self._segment_mha_workspace(dev, Nq, Nk, S, H)
+        with torch.cuda.device(dev), timed_call(dev, kernel="segment_mha_bwd", H=H, F=F, segments=S, queries=Nq, keys=Nk):
+            _lib.check(_lib.lib().mgx_segment_mha_bwd(S, _ptr(q_offsets), _ptr(kv_offsets), Nq, Nk, H, F, _ptr(q), ld_q, _ptr(k), ld_k,
+                                                      _ptr(v), ld_v, ctypes.c_float(scale), _ptr(out3d), _ptr(lse2d), _ptr(d_out3d),
+                                                      _ptr(d_q), _ptr(d_k), _ptr(d_v), _ptr(ws), _stream(dev)))
+        return d_q, d_k, d_v
+
     def _rows_gemm_lists(self, a2d, b2d, b_transposed, bias, row_scale, scale_from, split_col, rows, scatter_rows, out2):
         """rows_gemm with a row list in the kernel (mgx_rows_gemm_rows); None when the library has no kernel for the shape."""
         dev = self._check_dev(a2d, b2d, bias, row_scale, rows, scatter_rows, out2)

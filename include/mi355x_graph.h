@@ -719,6 +719,35 @@ int32_t mgx_segment_mm_grad_b(int64_t n, int64_t R, int64_t K, int64_t M, const 
                               const float* dc, int64_t lddc, const int64_t* c_rows /* or NULL */, const int64_t* offsets, float* db,
                               void* workspace, void* stream);
 
+/* Dense multi-head attention inside every row segment (dgl.nn.SetTransformerEncoder / SetTransformerDecoder, a global attention layer
+ * over a batch of graphs; csrc/segmha.hip): for the query rows i of query-segment g and head h
+ *   out[i,h,:] = sum_{j in kv-segment g} a[i,j,h] v[j,h,:],  a[i,:,h] = softmax_j(scale <q[i,h,:], k[j,h,:]>),  lse[i,h] = m + log(s).
+ * q [Nq, H, F] with row stride ld_q floats, k and v [Nk, H, F] with ld_k / ld_v (the H*F floats of a row contiguous: the column blocks of
+ * one fused QKV projection are read in place); out, d_out, d_q [Nq, H, F] and d_k, d_v [Nk, H, F] contiguous, lse [Nq, H]; all fp32.
+ * q_offsets / kv_offsets: int64 [S + 1] on the device; segment g of the queries meets segment g of the keys and nothing else (the same
+ * array twice: self-attention).  A segment whose own offsets do not satisfy 0 <= beg <= end <= rows gets no work item; one whose
+ * offsets on the other side do not is met as an empty one.
+ *   mgx_segment_mha_fwd  writes out and lse.  workspace: mgx_segment_mha_workspace(Nq, Nk, S, H) bytes.
+ *   mgx_segment_mha_bwd  writes d_q, d_k, d_v (each may be NULL: not computed) from q, k, v, out, lse, d_out; same workspace.
+ * Edge rules: a query whose key segment is empty gets out = 0, lse = 0 and d_q = 0; keys whose query segment is empty get d_k = d_v = 0;
+ * with offsets that partition the rows every row of out, lse, d_q, d_k, d_v is written.  A NaN stays inside its (segment, head).
+ * Supported (mgx_segment_mha_supported(H, F, ld_q, ld_kv); else MGX_ERR_UNSUPPORTED): F % 4 == 0 and 4 <= F <= 64 (padded with zeros to
+ * whole MFMA steps inside the kernel), any H >= 1, row strides that are multiples of 4 floats and at least H*F, q / k / v 16-byte aligned,
+ * rows x row stride < 2^30 (32-bit element indices), (rows / 32 + S) x H < 2^31.  Out of scope: an additive attention bias, masks other
+ * than the segment structure, attention-weight dropout inside the kernel, fp16 / bf16.
+ * fp32 MFMA 16x16x4; no padded tensor, no [n, n] tensor, no edge list.  The map from work item to segment is built on the device from the
+ * offsets; nothing is read back and the launches depend on Nq, Nk, S, H, F only: capture-safe.  Deterministic: no atomics, fixed
+ * summation order, reruns bitwise equal.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_segment_mha_supported(int64_t H, int64_t F, int64_t ld_q, int64_t ld_kv);
+int64_t mgx_segment_mha_workspace(int64_t Nq, int64_t Nk, int64_t S, int64_t H);  /* bytes; -1: bad sizes */
+int32_t mgx_segment_mha_fwd(int64_t S, const int64_t* q_offsets, const int64_t* kv_offsets, int64_t Nq, int64_t Nk, int64_t H, int64_t F,
+                            const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v, int64_t ld_v, float scale,
+                            float* out, float* lse, void* workspace, void* stream);
+int32_t mgx_segment_mha_bwd(int64_t S, const int64_t* q_offsets, const int64_t* kv_offsets, int64_t Nq, int64_t Nk, int64_t H, int64_t F,
+                            const float* q, int64_t ld_q, const float* k, int64_t ld_k, const float* v, int64_t ld_v, float scale,
+                            const float* out, const float* lse, const float* d_out, float* d_q /* or NULL */, float* d_k /* or NULL */,
+                            float* d_v /* or NULL */, void* workspace, void* stream);
+
 /* y = dropout_p(relu(x)) in one pass (inverted dropout: kept values scaled by 1/(1-p)); the activation between two
  * aggregations (main_dgl_product_sage.py:93-95).  n elements, n % 4 == 0, 16-byte aligned; mask: n/4 bytes, 4 bits per
  * float4 = (x > 0 AND kept), all that backward needs: dx = mask ? dy/(1-p) : 0.  Random bits are a counter-based function
