@@ -227,19 +227,7 @@ static bool dot_launch_lph(const DotArgs& a, int lph, bool kv_same, hipStream_t 
 
 template <int MODE>
 static bool dot_launch(const DotArgs& a, int F, bool kv_same, hipStream_t s) {
-  int G = 1;
-  while (G * 4 < a.D) G <<= 1;
-  const int lph = F / 4;
-  switch (G) {
-    case 1: return dot_launch_lph<1, MODE>(a, lph, kv_same, s);
-    case 2: return dot_launch_lph<2, MODE>(a, lph, kv_same, s);
-    case 4: return dot_launch_lph<4, MODE>(a, lph, kv_same, s);
-    case 8: return dot_launch_lph<8, MODE>(a, lph, kv_same, s);
-    case 16: return dot_launch_lph<16, MODE>(a, lph, kv_same, s);
-    case 32: return dot_launch_lph<32, MODE>(a, lph, kv_same, s);
-    case 64: return dot_launch_lph<64, MODE>(a, lph, kv_same, s);
-    default: return false;
-  }
+  return row_walk_dispatch(a.D, [&](auto g) { return dot_launch_lph<decltype(g)::value, MODE>(a, F / 4, kv_same, s); });
 }
 
 static bool dot_shape_ok(int64_t H, int64_t F) {
@@ -362,11 +350,8 @@ extern "C" int32_t mgx_dot_attention_bwd(const mgx_csr* csc, const mgx_spmm_plan
     a.out = out; a.dout = d_out; a.stat = stat; a.stat_w = stat; a.o1 = dq;
     a.partial = (float*)workspace;
     if (!dot_launch<DOT_BWD_DST>(a, (int)F, k == v && k_ld == v_ld, s)) MGX_UNSUPPORTED("mgx_dot_attention_bwd: unsupported head layout");
-    MGX_CHECK_LAUNCH();
-    if (hubs_dst) {
-      hub_rows_sum(csc_plan, (int)D, a.partial, dq, s);
-      MGX_CHECK_LAUNCH();
-    }
+    st = walk_launched(hubs_dst, csc_plan, (int)D, a.partial, dq, s);
+    if (st != MGX_OK) return st;
     note_spmm_kernel("dot_attn_bwd_dst");
   } else if (dk) {  // d k needs t of every destination
     const int64_t n = csc->num_rows * H;

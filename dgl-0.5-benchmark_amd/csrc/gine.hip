@@ -120,13 +120,10 @@ __global__ __launch_bounds__(kBlock) void gine_kernel(const GineArgs a) {
 
 template <bool BWD>
 static bool gine_launch(const GineArgs& a, hipStream_t s) {
-  const dim3 grid((unsigned)a.plan.nblocks), block(kBlock);
-  switch (row_walk_lanes(a.D)) {
-#define MGX_GINE_G(g) case g: hipLaunchKernelGGL((gine_kernel<g, BWD>), grid, block, 0, s, a); return true;
-    MGX_GINE_G(1) MGX_GINE_G(2) MGX_GINE_G(4) MGX_GINE_G(8) MGX_GINE_G(16) MGX_GINE_G(32) MGX_GINE_G(64)
-#undef MGX_GINE_G
-    default: return false;
-  }
+  return row_walk_dispatch(a.D, [&](auto g) {
+    hipLaunchKernelGGL((gine_kernel<decltype(g)::value, BWD>), dim3((unsigned)a.plan.nblocks), dim3(kBlock), 0, s, a);
+    return true;
+  });
 }
 
 static void gine_fill(GineArgs& a, const mgx_csr* csr, const mgx_spmm_plan* plan, int64_t D, const float* x, const float* w,
@@ -165,11 +162,8 @@ extern "C" int32_t mgx_gine_fwd(const mgx_csr* csc, const mgx_spmm_plan* plan, i
   gine_fill(a, csc, plan, D, x, w, scale, workspace);
   a.o = out;
   if (!gine_launch<false>(a, s)) MGX_UNSUPPORTED("mgx_gine_fwd: unsupported width");
-  MGX_CHECK_LAUNCH();
-  if (hubs) {
-    hub_rows_sum(plan, (int)D, a.partial, out, s);
-    MGX_CHECK_LAUNCH();
-  }
+  st = walk_launched(hubs, plan, (int)D, a.partial, out, s);
+  if (st != MGX_OK) return st;
   note_spmm_kernel("gine_fwd");
   return MGX_OK;
 }
@@ -191,11 +185,8 @@ extern "C" int32_t mgx_gine_bwd(const mgx_csr* csr, const mgx_spmm_plan* plan, i
   gine_fill(a, csr, plan, D, x, w, scale, workspace);
   a.dout = d_out; a.o = d_x; a.dw = d_w;
   if (!gine_launch<true>(a, s)) MGX_UNSUPPORTED("mgx_gine_bwd: unsupported width");
-  MGX_CHECK_LAUNCH();
-  if (hubs) {
-    hub_rows_sum(plan, (int)D, a.partial, d_x, s);
-    MGX_CHECK_LAUNCH();
-  }
+  st = walk_launched(hubs, plan, (int)D, a.partial, d_x, s);
+  if (st != MGX_OK) return st;
   note_spmm_kernel("gine_bwd");
   return MGX_OK;
 }

@@ -330,24 +330,18 @@ __global__ __launch_bounds__(kBlock) void multi_agg_bwd_kernel(const MultiAggArg
 
 template <bool MM, bool SQ>
 static bool multi_agg_launch(const MultiAggArgs& a, hipStream_t s) {
-  const dim3 grid((unsigned)a.plan.nblocks), block(kBlock);
-  switch (row_walk_lanes(a.D)) {
-#define MGX_MAGG_G(g) case g: hipLaunchKernelGGL((multi_agg_kernel<g, MM, SQ>), grid, block, 0, s, a); return true;
-    MGX_MAGG_G(1) MGX_MAGG_G(2) MGX_MAGG_G(4) MGX_MAGG_G(8) MGX_MAGG_G(16) MGX_MAGG_G(32) MGX_MAGG_G(64)
-#undef MGX_MAGG_G
-    default: return false;
-  }
+  return row_walk_dispatch(a.D, [&](auto g) {
+    hipLaunchKernelGGL((multi_agg_kernel<decltype(g)::value, MM, SQ>), dim3((unsigned)a.plan.nblocks), dim3(kBlock), 0, s, a);
+    return true;
+  });
 }
 
 template <bool MM>
 static bool multi_agg_bwd_launch(const MultiAggArgs& a, hipStream_t s) {
-  const dim3 grid((unsigned)a.plan.nblocks), block(kBlock);
-  switch (row_walk_lanes(a.D)) {
-#define MGX_MAGG_G(g) case g: hipLaunchKernelGGL((multi_agg_bwd_kernel<g, MM>), grid, block, 0, s, a); return true;
-    MGX_MAGG_G(1) MGX_MAGG_G(2) MGX_MAGG_G(4) MGX_MAGG_G(8) MGX_MAGG_G(16) MGX_MAGG_G(32) MGX_MAGG_G(64)
-#undef MGX_MAGG_G
-    default: return false;
-  }
+  return row_walk_dispatch(a.D, [&](auto g) {
+    hipLaunchKernelGGL((multi_agg_bwd_kernel<decltype(g)::value, MM>), dim3((unsigned)a.plan.nblocks), dim3(kBlock), 0, s, a);
+    return true;
+  });
 }
 
 template <bool MM, bool SQ>
@@ -434,11 +428,8 @@ extern "C" int32_t mgx_multi_agg_bwd(const mgx_csr* csr, const mgx_spmm_plan* pl
   a.partial = (float*)workspace;
   const bool ok = (g_max || g_min) ? multi_agg_bwd_launch<true>(a, s) : multi_agg_bwd_launch<false>(a, s);
   if (!ok) MGX_UNSUPPORTED("mgx_multi_agg_bwd: unsupported width");
-  MGX_CHECK_LAUNCH();
-  if (hubs) {
-    hub_rows_sum(plan, (int)D, a.partial, d_x, s);
-    MGX_CHECK_LAUNCH();
-  }
+  st = walk_launched(hubs, plan, (int)D, a.partial, d_x, s);
+  if (st != MGX_OK) return st;
   note_spmm_kernel("multi_agg_bwd");
   return MGX_OK;
 }

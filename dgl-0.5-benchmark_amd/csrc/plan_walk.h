@@ -2,9 +2,12 @@
 // of an mgx_spmm_plan as kernel arguments, a block's stretch of them and one item's (row, edge range), the slot convention of a
 // split (hub) row, the two kernels that merge a hub row's chunks in slot order, and the plan's argument checks.
 // What stays with each family: its edge loop and lane-group merge, its NaN rule and its statistics layout (dotattn.hip).
-// The row walks with 16-byte lanes (gine.hip, multiagg.hip) also take their supported set and argument checks from here (row_walk_*).
+// The row walks with 16-byte lanes (gine.hip, multiagg.hip) also take their supported set and argument checks from here (row_walk_*),
+// and with dotattn.hip the dispatch on the lane count G and the launch tail (row_walk_dispatch, walk_launched).
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -100,6 +103,17 @@ static inline int row_walk_lanes(int D) {  // the smallest power of two G with 4
   return G;
 }
 
+// launch(std::integral_constant<int, G>) -> bool for the G of a row of D floats (dotattn.hip too); false: no kernel for that G
+template <class Launch>
+static inline bool row_walk_dispatch(int D, Launch launch) {
+  switch (row_walk_lanes(D)) {
+#define MGX_ROW_G(g) case g: return launch(std::integral_constant<int, g>());
+    MGX_ROW_G(1) MGX_ROW_G(2) MGX_ROW_G(4) MGX_ROW_G(8) MGX_ROW_G(16) MGX_ROW_G(32) MGX_ROW_G(64)
+#undef MGX_ROW_G
+    default: return false;
+  }
+}
+
 static inline bool row_walk_width_ok(int64_t D) { return D >= 4 && D % 4 == 0 && D <= 256; }
 
 // gathered rows are addressed by 32-bit byte offsets: every [nodes, D] and [nnz, D] matrix stays below 4 GiB
@@ -152,6 +166,16 @@ static __global__ __launch_bounds__(kBlock) void hub_rows_sum_kernel(const int32
 static inline void hub_rows_sum(const mgx_spmm_plan* plan, int L, const float* partial, float* out, hipStream_t s) {
   hipLaunchKernelGGL(hub_rows_sum_kernel, hub_grid(plan), dim3(kBlock), 0, s, plan->hub_row, plan->hub_slot_ptr, plan->num_hubs, L, partial,
                      out);
+}
+
+// after a walk's launch: report it, then sum the slots of the hub rows when the plan split any (hubs)
+static inline int32_t walk_launched(bool hubs, const mgx_spmm_plan* plan, int L, const float* partial, float* out, hipStream_t s) {
+  MGX_CHECK_LAUNCH();
+  if (hubs) {
+    hub_rows_sum(plan, L, partial, out, s);
+    MGX_CHECK_LAUNCH();
+  }
+  return MGX_OK;
 }
 
 // Online softmax of a hub row: each chunk leaves (running max m_c, sum s_c) per head in pstat [slot, 2H] and an accumulator

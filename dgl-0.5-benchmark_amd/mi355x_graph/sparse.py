@@ -1070,8 +1070,9 @@ class HipBackend(object):
         """Shapes mgx_gine_* takes: D % 4 == 0, 4 <= D <= 256, 32-bit indices, at least one edge, x / w / d_w below 4 GiB each."""
         return bool(_lib.lib().mgx_gine_supported(ctypes.byref(csr.c_struct()), D))
 
-    def _gine_ws(self, plan, D, dev):
-        need = _lib.lib().mgx_gine_workspace(self._plan_ptr(plan), D)
+    def _row_ws(self, workspace_fn, plan, D, dev):
+        """Hub-row workspace of a row walk (workspace_fn: mgx_gine_workspace | mgx_multi_agg_workspace)."""
+        need = workspace_fn(self._plan_ptr(plan), D)
         return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
 
     def gine_fwd(self, csc, x2d, w2d, scale1d):
@@ -1082,7 +1083,7 @@ class HipBackend(object):
         D = int(x2d.shape[1])
         out = torch.empty((csc.num_rows, D), dtype=torch.float32, device=dev)
         plan = csc.plan()
-        ws = self._gine_ws(plan, D, dev)
+        ws = self._row_ws(_lib.lib().mgx_gine_workspace, plan, D, dev)
         with torch.cuda.device(dev), timed_call(dev, kernel="gine_fwd", D=D, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
             _lib.check(_lib.lib().mgx_gine_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), D, _ptr(x2d), _ptr(w2d), _ptr(scale1d),
                                                _ptr(out), _ptr(ws), _stream(dev)))
@@ -1100,7 +1101,7 @@ class HipBackend(object):
         d_x = torch.empty((csr.num_rows, D), dtype=torch.float32, device=dev) if need_x else None
         d_w = torch.empty((csr.nnz, D), dtype=torch.float32, device=dev) if need_w else None
         plan = csr.plan()
-        ws = self._gine_ws(plan, D, dev) if need_x else None
+        ws = self._row_ws(_lib.lib().mgx_gine_workspace, plan, D, dev) if need_x else None
         with torch.cuda.device(dev), timed_call(dev, kernel="gine_bwd", D=D, nnz=csr.nnz, n_src=csr.num_rows, n_dst=csr.num_cols):
             _lib.check(_lib.lib().mgx_gine_bwd(ctypes.byref(csr.c_struct()), self._plan_ptr(plan), D, _ptr(x2d), _ptr(w2d), _ptr(scale1d),
                                                _ptr(d_out2d), _ptr(d_x), _ptr(d_w), _ptr(ws), _stream(dev)))
@@ -1111,10 +1112,6 @@ class HipBackend(object):
     def multi_agg_supported(csr, D):
         """Shapes mgx_multi_agg_* takes: those of gine_supported."""
         return bool(_lib.lib().mgx_multi_agg_supported(ctypes.byref(csr.c_struct()), D))
-
-    def _multi_agg_ws(self, plan, D, dev):
-        need = _lib.lib().mgx_multi_agg_workspace(self._plan_ptr(plan), D)
-        return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
 
     def multi_agg_fwd(self, csc, x2d, w2d, aggregators, eps):
         """x2d [n_src, D], w2d [E, D] by edge id | None (any layout: what the kernels cannot read in place is copied, dense16) ->
@@ -1129,7 +1126,7 @@ class HipBackend(object):
         arg_min = torch.empty((csc.num_rows, D), dtype=torch.int32, device=dev) if "min" in block else None
         stats = torch.empty((csc.num_rows, 2, D), dtype=torch.float32, device=dev) if ("var" in block or "std" in block) else None
         plan = csc.plan()
-        ws = self._multi_agg_ws(plan, D, dev)
+        ws = self._row_ws(_lib.lib().mgx_multi_agg_workspace, plan, D, dev)
         with torch.cuda.device(dev), timed_call(dev, kernel="multi_agg_fwd", D=D, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
             _lib.check(_lib.lib().mgx_multi_agg_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), D, _ptr(x2d), _ptr(w2d),
                                                     ctypes.c_float(eps), *[block.get(n) for n in ("sum", "mean", "var", "std", "max", "min")],
@@ -1147,7 +1144,8 @@ class HipBackend(object):
         d_x = torch.empty((csr.num_rows, D), dtype=torch.float32, device=dev) if need_x else None
         d_w = torch.empty((csr.nnz, D), dtype=torch.float32, device=dev) if need_w else None
         plan = csr.plan()
-        ws = self._gine_ws(plan, D, dev) if need_x else None   # [slots, D] partial rows of d x
+        # the backward leaves one [D] partial row of d x per slot, as gine's walks do: mgx_gine_workspace is the size of [slots, D]
+        ws = self._row_ws(_lib.lib().mgx_gine_workspace, plan, D, dev) if need_x else None
         with torch.cuda.device(dev), timed_call(dev, kernel="multi_agg_bwd", D=D, nnz=csr.nnz, n_src=csr.num_rows, n_dst=csr.num_cols):
             _lib.check(_lib.lib().mgx_multi_agg_bwd(ctypes.byref(csr.c_struct()), self._plan_ptr(plan), D, _ptr(x2d), _ptr(w2d), _ptr(A2d),
                                                     _ptr(B2d), _ptr(g_max), _ptr(arg_max), _ptr(g_min), _ptr(arg_min), _ptr(d_x), _ptr(d_w),

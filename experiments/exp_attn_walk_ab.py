@@ -1,5 +1,6 @@
-"""Two builds of libmi355x_graph.so in ONE process: the attention walks (csrc/gatfused.hip + gat_tile.inc, csrc/dotattn.hip) of a
-parent build against this tree's, for a change that must not change a bit or a microsecond (the walk skeleton moved to plan_walk.h).
+"""Two builds of libmi355x_graph.so in ONE process: the plan-driven walks of a parent build against this tree's, for a change that
+must not change a bit or a microsecond (shared walk code moved to plan_walk.h).  --families attn: csrc/gatfused.hip + gat_tile.inc,
+csrc/dotattn.hip; row: csrc/gine.hip, csrc/multiagg.hip (row_walk_bits, row_walk_speed).
 
   bits    mgx_gat_fused_fwd/bwd (attn_drop 0 and 0.5; the 8 x 16 layer with el formed in the kernel, the ragged 1 x 41 layer),
           mgx_gat_tile_fwd/bwd where a tile plan exists, mgx_dot_attention_fwd/bwd (k, v separate and aliased) on the hub graphs of
@@ -89,11 +90,57 @@ def dot_run(be, csc, csr, q, k, v, up):
     return "dot", [out, fwd_stat, stat, dq, dk, dv]
 
 
+def gine_run(be, csc, csr, x, w, s, up):
+    out = be.gine_fwd(csc, x, w, s)
+    dx, dw = be.gine_bwd(csr, x, w, s, up, True, True)
+    return "gine", [out, dx, dw]
+
+
+def magg_run(be, csc, csr, x, w, aggs, rows):
+    """rows: A, B, g_max, g_min [n_dst, D] of the backward; B goes with mean / var / std, g_max / g_min with their aggregate"""
+    out, arg_max, arg_min, stats = be.multi_agg_fwd(csc, x, w, aggs, 1e-5)
+    A, B, g_max, g_min = rows
+    B = B if set(aggs) & {"mean", "var", "std"} else None
+    dx, dw = be.multi_agg_bwd(csr, x, w, A, B, g_max if arg_max is not None else None, arg_max, g_min if arg_min is not None else None,
+                              arg_min, True, w is not None)
+    return "magg", [t for t in (out, arg_max, arg_min, stats, dx, dw) if t is not None]
+
+
+ROW_DS = (4, 12, 64, 100, 256)
+AGG_SETS = (("sum",), ("mean", "std"), ("max",), ("mean", "max", "min", "std"))  # <MM, SQ> = <0,0>, <0,1>, <1,0>, <1,1>; backward <0>, <0>, <1>, <1>
+
+
+def row_walk_bits(be, compare):
+    """gine_fwd / gine_bwd and multi_agg_fwd / multi_agg_bwd on the hub graph: every output, arg, statistic and gradient"""
+    for split in (64, 256):
+        for D in ROW_DS:
+            n = 400
+            src, dst = hubby_graph(n, 40 * n, seed=D)
+            csc, csr = views(src, dst, n, split, False)
+            assert csc.plan().num_hubs >= 1 and csr.plan().num_hubs >= 1
+            E = len(src)
+            gen = torch.Generator(device=DEV).manual_seed(D)
+            x, up, A, B, gx, gn = (torch.randn(n, D, device=DEV, generator=gen) for _ in range(6))
+            w = torch.randn(E, D, device=DEV, generator=gen)
+            s = torch.randn(E, device=DEV, generator=gen)
+            nan, inf = x.clone(), x.clone()
+            nan[n // 2, D - 1] = float("nan")
+            inf[3, 0], inf[n // 3, D - 1] = float("inf"), -float("inf")
+            for name, xx in (("plain", x), ("NaN", nan), ("+-inf", inf)):
+                for ss in (s, None):
+                    compare("gine n=%d D=%d split=%d %s %s" % (n, D, split, name, "scale" if ss is not None else "no scale"),
+                            lambda: gine_run(be, csc, csr, xx, w, ss, up))
+                for aggs in AGG_SETS:
+                    for ww in (w, None):
+                        compare("magg n=%d D=%d split=%d %s {%s} %s" % (n, D, split, name, ",".join(aggs), "w" if ww is not None else "no w"),
+                                lambda: magg_run(be, csc, csr, xx, ww, aggs, (A, B, gx, gn)))
+
+
 def same_bits(a, b):
-    return all(torch.equal(x.contiguous().view(torch.int32), y.contiguous().view(torch.int32)) for x, y in zip(a, b))
+    return len(a) == len(b) and all(torch.equal(x.contiguous().view(torch.int32), y.contiguous().view(torch.int32)) for x, y in zip(a, b))
 
 
-def bits(builds):
+def bits(builds, families):
     be = sparse.backend_for(torch.zeros(1, device=DEV))
     parent, new = builds["parent"], builds["new"]
     n_cmp = n_bad = 0
@@ -110,7 +157,9 @@ def bits(builds):
         nonfinite = sum(int((~torch.isfinite(x)).sum()) for x in b)
         say("%-66s %-5s %s%s" % (what, form, "bit-identical" if ok else "DIFFERENT", "  (%d non-finite values)" % nonfinite if nonfinite else ""))
 
-    for split in (64, 256):
+    if "row" in families:
+        row_walk_bits(be, compare)
+    for split in (64, 256) if "attn" in families else ():
         for n, H, F in GAT_SHAPES:
             src, dst = hubby_graph(n, 40 * n, seed=H * 100 + F)
             gen = torch.Generator(device=DEV).manual_seed(H + F)
@@ -154,6 +203,28 @@ def bits(builds):
     return n_bad
 
 
+def row_walk_speed(be, row):
+    """the molhiv-sized and ppa-sized batches of gine_bench.py / pna_bench.py, at widths that select the lane counts G = 2 .. 64"""
+    from gine_bench import shapes
+    for name, bg in shapes():
+        if name not in ("molhiv-2048", "ppa-32"):
+            continue
+        g = bg.int().formats(["csr", "csc"]).to(DEV)
+        csc, csr, n, E = g._index.csc(), g._index.csr(), g.number_of_nodes(), g.number_of_edges()
+        for D in (8, 16, 64, 128, 256):
+            gen = torch.Generator(device=DEV).manual_seed(D)
+            x, up, A, B, gx, gn = (torch.randn(n, D, device=DEV, generator=gen) for _ in range(6))
+            w = torch.randn(E, D, device=DEV, generator=gen)
+            row("gine %s D=%d forward" % (name, D), lambda: be.gine_fwd(csc, x, w, None))
+            row("gine %s D=%d backward" % (name, D), lambda: be.gine_bwd(csr, x, w, None, up, True, True))
+            for aggs in ((("mean", "max", "min", "std"), ("sum",), ("max",)) if D in (64, 256) else ()):
+                out, arg_max, arg_min, stats = be.multi_agg_fwd(csc, x, w, aggs, 1e-5)
+                row("magg %s D=%d {%s} forward" % (name, D, ",".join(aggs)), lambda: be.multi_agg_fwd(csc, x, w, aggs, 1e-5))
+                row("magg %s D=%d {%s} backward" % (name, D, ",".join(aggs)),
+                    lambda: be.multi_agg_bwd(csr, x, w, A, B if "mean" in aggs else None, gx if arg_max is not None else None, arg_max,
+                                             gn if arg_min is not None else None, arg_min, True, True))
+
+
 def timed(fns, rounds, reps):
     """fns: {build: callable}; 3 warm-up calls each, then `rounds` rounds in which the builds alternate call by call for `reps` calls
     each -> {build: [the median of every round]} in ms"""
@@ -178,7 +249,7 @@ def timed(fns, rounds, reps):
     return res
 
 
-def speed(builds, rounds, reps, scale):
+def speed(builds, rounds, reps, scale, families):
     """Per row: every build's median over its rounds' medians [the least .. the largest round median].  The parents' spread is the range
     of the 2 x rounds round medians of the two loads of the parent; the new build fails a row when its median lies above that range."""
     be = sparse.backend_for(torch.zeros(1, device=DEV))
@@ -187,7 +258,7 @@ def speed(builds, rounds, reps, scale):
     os.environ.pop("MGX_GAT_TILE", None)
     config.HUB_SPLIT = 256
     slow = 0
-    say("%-50s %-26s %-26s %-26s %s" % ("call (ms; %d rounds of %d calls, builds alternate)" % (rounds, reps), "parent", "parent again", "new",
+    say("%-50s %-29s %-29s %-29s %s" % ("call (ms; %d rounds of %d calls, builds alternate)" % (rounds, reps), "parent", "parent again", "new",
                                         "parents' spread, verdict"))
 
     def row(what, make):
@@ -200,11 +271,15 @@ def speed(builds, rounds, reps, scale):
         lo, hi = min(both), max(both)
         nw = sorted(t["new"])[rounds // 2]
         slow += nw > hi
-        cells = ("%7.3f [%7.3f .. %7.3f]" % (sorted(t[k])[rounds // 2], min(t[k]), max(t[k])) for k in ("parent", "parent again", "new"))
-        say("%-50s %-26s %-26s %-26s [%.3f .. %.3f] %s" % (what, *cells, lo, hi, "within" if nw <= hi else "SLOWER: %.3f above" % (nw - hi)))
+        cells = ("%7.4f [%7.4f .. %7.4f]" % (sorted(t[k])[rounds // 2], min(t[k]), max(t[k])) for k in ("parent", "parent again", "new"))
+        say("%-50s %-29s %-29s %-29s [%.4f .. %.4f] %s" % (what, *cells, lo, hi, "within" if nw <= hi else "SLOWER: %.4f above" % (nw - hi)))
 
-    cases = [("arxiv", sh, "dot") for sh in ((1, 16), (8, 16), (4, 64))] + [("reddit-small", sh, "dot") for sh in ((1, 16), (8, 16), (4, 64))]
-    cases += [("reddit", (1, 16), "gat"), ("reddit", (1, 41), "gat")]
+    if "row" in families:
+        row_walk_speed(be, row)
+    cases = []
+    if "attn" in families:
+        cases = [("arxiv", sh, "dot") for sh in ((1, 16), (8, 16), (4, 64))] + [("reddit-small", sh, "dot") for sh in ((1, 16), (8, 16), (4, 64))]
+        cases += [("reddit", (1, 16), "gat"), ("reddit", (1, 41), "gat")]
     graphs = {}
     for name, (H, F), fam in cases:
         if name not in graphs:
@@ -246,6 +321,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=20, help="calls of every build per round")
     ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--families", default="attn,row", help="attn: gat / dot; row: gine / multi_agg")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -258,9 +334,9 @@ def main():
     say("experiments/exp_attn_walk_ab.py -- device '%s' (%s, %d CUs)" % (prop.name, getattr(prop, "gcnArchName", "?"), prop.multi_processor_count))
     bad = 0
     if args.mode in ("bits", "both"):
-        bad += bits(builds)
+        bad += bits(builds, args.families.split(","))
     if args.mode in ("speed", "both"):
-        bad += speed(builds, max(args.rounds, 3), max(args.reps, 10), args.scale)
+        bad += speed(builds, max(args.rounds, 3), max(args.reps, 10), args.scale, args.families.split(","))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:

@@ -90,7 +90,17 @@ def hub_graph():
     return src, dst, 200, 200
 
 
-GRAPHS = {"small": small_graph, "hubby": hub_graph}
+def degrees_graph():
+    """300 nodes: destinations 0..3 of in-degree 1, 63, 64, 65 and sources 10..13 of out-degree 1, 63, 64, 65 (one 64-edge chunk
+    of the row walks less one, full, plus one), every other end among the nodes 20..299"""
+    rng = np.random.default_rng(29)
+    degs = (1, 63, 64, 65)
+    src = [rng.integers(20, 300, d) for d in degs] + [np.full(d, 10 + i) for i, d in enumerate(degs)]
+    dst = [np.full(d, i) for i, d in enumerate(degs)] + [rng.integers(20, 300, d) for d in degs]
+    return np.concatenate(src).astype(np.int64), np.concatenate(dst).astype(np.int64), 300, 300
+
+
+GRAPHS = {"small": small_graph, "hubby": hub_graph, "degrees": degrees_graph}
 
 
 def operands(n_src, n_dst, E, D, seed):
@@ -627,8 +637,8 @@ def integer_operands(n_src, n_dst, E, D, seed):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("with_w", [False, True])
-@pytest.mark.parametrize("D", [4, 64])
-@pytest.mark.parametrize("name", ["small", "hubby"])
+@pytest.mark.parametrize("D", [4, 12, 64])
+@pytest.mark.parametrize("name", ["small", "hubby", "degrees"])
 def test_exact_arithmetic_is_bitwise(name, D, with_w):
     """integers in [-8, 8]: every message, square and partial sum is exact in fp32 in any order, so a lost, doubled or misrouted edge,
     arg or edge id changes a value and anything else is bitwise the restatement"""
