@@ -32,7 +32,7 @@ import torch.nn.functional as F  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dgl  # noqa: E402
 import dgl.function as fn  # noqa: E402
-from dgl.nn.pytorch import GATConv, DotGatConv, Linear, BatchNorm1d, RelGraphConv  # noqa: E402
+from dgl.nn.pytorch import GATConv, DotGatConv, GATv2Conv, Linear, BatchNorm1d, RelGraphConv  # noqa: E402
 from mi355x_graph import config, ops  # noqa: E402
 from dgl.utils import expand_as_pair  # noqa: E402
 
@@ -213,6 +213,34 @@ class DotGAT(nn.Module):
         return self.gat_layers[-1](self.g, self.feat_drop(h)).mean(1)
 
 
+class GATv2(nn.Module):
+    """The GAT stack above over dgl.nn GATv2Conv layers: same heads, hidden size, activation and feat_drop.  attn_drop stays 0: a
+    dropping layer runs the operators one by one (nn.GATv2Conv), and their [E, H, F] tensors are what this model is here to avoid."""
+
+    def __init__(self, g, num_layers, in_feats, num_hidden, num_classes, heads, activation=F.elu, feat_drop=0.0, negative_slope=0.2):
+        super(GATv2, self).__init__()
+        self.num_layers, self.g = num_layers, g
+        widths = [in_feats] + [num_hidden * heads[l] for l in range(num_layers - 1)]
+        self.gat_layers = nn.ModuleList()
+        for l in range(num_layers - 1):
+            self.gat_layers.append(GATv2Conv(widths[l], num_hidden, heads[l], feat_drop if l > 0 else 0., 0., negative_slope,
+                                             activation=activation))
+        # the output layer is as wide as the next width the fused walk takes (41 classes -> 64); forward() drops the extra columns
+        self.num_classes = num_classes
+        out_width = min([w for w in (4, 8, 16, 32, 64) if w >= num_classes] or [num_classes])
+        self.gat_layers.append(GATv2Conv(widths[-1], out_width, heads[-1], feat_drop, 0., negative_slope, activation=None))
+
+    def forward(self, h):
+        for l in range(self.num_layers - 1):
+            h = self.gat_layers[l](self.g, h).flatten(1)
+        return self.gat_layers[-1](self.g, h).mean(1)[:, :self.num_classes]
+
+
+def gatv2_composed_bytes(num_edges, heads, num_hidden, num_classes):
+    """Bytes of ONE [E, H, F] fp32 tensor of the widest layer: what the operators one by one keep (several times over) and the fused walk does not."""
+    return max(4 * num_edges * h * f for h, f in zip(heads, [num_hidden] * (len(heads) - 1) + [num_classes]))
+
+
 def sage_train_step(model, g, feats, labels, train_idx, optimizer):
     """main_dgl_product_sage.py:101-110."""
     model.train()
@@ -336,8 +364,8 @@ def spmm_edges_per_epoch(num_layers, num_edges):
 
 def main():
     p = argparse.ArgumentParser("full-graph training on the MI355X message-passing backend")
-    p.add_argument("--model", default="sage", choices=["sage", "gat", "dotgat", "rgcn"],
-                   help="dotgat: the GAT stack with DotGatConv layers (dropout = feat_drop only); rgcn: the edge-weighted relational model on the proteins stand-in (--dataset is not read)")
+    p.add_argument("--model", default="sage", choices=["sage", "gat", "dotgat", "gatv2", "rgcn"],
+                   help="dotgat / gatv2: the GAT stack with DotGatConv / GATv2Conv layers (dropout = feat_drop only); rgcn: the edge-weighted relational model on the proteins stand-in (--dataset is not read)")
     p.add_argument("--dataset", default="products")
     p.add_argument("--epochs", type=int, default=10)
     p.add_argument("--scale", type=float, default=1.0)
@@ -397,6 +425,12 @@ def main():
             print("DotGAT: %d layers, heads %s, hidden %d, feat_drop = %g" % (gcfg["num_layers"], heads, gcfg["hidden"], gcfg["dropout"]))
             model = DotGAT(g, gcfg["num_layers"], data.features.shape[1], gcfg["hidden"], data.num_classes, heads,
                            feat_drop=gcfg["dropout"]).to(device)
+        elif args.model == "gatv2":
+            print("GATv2: %d layers, heads %s, hidden %d, feat_drop = %g" % (gcfg["num_layers"], heads, gcfg["hidden"], gcfg["dropout"]))
+            print("GATv2: one [E, H, F] tensor of the composed operators would take %.1f GB here; the fused walks keep none"
+                  % (gatv2_composed_bytes(g.number_of_edges(), heads, gcfg["hidden"], data.num_classes) / 1e9))
+            model = GATv2(g, gcfg["num_layers"], data.features.shape[1], gcfg["hidden"], data.num_classes, heads,
+                          feat_drop=gcfg["dropout"]).to(device)
         else:
             print("GAT: %d layers, heads %s, hidden %d, feat_drop = attn_drop = %g" % (gcfg["num_layers"], heads, gcfg["hidden"], gcfg["dropout"]))
             model = GAT(g, gcfg["num_layers"], data.features.shape[1], gcfg["hidden"], data.num_classes, heads,

@@ -89,6 +89,11 @@ SIGNATURES = {
     "mgx_dot_attention_fwd": (_i32, [_csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, ctypes.c_float, _fp, _fp, _vp, _vp]),
     "mgx_dot_attention_bwd": (_i32, [_csr_p, _vp, _csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, ctypes.c_float, _fp, _fp, _fp,
                                      _fp, _fp, _fp, _vp, _vp]),
+    "mgx_gatv2_supported": (_i32, [_csr_p, _i64, _i64]),
+    "mgx_gatv2_workspace": (_i64, [_vp, _csr_p, _i64, _i64]),
+    "mgx_gatv2_fwd": (_i32, [_csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, ctypes.c_float, _fp, _fp, _vp, _vp]),
+    "mgx_gatv2_bwd": (_i32, [_csr_p, _vp, _csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp,
+                             _vp, _vp]),
     "mgx_gine_supported": (_i32, [_csr_p, _i64]),
     "mgx_gine_workspace": (_i64, [_vp, _i64]),
     "mgx_gine_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _vp, _vp]),

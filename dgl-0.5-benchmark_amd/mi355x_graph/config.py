@@ -39,6 +39,9 @@ GAT_PACK = True            # one packed gather operand per node for the fused wa
 
 # ---- dot-product attention (ops.dot_attention, nn.DotGatConv)
 DOT_ATTENTION_FUSED = True  # the fused walks of csrc/dotattn.hip; False: u_dot_v -> edge_softmax -> u_mul_e/sum through the existing operators
+
+# ---- GATv2 attention (ops.gatv2_attention, nn.GATv2Conv)
+GATV2_FUSED = True  # the fused walks of csrc/gatv2.hip; False: u_add_v -> leaky_relu -> (. * attn).sum(-1) -> edge_softmax -> u_mul_e/sum, an [E, H, F] tensor each way
 # ---- relu(x_u + w_e) messages summed per destination (ops.gine_sum, nn.GINEConv, graph_classification.py --fused-message)
 GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> relu -> mul -> copy_e/sum through the existing operators
 # ---- sum / mean / var / std / max / min of the same messages at once (ops.multi_aggregate, nn.PNAConv, graph_classification.py --model pna)

@@ -1,6 +1,7 @@
 """dgl.nn.pytorch modules used by the benchmark scripts, written against this backend's ops:
   GATConv    main_dgl_reddit_gat.py:10,31-55 (u_add_v SDDMM + fused edge_softmax + u_mul_e/sum SpMM)
   DotGatConv dgl.nn.pytorch.DotGatConv (u_dot_v SDDMM + edge_softmax + u_mul_e/sum SpMM, fused: ops.dot_attention)
+  GATv2Conv  dgl.nn.pytorch.GATv2Conv (u_add_v -> leaky_relu -> feature sum -> edge_softmax -> u_mul_e/sum, fused: ops.gatv2_attention)
   GINEConv   dgl.nn.pytorch.GINEConv (sum of relu(h_u + e_uv) messages, fused: ops.gine_sum)
   PNAConv    dgl.nn.pytorch.PNAConv (mean / max / min / std ... of one message per edge, fused: ops.multi_aggregate)
   TypedLinear / TypedRelGraphConv   dgl.nn.pytorch.TypedLinear and DGL >= 0.8's RelGraphConv (one weight per type: ops.segment_mm / gather_mm)
@@ -281,6 +282,98 @@ class DotGatConv(nn.Module):
                 return ops.dot_attention(graph, feat_dst, feat_src, feat_src, scale)
             a = ops.edge_softmax(graph, ops.gsddmm(graph, "dot", feat_src, feat_dst, "u", "v") * scale)
             return ops.gspmm(graph, "mul", "sum", feat_src, a), a
+
+
+class GATv2Conv(nn.Module):
+    """dgl.nn.pytorch.GATv2Conv (Brody et al., "How Attentive are Graph Attention Networks?"): the logit of an edge applies the
+    non-linearity BEFORE the reduction over features, e_uv = attn . leaky_relu(W_src h_u + W_dst h_v), and the messages are W_src h_u.
+    Parameters as in DGL: fc_src, fc_dst (share_weights: fc_dst IS fc_src and has no entry of its own in the state dict), attn
+    [1, H, F], res_fc; `bias` gives the projections (and a projecting res_fc) their bias vectors, as in DGL.  The block between the
+    projections and the result is ops.gatv2_attention (csrc/gatv2.hip when it takes the shape: no [E, H, F] tensor);
+    get_attention=True, or attn_drop > 0 in training, runs the operators one by one -- the fused walk has no dropout stream."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0., attn_drop=0., negative_slope=0.2, residual=False, activation=None,
+                 allow_zero_in_degree=False, bias=True, share_weights=False):
+        super(GATv2Conv, self).__init__()
+        self._num_heads = num_heads
+        self._in_src_feats, self._in_dst_feats = expand_as_pair(in_feats)
+        self._out_feats = out_feats
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.share_weights = share_weights
+        if share_weights and self._in_src_feats != self._in_dst_feats:
+            raise DGLError("GATv2Conv: share_weights needs source and destination inputs of one width, got %d and %d"
+                           % (self._in_src_feats, self._in_dst_feats))
+        self.fc_src = Linear(self._in_src_feats, out_feats * num_heads, bias=bias)
+        if not share_weights:
+            self.fc_dst = Linear(self._in_dst_feats, out_feats * num_heads, bias=bias)
+        self.attn = nn.Parameter(torch.FloatTensor(size=(1, num_heads, out_feats)))
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.leaky_relu = nn.LeakyReLU(negative_slope)
+        if residual:
+            if self._in_dst_feats != out_feats * num_heads:
+                self.res_fc = Linear(self._in_dst_feats, num_heads * out_feats, bias=bias)
+            else:
+                self.res_fc = Identity()
+        else:
+            self.register_buffer("res_fc", None)
+        self.activation = activation
+        self.reset_parameters()
+
+    def __getattr__(self, name):
+        if name == "fc_dst" and self.__dict__.get("share_weights"):  # one module under two names, one entry in the state dict
+            return self.fc_src
+        return super(GATv2Conv, self).__getattr__(name)
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        for fc in (self.fc_src, self.fc_dst, self.res_fc):
+            if isinstance(fc, nn.Linear):
+                nn.init.xavier_normal_(fc.weight, gain=gain)
+                if fc.bias is not None:
+                    nn.init.constant_(fc.bias, 0)
+        nn.init.xavier_normal_(self.attn, gain=gain)
+
+    def set_allow_zero_in_degree(self, set_value):
+        self._allow_zero_in_degree = set_value
+
+    def forward(self, graph, feat, get_attention=False):
+        with graph.local_scope():
+            if not self._allow_zero_in_degree:
+                if _has_zero_in_degree(graph):
+                    raise DGLError(
+                        "There are 0-in-degree nodes in the graph, output for those nodes will be invalid. "
+                        "This is harmful for some applications, causing silent performance regression. "
+                        "Adding self-loop on the input graph by calling `g = dgl.add_self_loop(g)` will resolve "
+                        "the issue. Setting ``allow_zero_in_degree`` to be `True` when constructing this module "
+                        "will suppress the check and let the code run.")
+            H, Fo = self._num_heads, self._out_feats
+            if isinstance(feat, tuple):
+                h_src, h_dst = self.feat_drop(feat[0]), self.feat_drop(feat[1])
+                feat_src = self.fc_src(h_src).view(-1, H, Fo)
+                feat_dst = self.fc_dst(h_dst).view(-1, H, Fo)
+            else:
+                h_src = h_dst = self.feat_drop(feat)
+                if graph.is_block:
+                    h_dst = h_src[:graph.number_of_dst_nodes()]
+                feat_src = self.fc_src(h_src).view(-1, H, Fo)
+                if self.share_weights:  # one tensor in both roles (on a block: its leading rows)
+                    feat_dst = feat_src if h_dst is h_src else feat_src[:h_dst.shape[0]]
+                else:
+                    feat_dst = self.fc_dst(h_dst).view(-1, H, Fo)
+            slope = self.leaky_relu.negative_slope
+            if not get_attention and not (self.training and self.attn_drop.p > 0.0):
+                a = None
+                rst = ops.gatv2_attention(graph, feat_src, feat_dst, self.attn, slope)
+            else:
+                e = self.leaky_relu(ops.gsddmm(graph, "add", feat_src, feat_dst, "u", "v"))      # [E, H, F]
+                a = self.attn_drop(ops.edge_softmax(graph, (e * self.attn).sum(dim=-1, keepdim=True)))
+                rst = ops.gspmm(graph, "mul", "sum", feat_src, a)
+            if self.res_fc is not None:
+                rst = rst + self.res_fc(h_dst).view(h_dst.shape[0], -1, Fo)
+            if self.activation:
+                rst = self.activation(rst)
+            return (rst, a) if get_attention else rst
 
 
 class SAGEConv(nn.Module):

@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -494,6 +494,82 @@ def dot_attention(graph, q, k, v, scale=None):
     if not _dot_attention_kernel_ok(gidx, q, k, v):
         return gspmm(gidx, "mul", "sum", v, edge_softmax(gidx, gsddmm(gidx, "dot", k, q, "u", "v") * scale))
     return DotAttention.apply(gidx, q, k, v, scale)
+
+
+class GATv2Attention(torch.autograd.Function):
+    """out[v,h,:] = sum_e softmax_{e->v}(sum_f attn[h,f] leaky_relu(fs[u,h,f] + fd[v,h,f]))[e,h] fs[u,h,:] -- dgl.nn.GATv2Conv's whole
+    message-passing block in one walk forward and two backward, with no E-sized tensor (the operators one by one keep [E, H, F] each
+    way): the attention of an edge is rebuilt from the per-row statistics where it is needed (csrc/gatv2.hip)."""
+
+    @staticmethod
+    def forward(ctx, gidx, fs, fd, attn, slope):
+        # fs and fd that are one tensor -- or two views of the same memory -- are one operand (share_weights on a square graph)
+        same = fs is fd or (fs.data_ptr() == fd.data_ptr() and fs.stride() == fd.stride() and fs.shape == fd.shape)
+        H, Fd = int(fs.shape[1]), int(fs.shape[2])
+        out, stat = sparse.backend_for(fs).gatv2_fwd(gidx.csc(), fs, fs if same else fd, attn.reshape(H, Fd), float(slope))
+        ctx.backward_cache = gidx, float(slope), same
+        ctx.save_for_backward(fs, fd, attn, out, stat)
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        gidx, slope, same = ctx.backward_cache
+        fs, fd, attn, out, stat = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d_fs, d_fd, d_attn = sparse.backend_for(fs).gatv2_bwd(gidx.csc(), gidx.csr(), fs, fs if same else fd,
+                                                              attn.reshape(int(fs.shape[1]), int(fs.shape[2])), slope, out,
+                                                              d_out.contiguous(), stat, need[1], need[2], need[3])
+        return None, d_fs, d_fd, None if d_attn is None else d_attn.view(attn.shape), None
+
+
+def _gatv2_args(graph, feat_src, feat_dst, attn):
+    """The graph index of a gatv2_attention call, or DGLError."""
+    gidx = _gidx(graph)
+    _want_tensor("gatv2_attention", "feat_src [N_src, H, F] and feat_dst [N_dst, H, F]", (feat_src, feat_dst), 3)
+    _want_tensor("gatv2_attention", "attn [H, F] or [1, H, F]", attn, (2, 3))
+    if (feat_src.shape[0] != gidx.num_src or feat_dst.shape[0] != gidx.num_dst or feat_src.shape[1:] != feat_dst.shape[1:]
+            or tuple(attn.shape) not in (tuple(feat_src.shape[1:]), (1,) + tuple(feat_src.shape[1:]))):
+        raise DGLError("gatv2_attention: expected feat_src [%d, H, F], feat_dst [%d, H, F] and attn [H, F] or [1, H, F], got %s, %s and %s"
+                       % (gidx.num_src, gidx.num_dst, tuple(feat_src.shape), tuple(feat_dst.shape), tuple(attn.shape)))
+    return gidx
+
+
+def _gatv2_kernel_ok(gidx, feat_src, feat_dst, attn):
+    if (not _device_kernels(feat_src, config.GATV2_FUSED, "gatv2_fwd") or feat_dst.device != feat_src.device
+            or attn.device != feat_src.device or gidx.num_edges() == 0):
+        return False
+    return sparse.backend_for(feat_src).gatv2_supported(gidx.csc(), int(feat_src.shape[1]), int(feat_src.shape[2]))
+
+
+def gatv2_attention_fused(graph, feat_src, feat_dst, attn):
+    """True when gatv2_attention(graph, feat_src, feat_dst, attn) runs the fused kernels (else it is the operators one by one)."""
+    try:
+        return _gatv2_kernel_ok(_gatv2_args(graph, feat_src, feat_dst, attn), feat_src, feat_dst, attn)
+    except DGLError:
+        return False
+
+
+def _gatv2_composed(gidx, feat_src, feat_dst, attn, negative_slope):
+    """u_add_v -> leaky_relu -> sum over f of (. * attn) -> edge_softmax -> u_mul_e / sum: an [E, H, F] tensor forward and backward."""
+    e = torch.nn.functional.leaky_relu(gsddmm(gidx, "add", feat_src, feat_dst, "u", "v"), negative_slope)
+    z = (e * attn.reshape((1,) + tuple(feat_src.shape[1:]))).sum(dim=-1, keepdim=True)
+    return gspmm(gidx, "mul", "sum", feat_src, edge_softmax(gidx, z))
+
+
+def gatv2_attention(graph, feat_src, feat_dst, attn, negative_slope=0.2):
+    """GATv2 attention over a graph: out[v,h,:] = sum_{e: u->v} a[e,h] feat_src[u,h,:] with
+    a = edge_softmax(sum_f attn[h,f] leaky_relu(feat_src[u,h,f] + feat_dst[v,h,f])).
+
+    feat_src: [N_src, H, F], feat_dst: [N_dst, H, F] (fp32; row-strided views such as the two column blocks of one projection are taken
+    without a copy, and the two may be one tensor), attn: [H, F] or [1, H, F]; result [N_dst, H, F], exactly 0 for destinations without
+    in-edges.  Device operands with F in {4, 8, 16, 32, 64} and H*F <= 256 on an int32 graph run csrc/gatv2.hip (gatv2_attention_fused);
+    everything else -- CPU tensors under a registered CPU backend, MGX_TORCH_OPS=1, 64-bit graphs, config.GATV2_FUSED = False -- takes
+    the same values through gsddmm / edge_softmax / gspmm."""
+    gidx = _gatv2_args(graph, feat_src, feat_dst, attn)
+    if not _gatv2_kernel_ok(gidx, feat_src, feat_dst, attn):
+        return _gatv2_composed(gidx, feat_src, feat_dst, attn, float(negative_slope))
+    return GATv2Attention.apply(gidx, feat_src, feat_dst, attn, float(negative_slope))
 
 
 class GineSum(torch.autograd.Function):

@@ -1064,6 +1064,55 @@ class HipBackend(object):
                                                         _ptr(dv), _ptr(ws), _stream(dev)))
         return dq, dk, dv
 
+    # ---- GATv2 attention (csrc/gatv2.hip)
+    @staticmethod
+    def gatv2_supported(csr, H, F):
+        """Shapes mgx_gatv2_* takes: the set of dot_attention_supported."""
+        return bool(_lib.lib().mgx_gatv2_supported(ctypes.byref(csr.c_struct()), H, F))
+
+    def _gatv2_ws(self, pairs, H, F, dev):
+        """Workspace of a GATv2 call: the hub slots of a plan and the per-workgroup partials of d attn; the largest need of the (plan, csr) pairs."""
+        need = max(_lib.lib().mgx_gatv2_workspace(self._plan_ptr(p), ctypes.byref(c.c_struct()), H, F) for p, c in pairs)
+        return torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+
+    def gatv2_fwd(self, csc, fs3d, fd3d, attn2d, slope):
+        """fs3d [n_src, H, F], fd3d [n_dst, H, F] (row-strided views are taken as they are; fd3d may be fs3d), attn2d [H, F]
+        -> (out [n_dst, H, F], stat [n_dst, H, 4] = (m, 1/S, -, -))."""
+        dev = self._check_dev(csc.indptr, fs3d, fd3d, attn2d)
+        H, F = int(fs3d.shape[1]), int(fs3d.shape[2])
+        fs, fs_ld = self._dot_operand(fs3d)
+        fd, fd_ld = (fs, fs_ld) if fd3d is fs3d else self._dot_operand(fd3d)
+        attn2d = dense16(attn2d)
+        out = torch.empty((csc.num_rows, H, F), dtype=torch.float32, device=dev)
+        stat = torch.empty((csc.num_rows, H, 4), dtype=torch.float32, device=dev)
+        plan = csc.plan()
+        ws = self._gatv2_ws([(plan, csc)], H, F, dev) if plan is not None and plan.num_slots else None  # forward: split rows only
+        with torch.cuda.device(dev), timed_call(dev, kernel="gatv2_fwd", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
+            _lib.check(_lib.lib().mgx_gatv2_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), H, F, _ptr(fs), fs_ld, _ptr(fd), fd_ld,
+                                                _ptr(attn2d), ctypes.c_float(slope), _ptr(out), _ptr(stat), _ptr(ws), _stream(dev)))
+        return out, stat
+
+    def gatv2_bwd(self, csc, csr, fs3d, fd3d, attn2d, slope, out3d, d_out3d, stat, need_fs, need_fd, need_attn):
+        """-> (d_fs | None, d_fd | None, d_attn [H, F] | None), each dense; stat[..., 2] is overwritten with <out, d_out> per head."""
+        dev = self._check_dev(csc.indptr, csr.indptr, fs3d, fd3d, attn2d, out3d, d_out3d, stat)
+        H, F = int(fs3d.shape[1]), int(fs3d.shape[2])
+        if not (need_fs or need_fd or need_attn):
+            return None, None, None
+        fs, fs_ld = self._dot_operand(fs3d)
+        fd, fd_ld = (fs, fs_ld) if fd3d is fs3d else self._dot_operand(fd3d)
+        attn2d, out3d, d_out3d = dense16(attn2d), dense16(out3d), dense16(d_out3d)
+        d_fs = torch.empty((csc.num_cols, H, F), dtype=torch.float32, device=dev) if need_fs else None
+        d_fd = torch.empty((csc.num_rows, H, F), dtype=torch.float32, device=dev) if need_fd else None
+        d_attn = torch.empty((H, F), dtype=torch.float32, device=dev) if need_attn else None
+        p_dst, p_src = csc.plan(), csr.plan()
+        ws = self._gatv2_ws([(p_dst, csc), (p_src, csr)], H, F, dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="gatv2_bwd", H=H, F=F, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
+            _lib.check(_lib.lib().mgx_gatv2_bwd(ctypes.byref(csc.c_struct()), self._plan_ptr(p_dst), ctypes.byref(csr.c_struct()),
+                                                self._plan_ptr(p_src), H, F, _ptr(fs), fs_ld, _ptr(fd), fd_ld, _ptr(attn2d),
+                                                ctypes.c_float(slope), _ptr(out3d), _ptr(d_out3d), _ptr(stat), _ptr(d_fs), _ptr(d_fd),
+                                                _ptr(d_attn), _ptr(ws), _stream(dev)))
+        return d_fs, d_fd, d_attn
+
     # ---- sum of relu(x_u + w_e) messages (csrc/gine.hip)
     @staticmethod
     def gine_supported(csr, D):

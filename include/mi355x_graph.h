@@ -495,6 +495,43 @@ int32_t mgx_dot_attention_bwd(const mgx_csr* csc, const mgx_spmm_plan* csc_plan 
                               const float* k, int64_t k_ld, const float* v, int64_t v_ld, float scale, const float* out,
                               const float* d_out, float* stat, float* dq, float* dk, float* dv, void* workspace, void* stream);
 
+/* GATv2 attention over a graph with NO E-sized tensor (dgl.nn.GATv2Conv between its projections and its result:
+ * apply_edges(fn.u_add_v) -> leaky_relu -> (e * attn).sum(-1) -> edge_softmax -> update_all(fn.u_mul_e, fn.sum); csrc/gatv2.hip).
+ * The non-linearity comes before the sum over features, so the operators one by one keep an [E, H, F] tensor each way:
+ *   s[e,h,f]   = fs[src(e),h,f] + fd[dst(e),h,f]
+ *   z[e,h]     = sum_f attn[h,f] * lrelu(s[e,h,f])                    lrelu(x) = x for x > 0, negative_slope * x otherwise
+ *   a[e,h]     = exp(z[e,h] - m[v,h]) / S[v,h],   m, S = max and sum over the in-edges of v = dst(e)
+ *   out[v,h,:] = sum_{e: u->v} a[e,h] * fs[u,h,:]                     (exactly 0 for a destination without in-edges)
+ *   fwd: writes out and stat[v,h,0..3] = (m, 1/S, -, -), from which the backward rebuilds a[e,h]; `a` is never written.
+ *   bwd: with t[v,h] = <out[v,h,:], d_out[v,h,:]> (written to stat[v,h,2]), dp[e,h] = <fs[u,h,:], d_out[v,h,:]>, dz = a * (dp - t)
+ *        and lrelu'(x) = 1 for x > 0, negative_slope otherwise (so the gradient at 0 is torch's):
+ *          d_fd[v]     = sum_{e: ->v} dz * attn * lrelu'(s)
+ *          d_fs[u]     = sum_{e: u->} (dz * attn * lrelu'(s) + a * d_out[v])
+ *          d_attn[h,f] = sum over ALL edges of dz * lrelu(s)          (per-workgroup partial sums, added in a fixed order)
+ *        `csc` is the in-CSR the forward ran on, `csr` its transpose (rows = source nodes).  d_fs, d_fd, d_attn may each be NULL.
+ * fs [num_cols, fs_ld], fd [num_rows, fd_ld]: the first H*F floats of a row are the operand; every row stride is a multiple of
+ * 4 floats, at least H*F, with a 16-byte aligned base -- so fs and fd may be the two column blocks of one [N, 2*H*F] projection,
+ * or one array (share_weights on a square graph).  attn [H, F], out, d_out, d_fd [num_rows, H*F], d_fs [num_cols, H*F], d_attn [H, F],
+ * stat [num_rows, H, 4]: dense, 16-byte aligned, allocated by the caller.
+ * A NaN logit reaches its row's result; a row of only -inf logits aggregates to 0 (the rule of mgx_dot_attention_*).
+ * Supported (mgx_gatv2_supported; everything else is MGX_ERR_UNSUPPORTED and the caller composes mgx_sddmm_*, mgx_edge_softmax_*
+ * and mgx_spmm_csr): the set of mgx_dot_attention_* -- F in {4, 8, 16, 32, 64}, H >= 1, H*F <= 256, 32-bit indices, nnz > 0,
+ * max(num_rows, num_cols) * H * max(4 F, 16) below 4 GiB, rows * row stride * 4 of fs and fd below 4 GiB.
+ * workspace: max over the (plan, csr) pairs passed of mgx_gatv2_workspace(plan, csr, H, F) bytes, 16-byte aligned: the hub slots of
+ * the plan plus the [workgroups, H*F] partial sums of d_attn (so it is non-zero without a plan too; the forward needs it only when
+ * the plan splits rows).
+ * mgx_last_spmm_kernel(): "gatv2_fwd" / "gatv2_bwd_dst" / "gatv2_bwd_src" after the respective launch.
+ * Deterministic: no atomics, hub partial sums combined in slot order, d_attn in block order.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_gatv2_supported(const mgx_csr* csr, int64_t H, int64_t F);
+int64_t mgx_gatv2_workspace(const mgx_spmm_plan* plan /* may be NULL */, const mgx_csr* csr, int64_t H, int64_t F);
+int32_t mgx_gatv2_fwd(const mgx_csr* csr, const mgx_spmm_plan* plan /* may be NULL */, int64_t H, int64_t F, const float* fs,
+                      int64_t fs_ld, const float* fd, int64_t fd_ld, const float* attn, float negative_slope, float* out, float* stat,
+                      void* workspace, void* stream);
+int32_t mgx_gatv2_bwd(const mgx_csr* csc, const mgx_spmm_plan* csc_plan /* may be NULL */, const mgx_csr* csr,
+                      const mgx_spmm_plan* csr_plan /* may be NULL */, int64_t H, int64_t F, const float* fs, int64_t fs_ld,
+                      const float* fd, int64_t fd_ld, const float* attn, float negative_slope, const float* out, const float* d_out,
+                      float* stat, float* d_fs, float* d_fd, float* d_attn, void* workspace, void* stream);
+
 /* Sum aggregation of relu(x_u + w_e) messages with NO E-sized temporary (the UDF message of main_dgl_molhiv_gcn.py:37-52 and
  * main_dgl_ppa_gcn.py:44-51 reduced with fn.sum; with scale = NULL upstream's dgl.nn.GINEConv; csrc/gine.hip):
  *   out[v,:] = sum_{e: u->v} s[e] * relu(x[u,:] + w[e,:])             (exactly 0 for a destination without in-edges)
