@@ -192,6 +192,52 @@ class PNA(nn.Module):
         return self.graph_pred_fc(self.readout(g, x))
 
 
+class MPNN(nn.Module):
+    """The message-passing network of Gilmer et al. (DGL's MPNNPredictor) on the molhiv-shaped batches: atom encoder; `num_layers` steps
+    of one shared dgl.nn.NNConv (sum; edge network bond features -> EDGE_HIDDEN -> emb_dim^2) followed by a GRUCell; Set2Set; a
+    two-layer head.  The NNConv's message passing and the last layer of its edge network are ONE dgl.ops.edge_bilinear call per step
+    (csrc/nnconv.hip): the [E, emb_dim^2] per-bond weights never exist."""
+
+    STEPS = 3
+    EDGE_HIDDEN = 128
+
+    def __init__(self, emb_dim, num_classes, num_layers=STEPS, dropout=0.0, atom_columns=9, bond_columns=3, edge_dim=16, **unused):
+        super(MPNN, self).__init__()
+        from dgl.nn.pytorch import NNConv, Set2Set
+        self.atom_encoder = CategoricalEncoder(emb_dim, atom_columns)
+        self.bond_encoder = CategoricalEncoder(edge_dim, bond_columns)
+        edge_net = nn.Sequential(nn.Linear(edge_dim, self.EDGE_HIDDEN), nn.ReLU(), nn.Linear(self.EDGE_HIDDEN, emb_dim * emb_dim))
+        self.conv = NNConv(emb_dim, emb_dim, edge_net, "sum")
+        self.gru = nn.GRUCell(emb_dim, emb_dim)
+        self.steps = num_layers
+        self.readout = Set2Set(emb_dim, n_iters=3, n_layers=1)
+        self.head = nn.Sequential(nn.Linear(2 * emb_dim, emb_dim), nn.ReLU(), nn.Linear(emb_dim, num_classes))
+
+    def forward(self, g, atom, bond):
+        hidden = self.atom_encoder(atom)
+        e = self.bond_encoder(bond)
+        for _ in range(self.steps):
+            hidden = self.gru(F.relu(self.conv(g, hidden, e)), hidden)
+        return self.head(self.readout(g, hidden))
+
+
+def mpnn_smoke_losses(steps=3, device="cuda:0", seed=0, num_graphs=8, emb_dim=16):
+    """The losses of `steps` Adam steps of a small MPNN on one batch of `num_graphs` molecules, from `seed`."""
+    from mi355x_graph.datasets import molhiv_like
+    bg, labels = next(iter(GraphDataLoader(molhiv_like(num_graphs), batch_size=num_graphs, shuffle=False)))
+    bg, labels = bg.to(device).int(), labels.to(device)
+    torch.manual_seed(seed)
+    model = MPNN(emb_dim, 1).to(device).train()
+    opt, loss_fn, losses = torch.optim.Adam(model.parameters(), lr=0.001), nn.BCEWithLogitsLoss(), []
+    for _ in range(steps):
+        opt.zero_grad()
+        loss = loss_fn(model(bg, bg.ndata["feat"], bg.edata["feat"]).float().view(-1), labels.float().view(-1))
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+    return losses
+
+
 def pna_delta(data, batch_size=1024):
     """PNA's degree normaliser: the mean of log(in_degree + 1) over the nodes of the training graphs, read from their batches"""
     total, count = 0.0, 0
@@ -466,9 +512,12 @@ def make_parser():
     p.add_argument("--hipgraph", action="store_true",
                    help="pad every batch to one static shape and replay one captured HIP graph (GraphedBatchTrainer)")
     p.add_argument("--dropout", type=float, default=0.5)
-    p.add_argument("--model", default="gcn", choices=["gcn", "gin", "pna"],
+    p.add_argument("--model", default="gcn", choices=["gcn", "gin", "pna", "mpnn"],
                    help="gcn: the reference's main_dgl_molhiv_gcn.py model; gin: BASELINE.json's wording of config 5; pna: Principal "
-                        "Neighbourhood Aggregation (dgl.nn.PNAConv with bond features; eager only)")
+                        "Neighbourhood Aggregation (dgl.nn.PNAConv with bond features; eager only); mpnn: --mpnn-steps steps of "
+                        "dgl.nn.NNConv + GRUCell of width --mpnn-dim, Set2Set (eager only)")
+    p.add_argument("--mpnn-dim", type=int, default=64, help="--model mpnn: node width (the edge network ends in its square)")
+    p.add_argument("--mpnn-steps", type=int, default=MPNN.STEPS, help="--model mpnn: message-passing steps")
     p.add_argument("--readout", default="mean", choices=["mean", "attention", "set2set", "sortpool", "settrans"],
                    help="mean: the reference's AvgPooling; attention: GlobalAttentionPooling; set2set: Set2Set (3 iterations); "
                         "sortpool: SortPooling (--sortpool-k nodes per graph); settrans: SetTransformerEncoder (1 SAB layer) + "
@@ -483,6 +532,8 @@ def make_parser():
 def main():
     parser = make_parser()
     args = parser.parse_args()
+    if args.model == "mpnn" and args.hipgraph:
+        parser.error("--model mpnn runs eager only")
     if args.model == "pna" and args.hipgraph:
         # the captured step pads every batch with dummy nodes and edges; PNAConv owns its batch norms and its 1 / sqrt(nodes of the graph)
         # factor, which would count the padding -- the capture machinery is not bent for it
@@ -498,8 +549,11 @@ def main():
     extra = {"fused": True} if args.fused_message and args.model == "gcn" else {}
     if args.model == "pna":
         extra = {"delta": pna_delta(data)}
-    model = {"gcn": GCN, "gin": GIN, "pna": PNA}[args.model](args.emb_dim, 1, args.num_layers, args.dropout, readout=args.readout,
-                                                             sortpool_k=args.sortpool_k, **extra).to(device)
+    if args.model == "mpnn":
+        model = MPNN(args.mpnn_dim, 1, args.mpnn_steps).to(device)
+    else:
+        model = {"gcn": GCN, "gin": GIN, "pna": PNA}[args.model](args.emb_dim, 1, args.num_layers, args.dropout, readout=args.readout,
+                                                                 sortpool_k=args.sortpool_k, **extra).to(device)
     loss_fn = nn.BCEWithLogitsLoss()
     trainer = None
     if args.hipgraph:

@@ -94,6 +94,11 @@ SIGNATURES = {
     "mgx_gatv2_fwd": (_i32, [_csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, ctypes.c_float, _fp, _fp, _vp, _vp]),
     "mgx_gatv2_bwd": (_i32, [_csr_p, _vp, _csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp,
                              _vp, _vp]),
+    "mgx_edge_bilinear_supported": (_i32, [_csr_p, _i64, _i64, _i64]),
+    "mgx_edge_bilinear_workspace": (_i64, [_i64, _i64, _i64, _i64, _i64, _i32]),
+    "mgx_edge_bilinear": (_i32, [_csr_p, _i64, _i64, _i64, _fp, _i64, _i32, _fp, _i64, _i32, _fp, _i64, _i64, _i64, _fp, _i64, _i64, _i32,
+                                 _fp, _i64, _i64, _vp, _vp]),
+    "mgx_edge_bilinear_grad_w": (_i32, [_csr_p, _i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _vp, _vp]),
     "mgx_gine_supported": (_i32, [_csr_p, _i64]),
     "mgx_gine_workspace": (_i64, [_vp, _i64]),
     "mgx_gine_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _vp, _vp]),

@@ -42,6 +42,9 @@ DOT_ATTENTION_FUSED = True  # the fused walks of csrc/dotattn.hip; False: u_dot_
 
 # ---- GATv2 attention (ops.gatv2_attention, nn.GATv2Conv)
 GATV2_FUSED = True  # the fused walks of csrc/gatv2.hip; False: u_add_v -> leaky_relu -> (. * attn).sum(-1) -> edge_softmax -> u_mul_e/sum, an [E, H, F] tensor each way
+# ---- edge-conditioned convolution (ops.edge_bilinear, nn.NNConv, graph_classification.py --model mpnn)
+NNCONV_FUSED = True      # the MFMA kernels of csrc/nnconv.hip; False: gather -> h @ Theta -> batched product -> copy_e/sum|mean, an [E, I*O] tensor each way
+NNCONV_ITEM_EDGES = 256  # CSR positions per workgroup of mgx_edge_bilinear: a multiple of 16, at most 256 (docs/LOG_nnconv.md has the sweep)
 # ---- relu(x_u + w_e) messages summed per destination (ops.gine_sum, nn.GINEConv, graph_classification.py --fused-message)
 GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> relu -> mul -> copy_e/sum through the existing operators
 # ---- sum / mean / var / std / max / min of the same messages at once (ops.multi_aggregate, nn.PNAConv, graph_classification.py --model pna)

@@ -674,6 +674,67 @@ class GINEConv(nn.Module):
         return rst
 
 
+class NNConv(nn.Module):
+    """dgl.nn.pytorch.NNConv (the edge-conditioned convolution of MPNN): h_v = reduce_{u->v} h_u W_e (+ residual, + bias) with
+    W_e = edge_func(e_uv).view(in, out).  When `edge_func` is an nn.Linear(., in * out), or an nn.Sequential that ends in one, and the
+    aggregator is sum or mean, the layer applies the modules before that last layer itself and hands its weight and bias to
+    ops.edge_bilinear (csrc/nnconv.hip when it takes the shape: no [E, in * out] tensor).  Any other edge_func and "max" run as DGL
+    writes it: u_mul_e messages of [E, in, out], reduced, then summed over `in`."""
+
+    def __init__(self, in_feats, out_feats, edge_func, aggregator_type="mean", residual=False, bias=True):
+        super(NNConv, self).__init__()
+        self._in_src_feats, self._in_dst_feats = expand_as_pair(in_feats)
+        self._out_feats = out_feats
+        self.edge_func = edge_func
+        if aggregator_type not in ("sum", "mean", "max"):
+            raise KeyError("Aggregator type {} not recognized: ".format(aggregator_type))
+        self._aggre_type = aggregator_type
+        if residual:
+            self.res_fc = nn.Linear(self._in_dst_feats, out_feats, bias=False) if self._in_dst_feats != out_feats else nn.Identity()
+        else:
+            self.register_buffer("res_fc", None)
+        if bias:
+            self.bias = nn.Parameter(torch.Tensor(out_feats))
+        else:
+            self.register_buffer("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        if self.bias is not None:
+            nn.init.zeros_(self.bias)
+        if isinstance(self.res_fc, nn.Linear):
+            nn.init.xavier_normal_(self.res_fc.weight, gain=nn.init.calculate_gain("relu"))
+
+    def _last_linear(self):
+        """(modules before it, the last nn.Linear) when edge_func ends in an nn.Linear(., in * out), else None"""
+        f = self.edge_func
+        mods = list(f) if isinstance(f, nn.Sequential) else [f]
+        if mods and type(mods[-1]) is nn.Linear and mods[-1].out_features == self._in_src_feats * self._out_feats:
+            return mods[:-1], mods[-1]
+        return None
+
+    def forward(self, graph, feat, efeat):
+        feat_src, feat_dst = expand_as_pair(feat, graph)
+        I, O = self._in_src_feats, self._out_feats
+        split = self._last_linear() if self._aggre_type != "max" else None
+        if split is not None:
+            h = efeat
+            for mod in split[0]:
+                h = mod(h)
+            lin = split[1]
+            theta = lin.weight.t().reshape(lin.in_features, I, O)  # one transposed copy per call; its gradient is transposed back
+            rst = ops.edge_bilinear(graph, feat_src, h, theta, None if lin.bias is None else lin.bias.view(I, O), self._aggre_type)
+        else:
+            gidx = ops._gidx(graph)
+            m = ops.gsddmm(gidx, "copy_lhs", feat_src, None, "u", "v").unsqueeze(-1) * self.edge_func(efeat).view(-1, I, O)
+            rst = ops.gspmm(gidx, "copy_rhs", self._aggre_type, None, m).sum(dim=1)
+        if self.res_fc is not None:
+            rst = rst + self.res_fc(feat_dst)
+        if self.bias is not None:
+            rst = rst + self.bias
+        return rst
+
+
 class PNAConvTower(nn.Module):
     """The parameters of one tower of PNAConv (UPSTREAM dgl.nn.pytorch.conv.pnaconv.PNAConvTower: M, U, batchnorm, dropout).  The
     arithmetic is PNAConv.forward's: all towers share one aggregation call."""

@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -570,6 +570,97 @@ def gatv2_attention(graph, feat_src, feat_dst, attn, negative_slope=0.2):
     if not _gatv2_kernel_ok(gidx, feat_src, feat_dst, attn):
         return _gatv2_composed(gidx, feat_src, feat_dst, attn, float(negative_slope))
     return GATv2Attention.apply(gidx, feat_src, feat_dst, attn, float(negative_slope))
+
+
+class EdgeBilinear(torch.autograd.Function):
+    """out[v] = sum | mean over e = (u -> v) of (h[e] (x) x[u]) weight + x[u] bias -- dgl.nn.NNConv's message passing with the last linear
+    layer of its edge network folded in, so the [E, I*O] per-edge weights never exist: the outer product h[e] (x) x[u] is formed in
+    registers as the A operand of an MFMA GEMM (csrc/nnconv.hip).  Saves x, h, weight and bias only."""
+
+    @staticmethod
+    def forward(ctx, gidx, x, h, weight, bias, mean):
+        weight = weight.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        out = sparse.backend_for(x).edge_bilinear_fwd(gidx.csc(), x, h, weight, bias, mean)
+        ctx.gidx, ctx.mean, ctx.has_bias = gidx, mean, bias is not None
+        ctx.save_for_backward(*((x, h, weight) + ((bias,) if bias is not None else ())))
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        x, h, weight = ctx.saved_tensors[:3]
+        bias = ctx.saved_tensors[3] if ctx.has_bias else None
+        csc, be, need = ctx.gidx.csc(), sparse.backend_for(x), ctx.needs_input_grad
+        g = d_out
+        if ctx.mean:  # the mean's division, once per destination row instead of once per edge
+            g = d_out / csc.degrees().clamp(min=1).to(torch.float32).unsqueeze(1)
+        d_x = be.edge_bilinear_grad_x(ctx.gidx.csr(), g, h, weight, bias) if need[1] else None
+        d_h = be.edge_bilinear_grad_h(csc, x, g, weight) if need[2] else None
+        d_w = d_b = None
+        if need[3] or (ctx.has_bias and need[4]):
+            d_w, d_b = be.edge_bilinear_grad_w(csc, x, h, g, int(weight.shape[0]), int(weight.shape[1]), int(weight.shape[2]),
+                                               ctx.has_bias and need[4])
+        return None, d_x, d_h, d_w if need[3] else None, d_b, None
+
+
+def _edge_bilinear_args(graph, x, h, weight, bias, reduce):
+    """The graph index of an edge_bilinear call, or DGLError."""
+    gidx = _gidx(graph)
+    _want_tensor("edge_bilinear", "x [N_src, I] and h [E, DH]", (x, h), 2)
+    _want_tensor("edge_bilinear", "weight [DH, I, O]", weight, 3)
+    if reduce not in ("sum", "mean"):
+        raise DGLError("edge_bilinear: reduce must be 'sum' or 'mean', got %r" % (reduce,))
+    if (x.shape[0] != gidx.num_src or h.shape[0] != gidx.num_edges() or weight.shape[0] != h.shape[1] or weight.shape[1] != x.shape[1]
+            or 0 in weight.shape):
+        raise DGLError("edge_bilinear: expected x [%d, I], h [%d, DH] and weight [DH, I, O], got %s, %s and %s"
+                       % (gidx.num_src, gidx.num_edges(), tuple(x.shape), tuple(h.shape), tuple(weight.shape)))
+    if bias is not None:
+        _want_tensor("edge_bilinear", "bias [I, O]", bias, 2)
+        if tuple(bias.shape) != tuple(weight.shape[1:]):
+            raise DGLError("edge_bilinear: expected bias %s, got %s" % (tuple(weight.shape[1:]), tuple(bias.shape)))
+    return gidx
+
+
+def _edge_bilinear_kernel_ok(gidx, x, h, weight, bias):
+    if (not _device_kernels(x, config.NNCONV_FUSED, "edge_bilinear_fwd", "edge_bilinear_grad_w")
+            or any(t is not None and t.device != x.device for t in (h, weight, bias)) or gidx.num_edges() == 0):
+        return False
+    return sparse.backend_for(x).edge_bilinear_supported(gidx.csc(), *(int(n) for n in weight.shape))
+
+
+def edge_bilinear_fused(graph, x, h, weight, bias=None, reduce="sum"):
+    """True when edge_bilinear(graph, x, h, weight, bias, reduce) runs the fused kernels (else it is the operators one by one)."""
+    try:
+        return _edge_bilinear_kernel_ok(_edge_bilinear_args(graph, x, h, weight, bias, reduce), x, h, weight, bias)
+    except DGLError:
+        return False
+
+
+def _edge_bilinear_composed(gidx, x, h, weight, bias, reduce):
+    """row gather -> h @ weight -> batched vector-matrix product -> copy_e / sum|mean: an [E, I*O] tensor forward, kept for backward."""
+    DH, I, O = (int(n) for n in weight.shape)
+    w_e = h @ weight.reshape(DH, I * O)
+    if bias is not None:
+        w_e = w_e + bias.reshape(1, I * O)
+    m = torch.bmm(gsddmm(gidx, "copy_lhs", x, None, "u", "v").unsqueeze(1), w_e.view(-1, I, O)).squeeze(1)
+    return gspmm(gidx, "copy_rhs", reduce, None, m)
+
+
+def edge_bilinear(graph, x, h, weight, bias=None, reduce="sum"):
+    """Edge-conditioned convolution: out[v,o] = reduce_{e: u->v} (sum_k sum_i h[e,k] x[u,i] weight[k,i,o] + sum_i x[u,i] bias[i,o]).
+
+    x: [N_src, I], h: [E, DH] by edge id (the edge network's output before its last Linear(DH, I*O)), weight: [DH, I, O] and bias: [I, O]
+    or None (that layer's weight and bias), fp32; reduce "sum" or "mean"; result [N_dst, O], exactly 0 for destinations without in-edges.
+    Device operands with I, O <= 128 on an int32 graph run csrc/nnconv.hip (edge_bilinear_fused): no [E, I*O], [E, O] or [N, DH, O]
+    tensor forward or backward, only the launches whose gradients are asked for.  Everything else -- CPU tensors under a registered CPU
+    backend, 64-bit graphs, wider layers, config.NNCONV_FUSED = False -- takes the same values through the existing operators."""
+    gidx = _edge_bilinear_args(graph, x, h, weight, bias, reduce)
+    if gidx.num_edges() == 0:
+        return _no_edges_zeros((gidx.num_dst, weight.shape[2]), x, h) + 0 * weight.sum() + (0 if bias is None else 0 * bias.sum())
+    if not _edge_bilinear_kernel_ok(gidx, x, h, weight, bias):
+        return _edge_bilinear_composed(gidx, x, h, weight, bias, reduce)
+    return EdgeBilinear.apply(gidx, x, h, weight, bias, reduce == "mean")
 
 
 class GineSum(torch.autograd.Function):

@@ -1113,6 +1113,74 @@ class HipBackend(object):
                                                 _ptr(d_attn), _ptr(ws), _stream(dev)))
         return d_fs, d_fd, d_attn
 
+    # ---- edge-conditioned convolution (csrc/nnconv.hip)
+    @staticmethod
+    def edge_bilinear_supported(csr, DH, I, O):
+        """Shapes mgx_edge_bilinear* takes: int32 graph with edges, 1 <= I, O <= 128, any DH >= 1, operands within 2^30 floats."""
+        return bool(_lib.lib().mgx_edge_bilinear_supported(ctypes.byref(csr.c_struct()), int(DH), int(I), int(O)))
+
+    def _edge_bilinear_ws(self, dev, nnz, DH, I, O, grad_w):
+        size = _lib.lib().mgx_edge_bilinear_workspace(nnz, DH, I, O, int(config.NNCONV_ITEM_EDGES), 1 if grad_w else 0)
+        if size < 0:
+            _lib.check(_lib.ERR_UNSUPPORTED)
+        return torch.empty(max(size, 4) // 4, dtype=torch.float32, device=dev)
+
+    @staticmethod
+    def _eb_rows(t):
+        """(tensor, row stride) of a [N, D] operand: the kernels read dwords, so any view whose rows are contiguous is taken as it is."""
+        if t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+            return t, int(t.stride(0))
+        return t.contiguous(), int(t.shape[1])
+
+    def _edge_bilinear(self, csr, kind, P, p_index, Q, q_index, theta, strides, one, one_strides, epilogue, out):
+        """One launch of the general form (include/mi355x_graph.h); A, B from P and Q, N from out."""
+        dev = out.device
+        (P, ldp), (Q, ldq) = self._eb_rows(P), self._eb_rows(Q)
+        A, B, N = int(P.shape[1]), int(Q.shape[1]), int(out.shape[1])
+        DH, I, O = (int(x) for x in theta.shape)
+        ws = self._edge_bilinear_ws(dev, csr.nnz, DH, I, O, False) if epilogue else None
+        with torch.cuda.device(dev), timed_call(dev, kernel=kind, A=A, B=B, N=N, nnz=csr.nnz):
+            _lib.check(_lib.lib().mgx_edge_bilinear(ctypes.byref(csr.c_struct()), A, B, N, _ptr(P), ldp, p_index, _ptr(Q), ldq, q_index,
+                                                    _ptr(theta), strides[0], strides[1], strides[2], _ptr(one), one_strides[0],
+                                                    one_strides[1], epilogue, _ptr(out), N, int(config.NNCONV_ITEM_EDGES), _ptr(ws),
+                                                    _stream(dev)))
+        return out
+
+    def edge_bilinear_fwd(self, csc, x2d, h2d, theta, bias, mean):
+        """out[v] = sum | mean over the in-edges e = (u -> v) of (h[e] (x) x[u]) theta + x[u] bias; theta [DH, I, O] and bias [I, O] | None
+        contiguous.  -> [n_dst, O], zeros for a destination without in-edges."""
+        dev = self._check_dev(csc.indptr, x2d, h2d, theta, bias)
+        DH, I, O = (int(x) for x in theta.shape)
+        out = torch.zeros((csc.num_rows, O), dtype=torch.float32, device=dev)  # rows without edges are not written
+        return self._edge_bilinear(csc, "edge_bilinear_fwd", h2d, 0, x2d, 1, theta, (I * O, O, 1), bias, (O, 1), 2 if mean else 1, out)
+
+    def edge_bilinear_grad_x(self, csr, g2d, h2d, theta, bias):
+        """d x[u] = sum over the out-edges e = (u -> v) of the same form with i and o exchanged; g2d = d out (divided by the in-degree for
+        mean).  -> [n_src, I]."""
+        dev = self._check_dev(csr.indptr, g2d, h2d, theta, bias)
+        DH, I, O = (int(x) for x in theta.shape)
+        out = torch.zeros((csr.num_rows, I), dtype=torch.float32, device=dev)
+        return self._edge_bilinear(csr, "edge_bilinear_grad_x", h2d, 0, g2d, 1, theta, (I * O, 1, O), bias, (1, O), 1, out)
+
+    def edge_bilinear_grad_h(self, csc, x2d, g2d, theta):
+        """d h[e, k] = sum_i sum_o x[u, i] g[v, o] theta[k, i, o], one row per edge id.  -> [E, DH]."""
+        dev = self._check_dev(csc.indptr, x2d, g2d, theta)
+        DH, I, O = (int(x) for x in theta.shape)
+        out = torch.empty((csc.nnz, DH), dtype=torch.float32, device=dev)
+        return self._edge_bilinear(csc, "edge_bilinear_grad_h", x2d, 1, g2d, 2, theta, (O, 1, I * O), None, (0, 0), 0, out)
+
+    def edge_bilinear_grad_w(self, csc, x2d, h2d, g2d, DH, I, O, with_bias):
+        """(d theta [DH, I, O], d bias [I, O] | None): the sums over all edges of h[e, k] x[u, i] g[v, o]."""
+        dev = self._check_dev(csc.indptr, x2d, h2d, g2d)
+        (x, ldx), (h, ldh), (g, ldg) = self._eb_rows(x2d), self._eb_rows(h2d), self._eb_rows(g2d)
+        d_theta = torch.empty((DH, I, O), dtype=torch.float32, device=dev)
+        d_bias = torch.empty((I, O), dtype=torch.float32, device=dev) if with_bias else None
+        ws = self._edge_bilinear_ws(dev, csc.nnz, DH, I, O, True)
+        with torch.cuda.device(dev), timed_call(dev, kernel="edge_bilinear_grad_w", DH=DH, I=I, O=O, nnz=csc.nnz):
+            _lib.check(_lib.lib().mgx_edge_bilinear_grad_w(ctypes.byref(csc.c_struct()), DH, I, O, _ptr(h), ldh, _ptr(x), ldx, _ptr(g), ldg,
+                                                           _ptr(d_theta), _ptr(d_bias), _ptr(ws), _stream(dev)))
+        return d_theta, d_bias
+
     # ---- sum of relu(x_u + w_e) messages (csrc/gine.hip)
     @staticmethod
     def gine_supported(csr, D):

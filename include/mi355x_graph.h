@@ -532,6 +532,38 @@ int32_t mgx_gatv2_bwd(const mgx_csr* csc, const mgx_spmm_plan* csc_plan /* may b
                       const float* fd, int64_t fd_ld, const float* attn, float negative_slope, const float* out, const float* d_out,
                       float* stat, float* d_fs, float* d_fd, float* d_attn, void* workspace, void* stream);
 
+/* Edge-conditioned convolution (dgl.nn.NNConv, the MPNN layer) with NO [E, I*O] tensor (csrc/nnconv.hip).  With h [E, DH] the output of
+ * the edge network before its last Linear(DH, I*O), whose weight is Theta[k,i,o] and bias Bias[i,o]:
+ *   out[v,o] = sum_{e: u->v} ( sum_k sum_i h[e,k] * x[u,i] * Theta[k,i,o] + sum_i x[u,i] * Bias[i,o] )
+ * is per edge (h_e (x) x_u) Theta, a GEMM whose A operand is an outer product formed in registers.  The general form
+ *   mgx_edge_bilinear:  out[row(p), n] (+)= sum_{a < A} sum_{b < B} P[ia(p), a] * Q[ib(p), b] * W[a*w_sa + b*w_sb + n*w_sn]
+ *                                          + sum_b Q[ib(p), b] * W_one[b*one_sb + n*one_sn]          (W_one may be NULL)
+ * runs over the positions p of `csr`; ia / ib are chosen by p_index / q_index: MGX_EB_BY_EDGE = eids[p] (p without eids), MGX_EB_BY_COL =
+ * indices[p], MGX_EB_BY_ROW = the row of p.  Epilogues: MGX_EB_STORE_BY_EDGE writes row p to out[eids[p]] (any N); MGX_EB_ROW_SUM / _MEAN
+ * add the positions of every CSR row in position order (mean: divided by the row length) into out[row]; a row without positions is NOT
+ * written -- pass zeros.  The forward is (in-CSR; P = h BY_EDGE, Q = x BY_COL, W = Theta with strides (I*O, O, 1), W_one = Bias (O, 1)),
+ * d x the same call on the out-CSR with Q = d out and strides (I*O, 1, O) / (1, O), d h the call with P = x BY_COL, Q = d out BY_ROW,
+ * strides (O, 1, I*O) and the store epilogue.
+ *   mgx_edge_bilinear_grad_w:  d_theta[k,i,o] = sum_p h[eid(p),k] * x[indices[p],i] * g[row(p),o],  d_bias[i,o] the same with h = 1
+ * over the in-CSR; per-chunk partial sums added in chunk order.  d_bias may be NULL.
+ * P, Q, h, x, g: fp32 with row strides (any alignment); out, d_theta, d_bias dense.  item_edges: a multiple of 16 in 16 .. 256.
+ * Supported (mgx_edge_bilinear_supported; the rest is MGX_ERR_UNSUPPORTED): 32-bit indices, nnz > 0, 1 <= I, O <= 128 (B <= 128, and
+ * N <= 128 for a row sum), DH >= 1, every operand within 2^30 floats.  workspace: mgx_edge_bilinear_workspace bytes (grad_w = 0: the
+ * [items, 2, 128] partial rows of the row-sum epilogue; 1: the [chunks, DH + 1, I, O] partial sums), -1 outside the supported shapes.
+ * mgx_last_spmm_kernel(): "edge_bilinear_rows" / "edge_bilinear_edges" / "edge_bilinear_grad_w".
+ * Deterministic: no atomics, fixed summation order.  Purely additive: mgx_abi_version() stays 35. */
+enum { MGX_EB_BY_EDGE = 0, MGX_EB_BY_COL = 1, MGX_EB_BY_ROW = 2 };
+enum { MGX_EB_STORE_BY_EDGE = 0, MGX_EB_ROW_SUM = 1, MGX_EB_ROW_MEAN = 2 };
+int32_t mgx_edge_bilinear_supported(const mgx_csr* csr, int64_t DH, int64_t I, int64_t O);
+int64_t mgx_edge_bilinear_workspace(int64_t nnz, int64_t DH, int64_t I, int64_t O, int64_t item_edges, int32_t grad_w);
+int32_t mgx_edge_bilinear(const mgx_csr* csr, int64_t A, int64_t B, int64_t N, const float* P, int64_t ldp, int32_t p_index,
+                          const float* Q, int64_t ldq, int32_t q_index, const float* W, int64_t w_sa, int64_t w_sb, int64_t w_sn,
+                          const float* W_one /* may be NULL */, int64_t one_sb, int64_t one_sn, int32_t epilogue, float* out, int64_t ldo,
+                          int64_t item_edges, void* workspace, void* stream);
+int32_t mgx_edge_bilinear_grad_w(const mgx_csr* csr, int64_t DH, int64_t I, int64_t O, const float* h, int64_t ldh, const float* x,
+                                 int64_t ldx, const float* g, int64_t ldg, float* d_theta, float* d_bias /* may be NULL */,
+                                 void* workspace, void* stream);
+
 /* Sum aggregation of relu(x_u + w_e) messages with NO E-sized temporary (the UDF message of main_dgl_molhiv_gcn.py:37-52 and
  * main_dgl_ppa_gcn.py:44-51 reduced with fn.sum; with scale = NULL upstream's dgl.nn.GINEConv; csrc/gine.hip):
  *   out[v,:] = sum_{e: u->v} s[e] * relu(x[u,:] + w[e,:])             (exactly 0 for a destination without in-edges)
