@@ -45,6 +45,11 @@ GATV2_FUSED = True  # the fused walks of csrc/gatv2.hip; False: u_add_v -> leaky
 # ---- edge-conditioned convolution (ops.edge_bilinear, nn.NNConv, graph_classification.py --model mpnn)
 NNCONV_FUSED = True      # the MFMA kernels of csrc/nnconv.hip; False: gather -> h @ Theta -> batched product -> copy_e/sum|mean, an [E, I*O] tensor each way
 NNCONV_ITEM_EDGES = 256  # CSR positions per workgroup of mgx_edge_bilinear: a multiple of 16, at most 256 (docs/LOG_nnconv.md has the sweep)
+# ---- sparse x sparse product (ops.spgemm, dgl.adj_product_graph, dgl.metapath_reachable_graph)
+SPGEMM_FUSED = True  # the kernels of csrc/spgemm.hip; False: repeat_interleave -> unique -> index_add, every product materialised
+SPGEMM_T1 = 512      # rows of at most T1 products: a wave and 2 T1 hash slots in LDS each (a power of two in 64 .. 1024)
+SPGEMM_T2 = 2048     # rows of at most T2 products: a workgroup and 2 T2 slots (a power of two, T1 < T2 <= 4096); above: column windows
+SPGEMM_W = 4096      # columns per window of the rows above T2 (a multiple of 32, at most 7168); docs/LOG_spgemm.md has the sweep
 # ---- relu(x_u + w_e) messages summed per destination (ops.gine_sum, nn.GINEConv, graph_classification.py --fused-message)
 GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> relu -> mul -> copy_e/sum through the existing operators
 # ---- sum / mean / var / std / max / min of the same messages at once (ops.multi_aggregate, nn.PNAConv, graph_classification.py --model pna)

@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -661,6 +661,120 @@ def edge_bilinear(graph, x, h, weight, bias=None, reduce="sum"):
     if not _edge_bilinear_kernel_ok(gidx, x, h, weight, bias):
         return _edge_bilinear_composed(gidx, x, h, weight, bias, reduce)
     return EdgeBilinear.apply(gidx, x, h, weight, bias, reduce == "mean")
+
+
+class SpGEMM(torch.autograd.Function):
+    """wc of the product of two adjacency matrices (csrc/spgemm.hip); the product's CSR is left in `out["csr"]`.  Saves wa and wb only;
+    backward is one launch per gradient asked for: a lane group per entry of the operand walks a row of the other operand (B for d wa,
+    A's in-CSR for d wb) and finds its terms in the product's sorted rows."""
+
+    @staticmethod
+    def forward(ctx, out, ga, gb, wa, wb):
+        a, b = ga.csr(), gb.csr()
+        wa, wb = (None if w is None else w.contiguous() for w in (wa, wb))
+        c, wc = sparse.backend_for(a.indptr).spgemm(a, b, wa, wb)
+        out["csr"] = c
+        ctx.ga, ctx.gb, ctx.c, ctx.w = ga, gb, c, (wa, wb)
+        return wc
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_wc):
+        (wa, wb), be, d_wc = ctx.w, sparse.backend_for(ctx.c.indptr), d_wc.contiguous()
+        d_wa = be.spgemm_grad(ctx.ga.csr(), ctx.gb.csr(), 0, wb, ctx.c, d_wc) if ctx.needs_input_grad[3] else None
+        d_wb = be.spgemm_grad(ctx.gb.csr(), ctx.ga.csc(), 1, wa, ctx.c, d_wc) if ctx.needs_input_grad[4] else None
+        return None, None, None, d_wa, d_wb
+
+
+def _spgemm_args(ga, gb, wa, wb):
+    """The graph indices of a spgemm call, or DGLError."""
+    idx = []
+    for g in (ga, gb):
+        rels = getattr(g, "_rels", None)  # a heterograph of one relation (dgl.bipartite) is that relation
+        if rels is not None and len(rels) == 1:
+            g = next(iter(rels.values()))
+        if not isinstance(g, (DGLGraph, GraphIndex)):
+            raise DGLError("spgemm: expected two graphs of one relation each, got %s and %s" % (type(ga).__name__, type(gb).__name__))
+        idx.append(_gidx(g))
+    ia, ib = idx
+    if ia.num_dst != ib.num_src:
+        raise DGLError("spgemm: the first graph has %d destination nodes, the second %d source nodes" % (ia.num_dst, ib.num_src))
+    if ia.idtype != ib.idtype or ia.device != ib.device:
+        raise DGLError("spgemm: the graphs differ in idtype or device (%s on %s, %s on %s)" % (ia.idtype, ia.device, ib.idtype, ib.device))
+    for name, w, i in (("wa", wa, ia), ("wb", wb, ib)):
+        if w is None:
+            continue
+        if not torch.is_tensor(w) or w.dtype != torch.float32 or w.dim() != 1 or w.shape[0] != i.num_edges():
+            raise DGLError("spgemm: %s must be a float32 tensor [%d], got %s"
+                           % (name, i.num_edges(), "%s %s" % (w.dtype, tuple(w.shape)) if torch.is_tensor(w) else type(w).__name__))
+        if w.device != i.device:
+            raise DGLError("spgemm: %s is on %s, its graph on %s" % (name, w.device, i.device))
+    return ia, ib
+
+
+def _spgemm_kernel_ok(ia, ib):
+    if not (config.SPGEMM_FUSED and ia.device.type == "cuda" and hasattr(sparse._BACKENDS.get("cuda"), "spgemm")):
+        return False
+    return sparse._BACKENDS["cuda"].spgemm_supported(ia.csr(), ib.csr())
+
+
+def spgemm_fused(ga, gb, wa=None, wb=None):
+    """True when spgemm(ga, gb, wa, wb) runs the kernels of csrc/spgemm.hip (else the composition, or it raises)."""
+    try:
+        return _spgemm_kernel_ok(*_spgemm_args(ga, gb, wa, wb))
+    except DGLError:
+        return False
+
+
+def _spgemm_composed(a, b, wa, wb):
+    """Every product expanded (repeat_interleave), unique on row * m + col, index_add: the reference composition in plain torch."""
+    dev, dt, n, m = a.indptr.device, a.indptr.dtype, a.num_rows, b.num_cols
+    b_len = (b.indptr[1:] - b.indptr[:-1]).long()
+    ks = a.indices.long()
+    lens = b_len[ks]  # products per entry of A
+    pa = torch.repeat_interleave(torch.arange(a.nnz, device=dev), lens)  # the entry of A of every product
+    first = torch.cumsum(lens, 0) - lens
+    qb = b.indptr[:-1].long()[ks][pa] + (torch.arange(pa.shape[0], device=dev) - first[pa])  # ... and its entry of B
+    key, inv = torch.unique(a.row_of_position().long()[pa] * m + b.indices.long()[qb], return_inverse=True)
+    rows = torch.div(key, max(m, 1), rounding_mode="floor")
+    indptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(rows, minlength=n), 0, out=indptr[1:])
+    c = sparse.CsrView(n, m, indptr.to(dt), (key - rows * m).to(dt), None)
+    if wa is None and wb is None:
+        return c, None
+    ea, eb = (pa if a.eids is None else a.eids.long()[pa]), (qb if b.eids is None else b.eids.long()[qb])
+    va = torch.ones((), device=dev) if wa is None else wa[ea]
+    vb = torch.ones((), device=dev) if wb is None else wb[eb]
+    return c, torch.zeros(key.shape[0], dtype=torch.float32, device=dev).index_add(0, inv, (va * vb).expand(pa.shape[0]))
+
+
+def spgemm(ga, gb, wa=None, wb=None):
+    """The product of two adjacency matrices: (gc, wc) with gc the graph of A B and wc[e] = sum of wa * wb over the products of its edge e.
+
+    ga: n source and k destination nodes, gb: k source and m destination nodes (graphs, bipartite graphs or blocks of one idtype on one
+    device); A[src, dst] is a graph's adjacency, parallel edges are entries that add.  wa [E_a], wb [E_b]: fp32 by edge id, None = ones;
+    wc is None when both are (pattern only), else differentiable in both.  gc has one edge per structural non-zero -- also where the
+    weights cancel -- sorted by (source, destination); edge id = position in its out-CSR.  Device graphs run csrc/spgemm.hip
+    (spgemm_fused): hash tables and column windows in LDS, no product ever written to memory, bitwise equal reruns; what those kernels
+    do not take raises.  CPU graphs under a registered CPU backend, and config.SPGEMM_FUSED = False, expand every product in torch."""
+    ia, ib = _spgemm_args(ga, gb, wa, wb)
+    if _spgemm_kernel_ok(ia, ib):
+        if wa is None and wb is None:
+            c, wc = sparse.backend_for(ia.csr().indptr).spgemm(ia.csr(), ib.csr(), None, None)
+        else:
+            out = {}
+            wc = SpGEMM.apply(out, ia, ib, wa, wb)
+            c = out["csr"]
+    else:
+        if config.SPGEMM_FUSED and ia.device.type == "cuda":
+            raise DGLError("spgemm: operands outside what csrc/spgemm.hip takes (%d x %d by %d x %d, %d and %d edges)"
+                           % (ia.num_src, ia.num_dst, ib.num_src, ib.num_dst, ia.num_edges(), ib.num_edges()))
+        if ia.device.type not in sparse._BACKENDS:
+            raise DGLError("spgemm: %s graphs need a registered backend (mi355x_graph.enable_cpu_backend)" % ia.device.type)
+        c, wc = _spgemm_composed(ia.csr(), ib.csr(), wa, wb)
+    gc = DGLGraph(GraphIndex(ia.num_src, ib.num_dst, csr=c), is_block=ia.num_src != ib.num_dst)
+    gc._unibipartite = gc._is_block  # two node sets, not a message-flow block
+    return gc, wc
 
 
 class GineSum(torch.autograd.Function):

@@ -1181,6 +1181,60 @@ class HipBackend(object):
                                                            _ptr(d_theta), _ptr(d_bias), _ptr(ws), _stream(dev)))
         return d_theta, d_bias
 
+    # ---- sparse x sparse product (csrc/spgemm.hip)
+    @staticmethod
+    def spgemm_supported(a, b):
+        """Operands mgx_spgemm_* takes: one index width, inner sizes equal, m < 2^31 - 1, n and both nnz below 2^27."""
+        return bool(_lib.lib().mgx_spgemm_supported(ctypes.byref(a.c_struct()), ctypes.byref(b.c_struct())))
+
+    def spgemm(self, a, b, wa, wb):
+        """a [n, k], b [k, m]: CsrViews (for graphs the out-CSRs); wa / wb: contiguous fp32 by edge id or None (ones).  -> (the CsrView
+        of A B: rows and the columns of a row ascending, eids None; wc by position, None when wa and wb both are).  Two host reads: the
+        class sizes with the error bits, and nnz(C)."""
+        dev = self._check_dev(a.indptr, b.indptr, wa, wb)
+        L, dt, n = _lib.lib(), a.indptr.dtype, a.num_rows
+        ca, cb = ctypes.byref(a.c_struct()), ctypes.byref(b.c_struct())
+        t1, t2, w = int(config.SPGEMM_T1), int(config.SPGEMM_T2), int(config.SPGEMM_W)
+        values = wa is not None or wb is not None
+        if n == 0 or a.nnz == 0 or b.nnz == 0:
+            wc = torch.zeros(0, dtype=torch.float32, device=dev) if values else None
+            return CsrView(n, b.num_cols, torch.zeros(n + 1, dtype=dt, device=dev), torch.zeros(0, dtype=dt, device=dev), None), wc
+        with torch.cuda.device(dev), timed_call(dev, kernel="spgemm", n=n, nnz_a=a.nnz, nnz_b=b.nnz):
+            ws_bytes = L.mgx_spgemm_workspace(n)
+            if ws_bytes < 0:
+                _lib.check(_lib.ERR_UNSUPPORTED)
+            ws = torch.empty(ws_bytes // 8 + 1, dtype=torch.int64, device=dev)
+            _lib.check(L.mgx_spgemm_bound(ca, cb, t1, t2, _ptr(ws), _stream(dev)))
+            head = ws[:7].tolist()  # host read 1: where every class of rows starts, and the error bits
+            if head[6] & 1:
+                raise DGLError("spgemm: the first operand has a column outside [0, %d)" % a.num_cols)
+            if head[6] & 2:
+                raise DGLError("spgemm: the second operand has a column outside [0, %d)" % b.num_cols)
+            class_start = (ctypes.c_int64 * 6)(*head[:6])
+            counts = torch.empty(n, dtype=torch.int64, device=dev)
+            _lib.check(L.mgx_spgemm_count(ca, cb, t1, t2, w, class_start, _ptr(ws), _ptr(counts), _stream(dev)))
+            offsets = self._sample_offsets(counts)
+            total = int(offsets[-1].item())  # host read 2: nnz(C)
+            if dt == torch.int32 and total >= 2 ** 31:
+                raise DGLError("spgemm: the product has %d entries, too many for int32 ids" % total)
+            indices = torch.empty(total, dtype=dt, device=dev)
+            wc = torch.empty(total, dtype=torch.float32, device=dev) if values else None
+            if total:
+                _lib.check(L.mgx_spgemm_fill(ca, cb, _ptr(wa), _ptr(wb), t1, t2, w, class_start, _ptr(ws), _ptr(offsets), _ptr(indices),
+                                             _ptr(wc), _stream(dev)))
+        return CsrView(n, b.num_cols, offsets.to(dt), indices, None), wc
+
+    def spgemm_grad(self, x, y, mode, wy, c, d_wc):
+        """d wx by edge id of x.  mode 0: x = A, y = B, wy = wb; mode 1: x = B, y = A^T (A's in-CSR, A's edge ids), wy = wa.  c: the
+        product's CsrView, d_wc contiguous fp32 by its positions."""
+        dev = self._check_dev(x.indptr, y.indptr, c.indptr, wy, d_wc)
+        d_wx = torch.zeros(x.nnz, dtype=torch.float32, device=dev)
+        if x.nnz and c.nnz:
+            with torch.cuda.device(dev), timed_call(dev, kernel="spgemm_grad", mode=mode, nnz=x.nnz):
+                _lib.check(_lib.lib().mgx_spgemm_grad(ctypes.byref(x.c_struct()), ctypes.byref(y.c_struct()), int(mode), _ptr(wy),
+                                                      ctypes.byref(c.c_struct()), _ptr(d_wc), _ptr(d_wx), _stream(dev)))
+        return d_wx
+
     # ---- sum of relu(x_u + w_e) messages (csrc/gine.hip)
     @staticmethod
     def gine_supported(csr, D):

@@ -493,3 +493,66 @@ def metis_partition(g, k, extra_cached_hops=0, reshuffle=False, balance_ntypes=N
             parts[i] = g.subgraph(order[off:off + c])
         off += c
     return parts
+
+
+def _one_relation(g, who):
+    """(the relation of `g` as a DGLGraph view, its source node type, its destination node type)"""
+    if hasattr(g, "canonical_etypes"):
+        if len(g.canonical_etypes) != 1:
+            raise DGLError("%s: expected a graph of one relation, got %d" % (who, len(g.canonical_etypes)))
+        g = g[g.canonical_etypes[0]]
+    if not isinstance(g, DGLGraph):
+        raise DGLError("%s: expected a graph, got %s" % (who, type(g).__name__))
+    stype, dtype = getattr(g, "_ntypes", None) or ("_N", "_N")
+    return g, stype, dtype
+
+
+def _derived_graph(index, stype, dtype, etype, src_frame, dst_frame):
+    """The graph of a product: homogeneous when stype is dtype, else the bipartite stype -etype-> dtype; node data copied."""
+    if stype == dtype:
+        out = DGLGraph(index)
+        for frame in (src_frame, dst_frame):
+            for k, v in frame.items():
+                out.ndata[k] = v
+        return out
+    from collections import OrderedDict
+    from .heterograph import DGLHeteroGraph
+    out = DGLHeteroGraph(OrderedDict(sorted(((stype, index.num_src), (dtype, index.num_dst)))), OrderedDict([((stype, etype, dtype), index)]))
+    for t, frame in ((stype, src_frame), (dtype, dst_frame)):
+        for k, v in frame.items():
+            out.nodes[t].data[k] = v
+    return out
+
+
+def adj_product_graph(A, B, weight_name, etype="_E"):
+    """dgl.adj_product_graph: the graph whose weighted adjacency is the product of those of A and B (ops.spgemm, csrc/spgemm.hip on the
+    device).  The weights are A.edata[weight_name] and B.edata[weight_name] (fp32 [E]); the result's edata[weight_name] carries the
+    autograd graph to both.  Node data: A's source type and B's destination type; homogeneous when those are one node set."""
+    from . import ops
+    (A, s_a, d_a), (B, s_b, d_b) = _one_relation(A, "adj_product_graph"), _one_relation(B, "adj_product_graph")
+    if d_a != s_b:
+        raise DGLError("adj_product_graph: the destination node type of A (%s) is not the source node type of B (%s)" % (d_a, s_b))
+    gc, wc = ops.spgemm(A, B, A.edata[weight_name], B.edata[weight_name])
+    out = _derived_graph(gc._index, s_a, d_b, etype, A.srcdata, B.dstdata)
+    out.edata[weight_name] = wc
+    return out
+
+
+def metapath_reachable_graph(g, metapath):
+    """dgl.metapath_reachable_graph: an edge (u, v) wherever v is reached from u along the edge types of `metapath` -- the pattern-only
+    chain of the relations' adjacencies, one ops.spgemm per step.  On the first source and the last destination node type."""
+    from . import ops
+    if not hasattr(g, "to_canonical_etype") or len(metapath) == 0:
+        raise DGLError("metapath_reachable_graph: expected a heterograph and a non-empty list of edge types")
+    cets = [g.to_canonical_etype(e) for e in metapath]
+    for prev, cur in zip(cets, cets[1:]):
+        if prev[2] != cur[0]:
+            raise DGLError("metapath_reachable_graph: %r does not continue %r" % (cur, prev))
+    index = g._rels[cets[0]]
+    for cet in cets[1:]:
+        index = ops.spgemm(index, g._rels[cet])[0]._index
+    if len(cets) == 1:  # one step: the relation itself with parallel edges merged
+        n = index.num_dst
+        index = ops.spgemm(index, GraphIndex(n, n, coo=tuple(torch.arange(n, dtype=index.idtype, device=index.device) for _ in range(2))))[0]._index
+    stype, dtype = cets[0][0], cets[-1][2]
+    return _derived_graph(index, stype, dtype, "_E", g.nodes[stype].data, g.nodes[dtype].data)

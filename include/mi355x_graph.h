@@ -564,6 +564,40 @@ int32_t mgx_edge_bilinear_grad_w(const mgx_csr* csr, int64_t DH, int64_t I, int6
                                  int64_t ldx, const float* g, int64_t ldg, float* d_theta, float* d_bias /* may be NULL */,
                                  void* workspace, void* stream);
 
+/* Sparse x sparse product C = A B of two CSR operands (csrc/spgemm.hip; ops.spgemm, dgl.adj_product_graph,
+ * dgl.metapath_reachable_graph).  A is `a` (n rows, k columns), B is `b` (k rows, m columns); for graphs these are the OUT-CSRs, A[src,
+ * dst].  Stored entries that repeat a (row, column) pair are separate entries that add.  C has one entry per structural non-zero (kept
+ * when its sum is 0.0), rows and the columns of a row ascending, and, with values,
+ *   wc[(i,j)] = sum over the products (i,k) of A, (k,j) of B of wa[eid_a] * wb[eid_b]        (wa / wb fp32 by edge id, NULL = ones).
+ * Count then fill, as mgx_node_subgraph_count / _fill; the caller allocates everything and makes two host reads:
+ *   mgx_spgemm_bound   products per row of A -> the rows sorted by class (0 empty, 1: <= 32 products, 2: <= t1, 3: <= t2, 4: above) in the
+ *                      workspace, whose first 7 int64 words then are class_start[0 .. 5] (class c is positions class_start[c] ..
+ *                      class_start[c + 1] of the row list; class_start[5] = n) and the error bits (1: a column of A outside [0, k),
+ *                      2: a column of B outside [0, m); such entries are skipped).  READ 1: these 7 words.
+ *   mgx_spgemm_count   counts[i] = distinct columns of row i of C, every row written.  The caller's exclusive scan of counts is `offsets`
+ *                      [n + 1] (int64); READ 2: offsets[n] = nnz(C).
+ *   mgx_spgemm_fill    c_indices [nnz(C)] (the operands' index type) and, unless wc is NULL (pattern only), wc [nnz(C)].
+ *   mgx_spgemm_grad    d_wx[eid_x(p)] for every stored position p = (r, c) of x, given d_wc by position of C (indptr and indices in the
+ *                      operands' index type): mode 0, x = A and y = B: sum over the entries (c, j) of y of wy * d_wc[(r, j)]; mode 1,
+ *                      x = B and y = A^T (rows k, columns i, eids those of A, as mgx_csr_transpose gives it): sum over the entries
+ *                      (r, i) of y of wy * d_wc[(i, c)].  wy may be NULL (ones).
+ * class_start of count / fill: the 6 words read from the workspace, in HOST memory.  t1, t2: powers of two, 64 <= t1 <= 1024, t1 < t2 <=
+ * 4096; w: a multiple of 32 in 32 .. 7168 (the LDS of a workgroup holds 3 t2 + 1 words, or w / 32 + 260 + 2 w).  Supported
+ * (mgx_spgemm_supported; the rest is MGX_ERR_UNSUPPORTED): both operands of one index width, a.num_cols == b.num_rows, m < 2^31 - 1
+ * (32-bit keys), n and both nnz below 2^27.  workspace: mgx_spgemm_workspace(n) bytes, the same buffer from bound to fill.
+ * Deterministic: integer LDS atomics decide membership and who adds next, no floating-point atomic; sums are in (A position, B position)
+ * order.  No call synchronises.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_spgemm_supported(const mgx_csr* a, const mgx_csr* b);
+int64_t mgx_spgemm_workspace(int64_t n_rows);
+int32_t mgx_spgemm_bound(const mgx_csr* a, const mgx_csr* b, int64_t t1, int64_t t2, void* workspace, void* stream);
+int32_t mgx_spgemm_count(const mgx_csr* a, const mgx_csr* b, int64_t t1, int64_t t2, int64_t w, const int64_t* class_start /* host [6] */,
+                         void* workspace, int64_t* counts, void* stream);
+int32_t mgx_spgemm_fill(const mgx_csr* a, const mgx_csr* b, const float* wa /* may be NULL */, const float* wb /* may be NULL */, int64_t t1,
+                        int64_t t2, int64_t w, const int64_t* class_start /* host [6] */, void* workspace, const int64_t* offsets,
+                        void* c_indices, float* wc /* may be NULL */, void* stream);
+int32_t mgx_spgemm_grad(const mgx_csr* x, const mgx_csr* y, int32_t mode, const float* wy /* may be NULL */, const mgx_csr* c,
+                        const float* d_wc, float* d_wx, void* stream);
+
 /* Sum aggregation of relu(x_u + w_e) messages with NO E-sized temporary (the UDF message of main_dgl_molhiv_gcn.py:37-52 and
  * main_dgl_ppa_gcn.py:44-51 reduced with fn.sum; with scale = NULL upstream's dgl.nn.GINEConv; csrc/gine.hip):
  *   out[v,:] = sum_{e: u->v} s[e] * relu(x[u,:] + w[e,:])             (exactly 0 for a destination without in-edges)
