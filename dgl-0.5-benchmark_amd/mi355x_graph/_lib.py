@@ -105,6 +105,9 @@ SIGNATURES = {
     "mgx_spgemm_count": (_i32, [_csr_p, _csr_p, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "mgx_spgemm_fill": (_i32, [_csr_p, _csr_p, _fp, _fp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _fp, _vp]),
     "mgx_spgemm_grad": (_i32, [_csr_p, _csr_p, _i32, _fp, _csr_p, _fp, _fp, _vp]),
+    "mgx_lstm_agg_supported": (_i32, [_csr_p, _i64]),
+    "mgx_lstm_agg_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _vp]),
+    "mgx_lstm_agg_bwd": (_i32, [_csr_p, _vp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _i64, _fp, _vp]),
     "mgx_gine_supported": (_i32, [_csr_p, _i64]),
     "mgx_gine_workspace": (_i64, [_vp, _i64]),
     "mgx_gine_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _vp, _vp]),

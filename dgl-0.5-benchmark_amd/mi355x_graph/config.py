@@ -50,6 +50,8 @@ SPGEMM_FUSED = True  # the kernels of csrc/spgemm.hip; False: repeat_interleave 
 SPGEMM_T1 = 512      # rows of at most T1 products: a wave and 2 T1 hash slots in LDS each (a power of two in 64 .. 1024)
 SPGEMM_T2 = 2048     # rows of at most T2 products: a workgroup and 2 T2 slots (a power of two, T1 < T2 <= 4096); above: column windows
 SPGEMM_W = 4096      # columns per window of the rows above T2 (a multiple of 32, at most 7168); docs/LOG_spgemm.md has the sweep
+# ---- the "lstm" aggregator (ops.lstm_aggregate, nn.SAGEConv(aggregator_type="lstm"))
+LSTM_AGG_FUSED = True  # the recurrent row walks of csrc/lstm_agg.hip; False: one nn.LSTM call per distinct in-degree over a gathered [B, deg, D] mailbox
 # ---- relu(x_u + w_e) messages summed per destination (ops.gine_sum, nn.GINEConv, graph_classification.py --fused-message)
 GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> relu -> mul -> copy_e/sum through the existing operators
 # ---- sum / mean / var / std / max / min of the same messages at once (ops.multi_aggregate, nn.PNAConv, graph_classification.py --model pna)

@@ -379,8 +379,8 @@ class GATv2Conv(nn.Module):
 class SAGEConv(nn.Module):
     def __init__(self, in_feats, out_feats, aggregator_type, feat_drop=0., bias=True, norm=None, activation=None):
         super(SAGEConv, self).__init__()
-        if aggregator_type not in ("mean", "gcn", "pool"):
-            raise DGLError("Unsupported aggregator type %r on this backend (mean, gcn, pool)" % (aggregator_type,))
+        if aggregator_type not in ("mean", "gcn", "pool", "lstm"):
+            raise DGLError("Unsupported aggregator type %r on this backend (mean, gcn, pool, lstm)" % (aggregator_type,))
         self._in_src_feats, self._in_dst_feats = expand_as_pair(in_feats)
         self._out_feats = out_feats
         self._aggre_type = aggregator_type
@@ -389,6 +389,8 @@ class SAGEConv(nn.Module):
         self.activation = activation
         if aggregator_type == "pool":
             self.fc_pool = Linear(self._in_src_feats, self._in_src_feats)
+        if aggregator_type == "lstm":
+            self.lstm = nn.LSTM(self._in_src_feats, self._in_src_feats, batch_first=True)
         if aggregator_type != "gcn":
             self.fc_self = Linear(self._in_dst_feats, out_feats, bias=bias)
         self.fc_neigh = Linear(self._in_src_feats, out_feats, bias=bias)
@@ -398,6 +400,8 @@ class SAGEConv(nn.Module):
         gain = nn.init.calculate_gain("relu")
         if self._aggre_type == "pool":
             nn.init.xavier_uniform_(self.fc_pool.weight, gain=gain)
+        if self._aggre_type == "lstm":
+            self.lstm.reset_parameters()
         if self._aggre_type != "gcn":
             nn.init.xavier_uniform_(self.fc_self.weight, gain=gain)
         nn.init.xavier_uniform_(self.fc_neigh.weight, gain=gain)
@@ -429,6 +433,9 @@ class SAGEConv(nn.Module):
                 degs = graph.in_degrees().to(feat_dst)
                 h_neigh = (graph.dstdata["neigh"] + graph.dstdata["h"]) / (degs.unsqueeze(-1) + 1)
                 h_neigh = self.fc_neigh(h_neigh)
+            elif self._aggre_type == "lstm":  # the whole recurrence of every row in one launch (csrc/lstm_agg.hip), rows in storage order
+                h_neigh = self.fc_neigh(ops.lstm_aggregate(graph, feat_src, self.lstm.weight_ih_l0, self.lstm.weight_hh_l0,
+                                                           self.lstm.bias_ih_l0, self.lstm.bias_hh_l0))
             else:  # pool
                 graph.srcdata["h"] = F.relu(self.fc_pool(feat_src))
                 graph.update_all(fn.copy_src("h", "m"), fn.max("m", "neigh"))

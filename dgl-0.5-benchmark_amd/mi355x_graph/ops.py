@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "lstm_aggregate", "lstm_aggregate_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -775,6 +775,122 @@ def spgemm(ga, gb, wa=None, wb=None):
     gc = DGLGraph(GraphIndex(ia.num_src, ib.num_dst, csr=c), is_block=ia.num_src != ib.num_dst)
     gc._unibipartite = gc._is_block  # two node sets, not a message-flow block
     return gc, wc
+
+
+class LstmAggregate(torch.autograd.Function):
+    """out[v] = the last h of an LSTM run over the in-edges of v in storage order, from the input projections P [N_src, 4H] of the SOURCE
+    NODES (gate-interleaved columns, see _lstm_interleave) and w_hh [4H, H]: csrc/lstm_agg.hip, one launch forward and one backward for
+    all rows.  With a gradient asked for, keeps the state before every position, two [E, H] tensors; the backward kernel leaves dG [E, 4H]
+    and three existing kernels finish: d w_hh = dG^T h_prev, d P = copy_e / sum of dG over the reversed graph."""
+
+    @staticmethod
+    def forward(ctx, gidx, P, w_hh):
+        P, w_hh = P.contiguous(), w_hh.contiguous()
+        save = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        out, h_prev, c_prev = sparse.backend_for(P).lstm_agg_fwd(gidx.csc(), P, w_hh, save)
+        ctx.gidx = gidx
+        if save:
+            ctx.save_for_backward(P, w_hh, h_prev, c_prev)
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        P, w_hh, h_prev, c_prev = ctx.saved_tensors
+        H = int(w_hh.shape[1])
+        dG = sparse.backend_for(P).lstm_agg_bwd(ctx.gidx.csc(), P, w_hh, h_prev, c_prev, d_out)
+        d_P = d_w = None
+        if ctx.needs_input_grad[1]:
+            d_P = sparse.gspmm_raw(ctx.gidx.csr(), "copy_rhs", "sum", None, dG, dense_out=True)[0]
+        if ctx.needs_input_grad[2]:  # rows 4 j + gate back to nn.LSTM's gate * H + j
+            d_w = _weight_grad(dG, h_prev).view(H, 4, H).transpose(0, 1).reshape(4 * H, H)
+        return None, d_P, d_w
+
+
+def _lstm_interleave(t, H):
+    """t [4H, ...] in nn.LSTM's row order gate * H + j -> rows 4 j + gate: the four gates of a hidden unit side by side, one 16-byte load
+    in the kernels."""
+    return t.view((4, H) + tuple(t.shape[1:])).transpose(0, 1).reshape(t.shape)
+
+
+def _lstm_aggregate_args(graph, x, w_ih, w_hh, b_ih, b_hh):
+    """The graph index of an lstm_aggregate call, or DGLError."""
+    if not isinstance(graph, (DGLGraph, GraphIndex)):
+        raise DGLError("lstm_aggregate: expected a DGLGraph, got %s" % type(graph).__name__)
+    gidx = _gidx(graph)
+    ts = (x, w_ih, w_hh)
+    if not all(torch.is_tensor(t) and t.dim() == 2 and t.is_floating_point() for t in ts):
+        raise DGLError("lstm_aggregate: expected floating-point x [N_src, D], w_ih [4H, D] and w_hh [4H, H], got %s"
+                       % ", ".join(str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__ for t in ts))
+    H = int(w_hh.shape[1])
+    if x.shape[0] != gidx.num_src or H < 1 or w_hh.shape[0] != 4 * H or tuple(w_ih.shape) != (4 * H, x.shape[1]):
+        raise DGLError("lstm_aggregate: expected x [%d, D], w_ih [4H, D] and w_hh [4H, H], got %s, %s and %s"
+                       % (gidx.num_src, tuple(x.shape), tuple(w_ih.shape), tuple(w_hh.shape)))
+    for b in (b_ih, b_hh):
+        if b is not None and not (torch.is_tensor(b) and tuple(b.shape) == (4 * H,)):
+            raise DGLError("lstm_aggregate: expected a bias [%d] or None, got %s" % (4 * H, tuple(b.shape) if torch.is_tensor(b) else type(b).__name__))
+    if any(t is not None and (t.dtype != x.dtype or t.device != x.device) for t in (w_ih, w_hh, b_ih, b_hh)):
+        raise DGLError("lstm_aggregate: operands of different dtypes or devices")
+    return gidx
+
+
+def _lstm_aggregate_kernel_ok(gidx, x, w_hh):
+    if not _device_kernels(x, config.LSTM_AGG_FUSED, "lstm_agg_fwd", "lstm_agg_bwd") or x.dtype != torch.float32 or gidx.num_edges() == 0:
+        return False
+    return sparse.backend_for(x).lstm_agg_supported(gidx.csc(), int(w_hh.shape[1]))
+
+
+def lstm_aggregate_fused(graph, x, w_ih, w_hh, b_ih=None, b_hh=None):
+    """True when lstm_aggregate(graph, x, w_ih, w_hh, b_ih, b_hh) runs the fused kernels (else one LSTM call per distinct in-degree)."""
+    try:
+        return _lstm_aggregate_kernel_ok(_lstm_aggregate_args(graph, x, w_ih, w_hh, b_ih, b_hh), x, w_hh)
+    except DGLError:
+        return False
+
+
+def _lstm_aggregate_composed(gidx, x, w_ih, w_hh, b_ih, b_hh):
+    """What DGL does: the rows bucketed by in-degree (read on the host), a gathered [B, deg, D] mailbox and one LSTM call per bucket, the
+    final h scattered.  The LSTM is ATen's own (a fused cell kernel per step), not the vendor library's, on every device."""
+    csc = gidx.csc()
+    H = int(w_hh.shape[1])
+    indptr, indices = csc.indptr.long(), csc.indices.long()
+    deg = indptr[1:] - indptr[:-1]
+    weights = [w_ih, w_hh]
+    if b_ih is not None or b_hh is not None:
+        weights += [b if b is not None else torch.zeros_like(b_ih if b_ih is not None else b_hh) for b in (b_ih, b_hh)]
+    out = x.new_zeros((gidx.num_dst, H)) + 0 * sum(w.sum() for w in weights) + x[:0].sum()
+    vendor, torch.backends.cudnn.enabled = torch.backends.cudnn.enabled, False
+    try:
+        for d in torch.unique(deg).tolist():
+            if d == 0:
+                continue
+            rows = (deg == d).nonzero().squeeze(1)
+            pos = indptr[rows].unsqueeze(1) + torch.arange(d, device=indptr.device)
+            zeros = x.new_zeros((1, rows.shape[0], H))
+            h_n = torch._VF.lstm(x[indices[pos]], (zeros, zeros), weights, len(weights) == 4, 1, 0.0, False, False, True)[1]
+            out = out.index_copy(0, rows, h_n[0])
+    finally:
+        torch.backends.cudnn.enabled = vendor
+    return out
+
+
+def lstm_aggregate(graph, x, w_ih, w_hh, b_ih=None, b_hh=None):
+    """The "lstm" aggregator of dgl.nn.SAGEConv: for every destination v, from h = c = 0, one LSTM step per in-edge reading x[u], in the
+    in-CSR row's storage order; the result [N_dst, H] is the last h, zeros for a destination without in-edges.
+
+    x: [N_src, D]; w_ih [4H, D], w_hh [4H, H] and the biases [4H] (or None) in nn.LSTM's layout and gate order (i, f, g, o).
+    fp32 device operands with H a multiple of 16 up to 64 on an int32 graph run csrc/lstm_agg.hip (lstm_aggregate_fused): the input
+    projection once per SOURCE NODE by a dense product, then every row's whole recurrence in one launch each way.  Everything else --
+    CPU tensors under a registered CPU backend, other H or dtypes, 64-bit graphs, config.LSTM_AGG_FUSED = False -- buckets the rows by
+    in-degree and runs one LSTM call per bucket on a gathered [B, deg, D] mailbox."""
+    gidx = _lstm_aggregate_args(graph, x, w_ih, w_hh, b_ih, b_hh)
+    H = int(w_hh.shape[1])
+    if not _lstm_aggregate_kernel_ok(gidx, x, w_hh):
+        sparse.backend_for(x)  # no CPU backend: DGLError
+        return _lstm_aggregate_composed(gidx, x, w_ih, w_hh, b_ih, b_hh)
+    bias = b_ih if b_hh is None else b_hh if b_ih is None else b_ih + b_hh
+    P = torch.nn.functional.linear(x, _lstm_interleave(w_ih, H), None if bias is None else _lstm_interleave(bias, H))
+    return LstmAggregate.apply(gidx, P, w_hh)
 
 
 class GineSum(torch.autograd.Function):

@@ -110,7 +110,7 @@ class CsrView(object):
     """An immutable CSR over torch tensors (in-CSR: rows = destination nodes)."""
 
     __slots__ = ("__weakref__", "num_rows", "num_cols", "indptr", "indices", "eids", "_c", "_deg", "_inv_deg", "_plan", "_sm_plan",
-                 "_row_order", "dst_is_src_prefix", "_tile_plan", "_short", "short_hint", "_rows", "_gate", "_head_dn")
+                 "_row_order", "dst_is_src_prefix", "_tile_plan", "_short", "short_hint", "_rows", "_gate", "_head_dn", "_by_degree")
 
     def __init__(self, num_rows, num_cols, indptr, indices, eids):
         self.num_rows, self.num_cols = int(num_rows), int(num_cols)
@@ -130,6 +130,7 @@ class CsrView(object):
         self._head_dn = None  # (matrix, row list, its version, its slots or None): the [N, K] operand ops.SageMeanCatHeadFn's backward gathers over this CSR, kept
                               # zero outside the list between steps (ops._head_dn)
         self.dst_is_src_prefix = False  # block graphs whose destination nodes are the first source nodes
+        self._by_degree = None  # rows_by_degree()
 
     @property
     def nnz(self):
@@ -170,6 +171,13 @@ class CsrView(object):
         if self._inv_deg is None:
             self._inv_deg = backend_for(self.indptr).inv_degrees(self)
         return self._inv_deg
+
+    def rows_by_degree(self):
+        """int32 [num_rows]: the rows by descending length, equal lengths in row order (a stable device sort; nothing is read back, so a
+        captured step records it).  The tile order of csrc/lstm_agg.hip; built once per CSR."""
+        if self._by_degree is None:
+            self._by_degree = torch.sort(self.indptr[1:] - self.indptr[:-1], descending=True, stable=True)[1].to(torch.int32)
+        return self._by_degree
 
     def short_rows(self, width):
         """True when the summing g-SpMM of `width` columns gives the work items a LANE GROUP each (see spmm_plan_for)."""
@@ -1234,6 +1242,37 @@ class HipBackend(object):
                 _lib.check(_lib.lib().mgx_spgemm_grad(ctypes.byref(x.c_struct()), ctypes.byref(y.c_struct()), int(mode), _ptr(wy),
                                                       ctypes.byref(c.c_struct()), _ptr(d_wc), _ptr(d_wx), _stream(dev)))
         return d_wx
+
+    # ---- the "lstm" aggregator (csrc/lstm_agg.hip)
+    @staticmethod
+    def lstm_agg_supported(csc, H):
+        """Shapes mgx_lstm_agg_* takes: an int32 graph, H a multiple of 16 in 16 .. 64."""
+        return bool(_lib.lib().mgx_lstm_agg_supported(ctypes.byref(csc.c_struct()), int(H)))
+
+    def lstm_agg_fwd(self, csc, P, w_hh, save):
+        """P [n_src, 4H] gate-interleaved input projections (column 4 j + gate), w_hh [4H, H], both contiguous -> (out [n_dst, H], h_prev,
+        c_prev): the last h of every row's recurrence and, with `save`, the state before every position, [E, H] by edge id (else None)."""
+        dev = self._check_dev(csc.indptr, P, w_hh)
+        H = int(w_hh.shape[1])
+        out = torch.empty((csc.num_rows, H), dtype=torch.float32, device=dev)  # every row is written, the empty ones with zeros
+        h_prev, c_prev = (torch.empty((csc.nnz, H), dtype=torch.float32, device=dev) for _ in range(2)) if save else (None, None)
+        order = csc.rows_by_degree()
+        with torch.cuda.device(dev), timed_call(dev, kernel="lstm_agg_fwd", H=H, nnz=csc.nnz):
+            _lib.check(_lib.lib().mgx_lstm_agg_fwd(ctypes.byref(csc.c_struct()), _ptr(order), H, _ptr(P), int(P.stride(0)), _ptr(w_hh), _ptr(out),
+                                                   _ptr(h_prev), _ptr(c_prev), _stream(dev)))
+        return out, h_prev, c_prev
+
+    def lstm_agg_bwd(self, csc, P, w_hh, h_prev, c_prev, d_out):
+        """-> dG [E, 4H] by edge id, gate-interleaved like P: the gradient of every position's pre-activation gates."""
+        dev = self._check_dev(csc.indptr, P, w_hh, h_prev, c_prev, d_out)
+        H = int(w_hh.shape[1])
+        d_out = d_out if d_out.stride(1) == 1 and d_out.stride(0) >= H else d_out.contiguous()
+        dG = torch.empty((csc.nnz, 4 * H), dtype=torch.float32, device=dev)
+        order = csc.rows_by_degree()
+        with torch.cuda.device(dev), timed_call(dev, kernel="lstm_agg_bwd", H=H, nnz=csc.nnz):
+            _lib.check(_lib.lib().mgx_lstm_agg_bwd(ctypes.byref(csc.c_struct()), _ptr(order), H, _ptr(P), int(P.stride(0)), _ptr(w_hh),
+                                                   _ptr(h_prev), _ptr(c_prev), _ptr(d_out), int(d_out.stride(0)), _ptr(dG), _stream(dev)))
+        return dG
 
     # ---- sum of relu(x_u + w_e) messages (csrc/gine.hip)
     @staticmethod

@@ -598,6 +598,26 @@ int32_t mgx_spgemm_fill(const mgx_csr* a, const mgx_csr* b, const float* wa /* m
 int32_t mgx_spgemm_grad(const mgx_csr* x, const mgx_csr* y, int32_t mode, const float* wy /* may be NULL */, const mgx_csr* c,
                         const float* d_wc, float* d_wx, void* stream);
 
+/* The "lstm" aggregator of dgl.nn.SAGEConv as one recurrent row walk each way (csrc/lstm_agg.hip).  For every row v of the in-CSR `csc`,
+ * from h = c = 0, one LSTM step per stored position p of the row, in storage order:
+ *   G = P[indices[p]] + h W_hh^T;  i, f, o = sigmoid(G_i, G_f, G_o), g = tanh(G_g);  c = f c + i g;  h = o tanh(c);   out[v] = the last h
+ * (zeros for a row without positions).  P [num_cols, 4H] is the input projection W_ih x_u + b_ih + b_hh of every SOURCE NODE, computed
+ * by the caller, with GATE-INTERLEAVED columns: column 4 j + gate holds gate `gate` (0 .. 3 = i, f, g, o) of hidden unit j; 16-byte
+ * aligned, ldp % 4 == 0.  w_hh [4H, H] dense, in nn.LSTM's layout (rows gate * H + j).  `order` [num_rows]: the rows sorted by
+ * descending length (any order of equal lengths); rows are walked 16 at a time in that order, a wave per tile.
+ *   fwd: out [num_rows, H] dense, every row written.  h_prev / c_prev [nnz, H] (both or neither): the state BEFORE each position,
+ *        stored by edge id (eids[p], or p without eids); with NULL nothing of size nnz is written.
+ *   bwd: dG [nnz, 4H] by edge id, gate-interleaved like P, every row written: the gradient of G at that position given d_out
+ *        [num_rows, H] (row stride ldd).  The caller finishes: d w_hh = dG^T h_prev, d P = the sum of dG over the out-edges of a node.
+ * Supported (mgx_lstm_agg_supported; the rest is MGX_ERR_UNSUPPORTED): 32-bit indices, H a multiple of 16 in 16 .. 64, fewer than 2^30
+ * rows, columns and edges.  No atomics, fixed order: a rerun gives the same bits.  mgx_last_spmm_kernel(): "lstm_agg_fwd" / "lstm_agg_bwd".
+ * Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_lstm_agg_supported(const mgx_csr* csc, int64_t H);
+int32_t mgx_lstm_agg_fwd(const mgx_csr* csc, const int32_t* order, int64_t H, const float* P, int64_t ldp, const float* w_hh, float* out,
+                         float* h_prev /* may be NULL */, float* c_prev /* may be NULL */, void* stream);
+int32_t mgx_lstm_agg_bwd(const mgx_csr* csc, const int32_t* order, int64_t H, const float* P, int64_t ldp, const float* w_hh,
+                         const float* h_prev, const float* c_prev, const float* d_out, int64_t ldd, float* dG, void* stream);
+
 /* Sum aggregation of relu(x_u + w_e) messages with NO E-sized temporary (the UDF message of main_dgl_molhiv_gcn.py:37-52 and
  * main_dgl_ppa_gcn.py:44-51 reduced with fn.sum; with scale = NULL upstream's dgl.nn.GINEConv; csrc/gine.hip):
  *   out[v,:] = sum_{e: u->v} s[e] * relu(x[u,:] + w[e,:])             (exactly 0 for a destination without in-edges)
