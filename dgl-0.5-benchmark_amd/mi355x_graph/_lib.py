@@ -99,6 +99,12 @@ SIGNATURES = {
     "mgx_edge_bilinear": (_i32, [_csr_p, _i64, _i64, _i64, _fp, _i64, _i32, _fp, _i64, _i32, _fp, _i64, _i64, _i64, _fp, _i64, _i64, _i32,
                                  _fp, _i64, _i64, _vp, _vp]),
     "mgx_edge_bilinear_grad_w": (_i32, [_csr_p, _i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _vp, _vp]),
+    "mgx_edge_filter_supported": (_i32, [_csr_p, _i64, _i64]),
+    "mgx_edge_filter_workspace": (_i64, [_i64, _i64]),
+    "mgx_edge_filter_sum": (_i32, [_csr_p, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, _i32, _fp, _i64, _i64, _vp,
+                                   _vp]),
+    "mgx_edge_filter_grad": (_i32, [_csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, _fp, _fp,
+                                    _fp, _fp, _i64, _vp]),
     "mgx_spgemm_supported": (_i32, [_csr_p, _csr_p]),
     "mgx_spgemm_workspace": (_i64, [_i64]),
     "mgx_spgemm_bound": (_i32, [_csr_p, _csr_p, _i64, _i64, _vp, _vp]),

@@ -45,6 +45,9 @@ GATV2_FUSED = True  # the fused walks of csrc/gatv2.hip; False: u_add_v -> leaky
 # ---- edge-conditioned convolution (ops.edge_bilinear, nn.NNConv, graph_classification.py --model mpnn)
 NNCONV_FUSED = True      # the MFMA kernels of csrc/nnconv.hip; False: gather -> h @ Theta -> batched product -> copy_e/sum|mean, an [E, I*O] tensor each way
 NNCONV_ITEM_EDGES = 256  # CSR positions per workgroup of mgx_edge_bilinear: a multiple of 16, at most 256 (docs/LOG_nnconv.md has the sweep)
+# ---- continuous-filter convolution (ops.edge_filter_sum, nn.CFConv)
+CFCONV_FUSED = True       # the chained MFMA GEMMs of csrc/cfconv.hip; False: expansion -> Linear, ssp, Linear, ssp over edges -> u_mul_e/sum|mean, [E, F] tensors each way
+CFCONV_ITEM_EDGES = 256   # CSR positions per wave of mgx_edge_filter_sum / _grad: a multiple of 16, at most 4096 (docs/LOG_cfconv.md has the sweep)
 # ---- sparse x sparse product (ops.spgemm, dgl.adj_product_graph, dgl.metapath_reachable_graph)
 SPGEMM_FUSED = True  # the kernels of csrc/spgemm.hip; False: repeat_interleave -> unique -> index_add, every product materialised
 SPGEMM_T1 = 512      # rows of at most T1 products: a wave and 2 T1 hash slots in LDS each (a power of two in 64 .. 1024)

@@ -742,6 +742,43 @@ class NNConv(nn.Module):
         return rst
 
 
+class ShiftedSoftplus(nn.Module):
+    """dgl.nn.pytorch.conv.cfconv.ShiftedSoftplus: softplus(x) - ln 2 (no parameters)."""
+
+    def forward(self, x):
+        return ops._ssp(x)
+
+
+class CFConv(nn.Module):
+    """dgl.nn.pytorch.CFConv, SchNet's continuous-filter convolution: h_v = project_out(sum_{u->v} project_node(h_u) * project_edge(e_uv)),
+    with DGL's parameters under DGL's names.  The sum and the whole of project_edge are ONE ops.edge_filter_sum call (csrc/cfconv.hip when
+    it takes the shape: no [E, hidden] tensor forward).  rbf=(low, high, gap) is an extension: edge_feats are then distances and the layer
+    expands them itself as dgllife's RBFExpansion does, centers = arange(low, high, gap), gamma = 1 / gap -- in registers on the fused
+    path; edge_in_feats must equal the number of centers."""
+
+    def __init__(self, node_in_feats, edge_in_feats, hidden_feats, out_feats, rbf=None):
+        super(CFConv, self).__init__()
+        self.project_edge = nn.Sequential(nn.Linear(edge_in_feats, hidden_feats), ShiftedSoftplus(),
+                                          nn.Linear(hidden_feats, hidden_feats), ShiftedSoftplus())
+        self.project_node = nn.Linear(node_in_feats, hidden_feats)
+        self.project_out = nn.Sequential(nn.Linear(hidden_feats, out_feats), ShiftedSoftplus())
+        self._gamma = None
+        if rbf is not None:
+            low, high, gap = rbf
+            centers = torch.arange(low, high, gap, dtype=torch.float32)
+            if centers.numel() != edge_in_feats:
+                raise DGLError("CFConv: rbf=(%r, %r, %r) has %d centers, edge_in_feats is %d" % (low, high, gap, centers.numel(), edge_in_feats))
+            self._gamma = 1.0 / gap
+            self.register_buffer("centers", centers, persistent=False)
+
+    def forward(self, g, node_feats, edge_feats):
+        feat_src, _ = expand_as_pair(node_feats, g)
+        lin1, lin2 = self.project_edge[0], self.project_edge[2]
+        rbf = None if self._gamma is None else (self.centers, self._gamma)
+        h = ops.edge_filter_sum(g, self.project_node(feat_src), edge_feats, lin1.weight, lin1.bias, lin2.weight, lin2.bias, rbf)
+        return self.project_out(h)
+
+
 class PNAConvTower(nn.Module):
     """The parameters of one tower of PNAConv (UPSTREAM dgl.nn.pytorch.conv.pnaconv.PNAConvTower: M, U, batchnorm, dropout).  The
     arithmetic is PNAConv.forward's: all towers share one aggregation call."""

@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "lstm_aggregate", "lstm_aggregate_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "edge_filter_sum", "edge_filter_sum_fused", "lstm_aggregate", "lstm_aggregate_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -661,6 +661,127 @@ def edge_bilinear(graph, x, h, weight, bias=None, reduce="sum"):
     if not _edge_bilinear_kernel_ok(gidx, x, h, weight, bias):
         return _edge_bilinear_composed(gidx, x, h, weight, bias, reduce)
     return EdgeBilinear.apply(gidx, x, h, weight, bias, reduce == "mean")
+
+
+class EdgeFilterSum(torch.autograd.Function):
+    """out[v] = sum | mean over e = (u -> v) of x[u] * ssp(ssp(a_e w1^T + b1) w2^T + b2) -- SchNet's continuous-filter convolution with the
+    filter network inside the kernel (csrc/cfconv.hip): two chained MFMA GEMMs per tile of 16 edges, nothing of size E forward.  Saves its
+    inputs only; backward recomputes both stages in one launch that leaves h1, d pre2 and d pre1 [E, F] for mgx_xty / mgx_column_sum, freed
+    on return.  ef and centers get no gradient (ops.edge_filter_sum sends such calls to the composition)."""
+
+    @staticmethod
+    def forward(ctx, gidx, x, ef, w1, b1, w2, b2, centers, gamma, mean):
+        w1, b1, w2, b2 = (None if t is None else t.contiguous() for t in (w1, b1, w2, b2))
+        rbf = None if centers is None else (centers.contiguous(), gamma)
+        out = sparse.backend_for(x).edge_filter_sum(gidx.csc(), x, ef, w1, b1, w2, b2, rbf, mean)
+        ctx.gidx, ctx.mean, ctx.gamma = gidx, mean, gamma
+        ctx.given = [t is not None for t in (b1, b2, centers)]
+        ctx.save_for_backward(*(t for t in (x, ef, w1, w2, b1, b2, centers) if t is not None))
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        saved = list(ctx.saved_tensors)
+        x, ef, w1, w2 = saved[:4]
+        b1, b2, centers = (saved.pop(4) if given else None for given in ctx.given)
+        rbf = None if centers is None else (centers, ctx.gamma)
+        csc, be, need = ctx.gidx.csc(), sparse.backend_for(x), ctx.needs_input_grad
+        g = d_out
+        if ctx.mean:  # the mean's division, once per destination row instead of once per edge
+            g = d_out / csc.degrees().clamp(min=1).to(torch.float32).unsqueeze(1)
+        d_x = be.edge_filter_sum(ctx.gidx.csr(), g, ef, w1, b1, w2, b2, rbf, False) if need[1] else None
+        grads = [None] * 4  # d w1, d b1, d w2, d b2
+        if any(need[3:7]):
+            h1, dp2, dp1, a = be.edge_filter_grad(csc, x, g, ef, w1, b1, w2, b2, rbf)
+            # mgx_xty at every E (not _weight_grad's library GEMM below 65 536 rows): its partial tiles are added in a fixed order, so a
+            # rerun gives the same bits, and as sums of sums they round less than one running sum over E terms
+            for i, (dy, z) in ((0, (dp1, a)), (2, (dp2, h1))):
+                if need[3 + i] and need[4 + i]:
+                    grads[i], grads[i + 1] = be.xty(dy, z, colsum=True)
+                elif need[3 + i]:
+                    grads[i] = be.xty(dy, z)
+                elif need[4 + i]:
+                    grads[i + 1] = be.column_sum(dy)
+        return (None, d_x, None) + tuple(grads) + (None, None, None)
+
+
+def _edge_filter_args(graph, x, ef, w1, b1, w2, b2, rbf, reduce):
+    """(graph index, centers | None, gamma) of an edge_filter_sum call, or DGLError."""
+    if not isinstance(graph, (DGLGraph, GraphIndex)):
+        raise DGLError("edge_filter_sum: expected a DGLGraph, got %s" % type(graph).__name__)
+    gidx = _gidx(graph)
+    _want_tensor("edge_filter_sum", "x [N_src, F], w1 [F, K] and w2 [F, F]", (x, w1, w2), 2)
+    if reduce not in ("sum", "mean"):
+        raise DGLError("edge_filter_sum: reduce must be 'sum' or 'mean', got %r" % (reduce,))
+    centers, gamma = None, 0.0
+    if rbf is not None:
+        if (not isinstance(rbf, (tuple, list)) or len(rbf) != 2 or not torch.is_tensor(rbf[0]) or rbf[0].dim() != 1
+                or isinstance(rbf[1], bool) or not isinstance(rbf[1], (int, float))):
+            raise DGLError("edge_filter_sum: rbf must be (centers [K] tensor, gamma float) or None, got %r" % (rbf,))
+        centers, gamma = rbf[0], float(rbf[1])
+        _want_tensor("edge_filter_sum", "rbf centers [K]", centers, 1)
+    _want_tensor("edge_filter_sum", "distances ef [E] or [E, 1]" if rbf is not None else "ef [E, K]", ef, (1, 2) if rbf is not None else 2)
+    F, K, E = int(x.shape[1]), int(w1.shape[1]), gidx.num_edges()
+    ef_shapes = ((E,), (E, 1)) if rbf is not None else ((E, K),)
+    if (x.shape[0] != gidx.num_src or F < 1 or K < 1 or w1.shape[0] != F or tuple(w2.shape) != (F, F) or tuple(ef.shape) not in ef_shapes
+            or (centers is not None and centers.shape[0] != K)):
+        raise DGLError("edge_filter_sum: expected x [%d, F], ef %s, w1 [F, K] and w2 [F, F], got %s, %s, %s and %s"
+                       % (gidx.num_src, " or ".join(str(list(s)) for s in ef_shapes), tuple(x.shape), tuple(ef.shape), tuple(w1.shape),
+                          tuple(w2.shape)))
+    for b in (b1, b2):
+        if b is not None:
+            _want_tensor("edge_filter_sum", "a bias [F] or None", b, 1)
+            if b.shape[0] != F:
+                raise DGLError("edge_filter_sum: expected a bias [%d] or None, got %s" % (F, tuple(b.shape)))
+    if any(t is not None and t.device != x.device for t in (ef, w1, b1, w2, b2, centers)):
+        raise DGLError("edge_filter_sum: operands on different devices")
+    return gidx, centers, gamma
+
+
+def _edge_filter_kernel_ok(gidx, x, ef, w1, centers):
+    if (not _device_kernels(x, config.CFCONV_FUSED, "edge_filter_sum", "edge_filter_grad") or gidx.num_edges() == 0 or ef.requires_grad
+            or (centers is not None and centers.requires_grad)):
+        return False
+    return sparse.backend_for(x).edge_filter_supported(gidx.csc(), int(w1.shape[0]), int(w1.shape[1]))
+
+
+def edge_filter_sum_fused(graph, x, ef, w1, b1, w2, b2, rbf=None, reduce="sum"):
+    """True when edge_filter_sum(graph, x, ef, w1, b1, w2, b2, rbf, reduce) runs the fused kernels (else it is the operators one by one)."""
+    try:
+        gidx, centers, _ = _edge_filter_args(graph, x, ef, w1, b1, w2, b2, rbf, reduce)
+        return _edge_filter_kernel_ok(gidx, x, ef, w1, centers)
+    except DGLError:
+        return False
+
+
+def _ssp(t):
+    """shifted softplus, SchNet's activation: softplus(t) - ln 2"""
+    return torch.nn.functional.softplus(t) - 0.6931471805599453
+
+
+def _edge_filter_composed(gidx, x, ef, w1, b1, w2, b2, centers, gamma, reduce):
+    """expansion -> Linear, ssp, Linear, ssp over the edges -> u_mul_e / sum|mean: an [E, K] and five [E, F] tensors, most kept for backward."""
+    a = ef if centers is None else torch.exp(-gamma * (ef.reshape(-1, 1) - centers.reshape(1, -1)) ** 2)
+    lin = torch.nn.functional.linear
+    return gspmm(gidx, "mul", reduce, x, _ssp(lin(_ssp(lin(a, w1, b1)), w2, b2)))
+
+
+def edge_filter_sum(graph, x, ef, w1, b1, w2, b2, rbf=None, reduce="sum"):
+    """Continuous-filter convolution (SchNet): out[v,f] = reduce_{e: u->v} x[u,f] * ssp(ssp(a_e w1^T + b1) w2^T + b2)[f], ssp(t) = softplus(t) - ln 2.
+
+    x: [N_src, F]; w1 [F, K], w2 [F, F] in nn.Linear's layout, b1 / b2 [F] or None; fp32.  rbf=None: a_e = ef[e], ef [E, K] by edge id.
+    rbf=(centers [K], gamma): ef holds distances, [E] or [E, 1], and a_e[k] = exp(-gamma (ef[e] - centers[k])^2).  reduce "sum" or "mean";
+    result [N_dst, F], exactly 0 for destinations without in-edges.  Differentiable in x and the four parameters.  Device operands with F
+    a multiple of 16 up to 128 and K <= 128 on an int32 graph run csrc/cfconv.hip (edge_filter_sum_fused): the expansion in registers, no
+    E-sized tensor forward, three transient [E, F] ones in backward.  Everything else -- CPU tensors under a registered CPU backend, 64-bit
+    graphs, other F, an ef or centers that asks for a gradient, config.CFCONV_FUSED = False -- takes the same values through the operators."""
+    gidx, centers, gamma = _edge_filter_args(graph, x, ef, w1, b1, w2, b2, rbf, reduce)
+    if gidx.num_edges() == 0:
+        return _no_edges_zeros((gidx.num_dst, x.shape[1]), x, None) + sum(0 * t.sum() for t in (ef, w1, b1, w2, b2) if t is not None)
+    if not _edge_filter_kernel_ok(gidx, x, ef, w1, centers):
+        return _edge_filter_composed(gidx, x, ef, w1, b1, w2, b2, centers, gamma, reduce)
+    return EdgeFilterSum.apply(gidx, x, ef, w1, b1, w2, b2, centers, gamma, reduce == "mean")
 
 
 class SpGEMM(torch.autograd.Function):

@@ -1189,6 +1189,47 @@ class HipBackend(object):
                                                            _ptr(d_theta), _ptr(d_bias), _ptr(ws), _stream(dev)))
         return d_theta, d_bias
 
+    # ---- continuous-filter convolution (csrc/cfconv.hip)
+    @staticmethod
+    def edge_filter_supported(csr, F, K):
+        """Shapes mgx_edge_filter_* takes: int32 graph with edges, F a multiple of 16 in 16 .. 128, 1 <= K <= 128."""
+        return bool(_lib.lib().mgx_edge_filter_supported(ctypes.byref(csr.c_struct()), int(F), int(K)))
+
+    def edge_filter_sum(self, csr, q2d, ef, w1, b1, w2, b2, rbf, mean):
+        """out[r] = sum | mean over the positions p of row r of q2d[indices[p]] * ssp(ssp(a_p w1^T + b1) w2^T + b2); a_p = ef[eid(p)] ([E, K]),
+        or with rbf = (centers [K], gamma) the expansion of the distances ef [E].  The forward on the in-CSR with q2d = x, d x on the out-CSR
+        with q2d = d out.  Weights contiguous.  -> [csr.num_rows, F], zeros for a row without positions."""
+        dev = self._check_dev(csr.indptr, q2d, ef, w1, b1, w2, b2, rbf[0] if rbf else None)
+        F, K, item = int(w1.shape[0]), int(w1.shape[1]), int(config.CFCONV_ITEM_EDGES)
+        (q, ldq), ef = self._eb_rows(q2d), ef.contiguous()
+        out = torch.zeros((csr.num_rows, F), dtype=torch.float32, device=dev)  # rows without edges are not written
+        size = _lib.lib().mgx_edge_filter_workspace(csr.nnz, item)
+        if size < 0:
+            raise DGLError("edge_filter_sum: config.CFCONV_ITEM_EDGES must be a multiple of 16 in 16 .. 4096, got %r" % (item,))
+        ws = torch.empty(size // 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="edge_filter_sum", F=F, K=K, nnz=csr.nnz):
+            _lib.check(_lib.lib().mgx_edge_filter_sum(ctypes.byref(csr.c_struct()), F, K, _ptr(q), ldq, _ptr(ef), 1 if rbf else K, _ptr(w1),
+                                                      _ptr(b1), _ptr(w2), _ptr(b2), _ptr(rbf[0]) if rbf else None,
+                                                      ctypes.c_float(rbf[1] if rbf else 0.0), 1 if mean else 0, _ptr(out), F, item, _ptr(ws),
+                                                      _stream(dev)))
+        return out
+
+    def edge_filter_grad(self, csc, x2d, g2d, ef, w1, b1, w2, b2, rbf):
+        """-> (h1, d pre2, d pre1, a): [E, F] each, h1 and d pre2 by position of the in-CSR, d pre1 by edge id with a = ef -- in rbf mode d pre1
+        by position with a [E, K] the recomputed expansion.  g2d = d out (divided by the in-degree for mean)."""
+        dev = self._check_dev(csc.indptr, x2d, g2d, ef, w1, b1, w2, b2, rbf[0] if rbf else None)
+        F, K = int(w1.shape[0]), int(w1.shape[1])
+        (x, ldx), (g, ldg), ef = self._eb_rows(x2d), self._eb_rows(g2d), ef.contiguous()
+        h1, dp2, dp1 = (torch.empty((csc.nnz, F), dtype=torch.float32, device=dev) for _ in range(3))
+        a = torch.empty((csc.nnz, K), dtype=torch.float32, device=dev) if rbf else ef
+        with torch.cuda.device(dev), timed_call(dev, kernel="edge_filter_grad", F=F, K=K, nnz=csc.nnz):
+            _lib.check(_lib.lib().mgx_edge_filter_grad(ctypes.byref(csc.c_struct()), _ptr(csc.row_of_position()), F, K, _ptr(x), ldx, _ptr(g), ldg,
+                                                       _ptr(ef), 1 if rbf else K, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2),
+                                                       _ptr(rbf[0]) if rbf else None, ctypes.c_float(rbf[1] if rbf else 0.0), _ptr(h1),
+                                                       _ptr(dp2), _ptr(dp1), _ptr(a) if rbf else None, int(config.CFCONV_ITEM_EDGES),
+                                                       _stream(dev)))
+        return h1, dp2, dp1, a
+
     # ---- sparse x sparse product (csrc/spgemm.hip)
     @staticmethod
     def spgemm_supported(a, b):

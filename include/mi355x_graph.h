@@ -564,6 +564,35 @@ int32_t mgx_edge_bilinear_grad_w(const mgx_csr* csr, int64_t DH, int64_t I, int6
                                  int64_t ldx, const float* g, int64_t ldg, float* d_theta, float* d_bias /* may be NULL */,
                                  void* workspace, void* stream);
 
+/* Continuous-filter convolution (SchNet's layer, dgl.nn.CFConv) with the filter network inside the kernel (csrc/cfconv.hip):
+ *   mgx_edge_filter_sum:  out[row(p), f] (+)= Q[indices[p], f] * ssp( ssp(a_p w1^T + b1) w2^T + b2 )[f]     over the positions p of `csr`
+ * with ssp(t) = softplus(t) - ln 2 = max(t, 0) + log1p(exp(-|t|)) - ln 2 and a_p the edge features of position p: ef[eid(p), 0 .. K)
+ * (row stride ldef; eid(p) = eids[p], or p without eids) when centers is NULL, else exp(-gamma * (ef[eid(p) * ldef] - centers[k])^2),
+ * k < K, formed in registers.  w1 [F, K], w2 [F, F] dense in nn.Linear's layout, b1 / b2 [F] or NULL.  The positions of every CSR row
+ * are added in position order (mean != 0: divided by the row length); a row without positions is NOT written -- pass zeros.  The
+ * forward is the call on the in-CSR with Q = x, d x the call on the out-CSR with Q = d out (divided by the in-degree for mean).
+ *   mgx_edge_filter_grad: over the in-CSR `csc` with row_of_position [nnz] (the row of every position), x gathered by column and g =
+ * d out by row: recomputes pre1 = a w1^T + b1, h1 = ssp(pre1), pre2 = h1 w2^T + b2 and stores, [nnz, F] each, h1 and d_pre2 = x[u] * g[v] *
+ * sigmoid(pre2) by POSITION and d_pre1 = (d_pre2 w2) * sigmoid(pre1) by EDGE ID -- with centers by position, beside expansion [nnz, K] =
+ * a by position (NULL exactly when centers is).  The caller finishes: d w2 = d_pre2^T h1, d w1 = d_pre1^T a, the bias gradients their
+ * column sums.
+ * Every operand is read and written a dword at a time (any alignment); Q, x, g take row strides.  item_edges: CSR positions per wave, a
+ * multiple of 16 in 16 .. 4096.  workspace: mgx_edge_filter_workspace bytes (the [items, 2, 128] partial rows of the rows that straddle
+ * items), -1 for a bad item_edges.  Supported (mgx_edge_filter_supported; the rest is MGX_ERR_UNSUPPORTED): 32-bit indices, nnz > 0, F a
+ * multiple of 16 in 16 .. 128, 1 <= K <= 128, fewer than 2^27 edges and 2^30 rows.  mgx_last_spmm_kernel(): "edge_filter_sum" /
+ * "edge_filter_grad".  Deterministic: no atomics, fixed summation order.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_edge_filter_supported(const mgx_csr* csr, int64_t F, int64_t K);
+int64_t mgx_edge_filter_workspace(int64_t nnz, int64_t item_edges);
+int32_t mgx_edge_filter_sum(const mgx_csr* csr, int64_t F, int64_t K, const float* Q, int64_t ldq, const float* ef, int64_t ldef,
+                            const float* w1, const float* b1 /* may be NULL */, const float* w2, const float* b2 /* may be NULL */,
+                            const float* centers /* may be NULL */, float gamma, int32_t mean, float* out, int64_t ldo,
+                            int64_t item_edges, void* workspace, void* stream);
+int32_t mgx_edge_filter_grad(const mgx_csr* csc, const int32_t* row_of_position, int64_t F, int64_t K, const float* x, int64_t ldx,
+                             const float* g, int64_t ldg, const float* ef, int64_t ldef, const float* w1, const float* b1 /* may be NULL */,
+                             const float* w2, const float* b2 /* may be NULL */, const float* centers /* may be NULL */, float gamma,
+                             float* h1, float* d_pre2, float* d_pre1, float* expansion /* may be NULL */, int64_t item_edges,
+                             void* stream);
+
 /* Sparse x sparse product C = A B of two CSR operands (csrc/spgemm.hip; ops.spgemm, dgl.adj_product_graph,
  * dgl.metapath_reachable_graph).  A is `a` (n rows, k columns), B is `b` (k rows, m columns); for graphs these are the OUT-CSRs, A[src,
  * dst].  Stored entries that repeat a (row, column) pair are separate entries that add.  C has one entry per structural non-zero (kept
