@@ -1,4 +1,4 @@
-from mi355x_graph.nn import GATConv, SAGEConv, GraphConv, AvgPooling, SumPooling, MaxPooling, Linear, HeteroGraphConv, GINConv, BatchNorm1d, RelGraphConv, DotGatConv, GATv2Conv, NNConv, CFConv,GINEConv, PNAConv, TypedLinear, TypedRelGraphConv  # noqa: F401
+from mi355x_graph.nn import GATConv, SAGEConv, GraphConv, AvgPooling, SumPooling, MaxPooling, Linear, HeteroGraphConv, GINConv, BatchNorm1d, RelGraphConv, DotGatConv, GATv2Conv, NNConv, CFConv, GatedGCNConv, GINEConv, PNAConv, TypedLinear, TypedRelGraphConv  # noqa: F401
 from mi355x_graph.nn import GlobalAttentionPooling, Set2Set, WeightAndSum, SortPooling, SetTransformerEncoder, SetTransformerDecoder  # noqa: F401
 from mi355x_graph.nn import KNNGraph, SegmentedKNNGraph, EdgeConv, FixedRadiusNNGraph, PointNetConv, FeaturePropagation  # noqa: F401
 from mi355x_graph.ops import edge_softmax  # noqa: F401

@@ -118,6 +118,11 @@ SIGNATURES = {
     "mgx_gine_workspace": (_i64, [_vp, _i64]),
     "mgx_gine_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _vp, _vp]),
     "mgx_gine_bwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),
+    "mgx_edge_gate_supported": (_i32, [_csr_p, _i64]),
+    "mgx_edge_gate_workspace": (_i64, [_vp, _i64]),
+    "mgx_edge_gate_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _vp, _vp]),
+    "mgx_edge_gate_bwd_dst": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),
+    "mgx_edge_gate_bwd_src": (_i32, [_csr_p, _vp, _i64, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),
     "mgx_multi_agg_supported": (_i32, [_csr_p, _i64]),
     "mgx_multi_agg_workspace": (_i64, [_vp, _i64]),
     "mgx_multi_agg_fwd": (_i32, [_csr_p, _vp, _i64, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, _fp, _fp, _fp, _i64, _vp, _vp, _fp, _vp, _vp]),

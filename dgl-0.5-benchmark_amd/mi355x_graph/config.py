@@ -57,6 +57,8 @@ SPGEMM_W = 4096      # columns per window of the rows above T2 (a multiple of 32
 LSTM_AGG_FUSED = True  # the recurrent row walks of csrc/lstm_agg.hip; False: one nn.LSTM call per distinct in-degree over a gathered [B, deg, D] mailbox
 # ---- relu(x_u + w_e) messages summed per destination (ops.gine_sum, nn.GINEConv, graph_classification.py --fused-message)
 GINE_FUSED = True  # the fused walks of csrc/gine.hip; False: gather -> add -> relu -> mul -> copy_e/sum through the existing operators
+# ---- edge-gated aggregation sum_e sig(e_hat) b_u / (sum_e sig(e_hat) + eps) (ops.edge_gated_sum, nn.GatedGCNConv)
+EDGE_GATED_FUSED = True  # the fused walks of csrc/edgegate.hip; False: u_add_v -> add -> sigmoid -> u_mul_e/sum, copy_e/sum -> divide through the existing operators
 # ---- sum / mean / var / std / max / min of the same messages at once (ops.multi_aggregate, nn.PNAConv, graph_classification.py --model pna)
 MULTI_AGG_FUSED = True  # the fused walks of csrc/multiagg.hip; False: one g-SpMM per aggregate through the existing operators
 # ONE of sum / mean / max / min without edge features is a single g-SpMM as a composition; the fused form walks the graph once as well

@@ -3,6 +3,7 @@
   DotGatConv dgl.nn.pytorch.DotGatConv (u_dot_v SDDMM + edge_softmax + u_mul_e/sum SpMM, fused: ops.dot_attention)
   GATv2Conv  dgl.nn.pytorch.GATv2Conv (u_add_v -> leaky_relu -> feature sum -> edge_softmax -> u_mul_e/sum, fused: ops.gatv2_attention)
   GINEConv   dgl.nn.pytorch.GINEConv (sum of relu(h_u + e_uv) messages, fused: ops.gine_sum)
+  GatedGCNConv   dgl.nn.pytorch.GatedGCNConv (sigmoid-gated mean of B h_u with updated edge features, fused: ops.edge_gated_sum)
   PNAConv    dgl.nn.pytorch.PNAConv (mean / max / min / std ... of one message per edge, fused: ops.multi_aggregate)
   TypedLinear / TypedRelGraphConv   dgl.nn.pytorch.TypedLinear and DGL >= 0.8's RelGraphConv (one weight per type: ops.segment_mm / gather_mm)
   SAGEConv   main_dgl_arxiv_sage_nn.py:9,27-34
@@ -679,6 +680,50 @@ class GINEConv(nn.Module):
         if self.apply_func is not None:
             rst = self.apply_func(rst)
         return rst
+
+
+class GatedGCNConv(nn.Module):
+    """dgl.nn.pytorch.GatedGCNConv (UPSTREAM), the ResGatedGCN layer of Bresson & Laurent with edge features:
+
+        e_hat_uv = D h_u + E h_v + C e_uv,   h_v' = A h_v + sum_u sigmoid(e_hat_uv) * B h_u / (sum_u sigmoid(e_hat_uv) + 1e-6),   e' = e_hat
+
+    then, on both, batch norm, the activation, the residual (when the widths match) and dropout.  forward -> (h, e).
+    The parameter names -- Linear layers A, B, D, E on nodes and C on edges, all with bias, bn_node, bn_edge -- and the argument order
+    follow upstream's layer AS REMEMBERED: they could not be checked against its source where this was written.
+    The four node projections are one GEMM against the concatenated weights; the aggregation is ops.edge_gated_sum (csrc/edgegate.hip
+    when it takes the shape: of the composition's five [E, F] tensors only e_hat is written)."""
+
+    def __init__(self, input_feats, edge_feats, output_feats, dropout=0, batch_norm=True, residual=True, activation=F.relu):
+        super(GatedGCNConv, self).__init__()
+        self.dropout = nn.Dropout(dropout)
+        self.batch_norm = batch_norm
+        self.activation = activation
+        self.residual = residual and input_feats == output_feats
+        self.residual_edge = residual and edge_feats == output_feats
+        self.A = nn.Linear(input_feats, output_feats, bias=True)
+        self.B = nn.Linear(input_feats, output_feats, bias=True)
+        self.C = nn.Linear(edge_feats, output_feats, bias=True)
+        self.D = nn.Linear(input_feats, output_feats, bias=True)
+        self.E = nn.Linear(input_feats, output_feats, bias=True)
+        self.bn_node = nn.BatchNorm1d(output_feats)
+        self.bn_edge = nn.BatchNorm1d(output_feats)
+
+    def forward(self, graph, feat, edge_feat):
+        n_dst = graph.number_of_dst_nodes()
+        nodes = (self.A, self.B, self.D, self.E)
+        proj = F.linear(feat, torch.cat([m.weight for m in nodes]), torch.cat([m.bias for m in nodes]))
+        Ah, Bh, Dh, Eh = proj.chunk(4, dim=1)  # column blocks; the operator's wrappers copy what its kernels cannot read in place
+        h, e = ops.edge_gated_sum(graph, Bh, Dh, Eh[:n_dst], self.C(edge_feat))
+        h = Ah[:n_dst] + h
+        if self.batch_norm:
+            h, e = self.bn_node(h), self.bn_edge(e)
+        if self.activation is not None:
+            h, e = self.activation(h), self.activation(e)
+        if self.residual:
+            h = feat[:n_dst] + h
+        if self.residual_edge:
+            e = edge_feat + e
+        return self.dropout(h), self.dropout(e)
 
 
 class NNConv(nn.Module):

@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "edge_filter_sum", "edge_filter_sum_fused", "lstm_aggregate", "lstm_aggregate_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "edge_filter_sum", "edge_filter_sum_fused", "lstm_aggregate", "lstm_aggregate_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "edge_gated_sum", "edge_gated_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -1090,6 +1090,103 @@ def gine_sum(graph, x, w, scale=None):
             m = m * scale.unsqueeze(-1)
         return gspmm(gidx, "copy_rhs", "sum", None, m)
     return GineSum.apply(gidx, x, w, scale)
+
+
+class EdgeGatedSum(torch.autograd.Function):
+    """(h, e_hat) of edge_gated_sum in one walk of the in-CSR; the backward is one walk of the in-CSR (d c, d d and the [N_dst, F] row
+    gn = d h / (den + eps)) and one of the out-CSR (d s, d b), the gate recomputed from e_hat in both (csrc/edgegate.hip).  Saves b, the
+    two outputs and den [N_dst, F]; writes nothing of size E but e_hat and d c."""
+
+    @staticmethod
+    def forward(ctx, gidx, b, s, d, c, eps):
+        b = b.contiguous()  # saved: a column block of the layer's one projection is copied once, not in both directions
+        h, e_hat, den = sparse.backend_for(b).edge_gate_fwd(gidx.csc(), b, s, d, c, eps)
+        ctx.gidx, ctx.eps = gidx, eps
+        ctx.set_materialize_grads(False)  # an output nobody differentiates arrives as None and its terms are skipped
+        ctx.save_for_backward(b, e_hat, h, den)
+        return h, e_hat
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_h, d_e_hat):
+        b, e_hat, h, den = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if d_h is None and d_e_hat is None:
+            return (None,) * 6
+        d_b, d_s, d_d, d_c = sparse.backend_for(b).edge_gate_bwd(ctx.gidx.csc(), ctx.gidx.csr(), b, e_hat, h, den, ctx.eps, d_h, d_e_hat,
+                                                                 need[1], need[2], need[3], need[4])
+        return None, d_b, d_s, d_d, d_c, None
+
+
+def _edge_gated_args(graph, b, s, d, c, eps):
+    """(graph index, eps as a float) of an edge_gated_sum call, or DGLError."""
+    if not isinstance(graph, (DGLGraph, GraphIndex)):
+        raise DGLError("edge_gated_sum: expected a DGLGraph, got %s" % type(graph).__name__)
+    gidx = _gidx(graph)
+    ts = (b, s, d, c)
+    if not all(torch.is_tensor(t) and t.dim() == 2 for t in ts):
+        raise DGLError("edge_gated_sum: expected b [N_src, F], s [N_src, F], d [N_dst, F] and c [E, F], got %s"
+                       % ", ".join(str(tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__ for t in ts))
+    if any(t.dtype != torch.float32 for t in ts):  # (_want_tensor's dtype message carries no colon after the name)
+        raise DGLError("edge_gated_sum: expected float32 operands, got %s" % " / ".join(str(t.dtype) for t in ts))
+    E, F = gidx.num_edges(), b.shape[1]
+    if (b.shape[0] != gidx.num_src or s.shape[0] != gidx.num_src or d.shape[0] != gidx.num_dst or c.shape[0] != E
+            or any(t.shape[1] != F for t in (s, d, c))):
+        raise DGLError("edge_gated_sum: expected b, s [%d, F], d [%d, F] and c [%d, F], got b %s, s %s, d %s, c %s"
+                       % (gidx.num_src, gidx.num_dst, E, tuple(b.shape), tuple(s.shape), tuple(d.shape), tuple(c.shape)))
+    if any(t.device != b.device for t in (s, d, c)):
+        raise DGLError("edge_gated_sum: operands on different devices")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 <= eps < float("inf"):
+        raise DGLError("edge_gated_sum: eps must be a finite number >= 0, got %r" % (eps,))
+    return gidx, float(eps)
+
+
+def _edge_gated_kernel_ok(gidx, b, s, d, c):
+    if (not _device_kernels(b, config.EDGE_GATED_FUSED, "edge_gate_fwd", "edge_gate_bwd") or gidx.num_edges() == 0
+            or not _aligned16(b, s, d, c)):
+        return False
+    return sparse.backend_for(b).edge_gate_supported(gidx.csc(), int(b.shape[1]))
+
+
+def edge_gated_sum_fused(graph, b, s, d, c, eps=1e-6):
+    """True when edge_gated_sum(graph, b, s, d, c, eps) runs the fused kernels (else it is composed of gsddmm, sigmoid and two gspmm)."""
+    try:
+        gidx, _ = _edge_gated_args(graph, b, s, d, c, eps)
+        return _edge_gated_kernel_ok(gidx, b, s, d, c)
+    except DGLError:
+        return False
+
+
+def _edge_gated_composed(gidx, b, s, d, c, eps):
+    """The same values through the existing operators: u_add_v, add, sigmoid, u_mul_e / sum, copy_e / sum, divide."""
+    e_hat = gsddmm(gidx, "add", s, d, "u", "v") + c
+    sig = torch.sigmoid(e_hat)
+    num = gspmm(gidx, "mul", "sum", b, sig)
+    den = gspmm(gidx, "copy_rhs", "sum", None, sig)
+    empty = (gidx.in_degrees() == 0).to(den.dtype).unsqueeze(-1)  # 0 / (0 + eps + 1): a row without in-edges is 0 with eps = 0 too
+    return num / (den + eps + empty), e_hat
+
+
+def edge_gated_sum(graph, b, s, d, c, eps=1e-6):
+    """The gated aggregation of ResGatedGCN (Bresson & Laurent; upstream's dgl.nn.GatedGCNConv): for every edge e: u -> v
+
+        e_hat[e,:] = (s[u,:] + d[v,:]) + c[e,:],   sig = 1 / (1 + exp(-e_hat)),
+        h[v,:] = (sum_{e into v} sig[e,:] * b[u,:]) / (sum_{e into v} sig[e,:] + eps)
+
+    -> (h [N_dst, F], e_hat [E, F] in edge-id order).  b, s: [N_src, F], d: [N_dst, F], c: [E, F] by edge id, fp32; eps a finite number
+    >= 0.  A destination without in-edges gets exactly 0, also with eps = 0.  Gradients go to b, s, d and c from either output.
+    Device operands (16-byte aligned) with F % 4 == 0 and 4 <= F <= 256 on an int32 graph run csrc/edgegate.hip (edge_gated_sum_fused):
+    one walk forward, two backward, nothing of size E written but e_hat and d c; everything else -- CPU tensors under a registered
+    backend, MGX_TORCH_OPS=1, int64 graphs, other F, config.EDGE_GATED_FUSED = False -- is composed of gsddmm (add), sigmoid, gspmm
+    (mul / sum and copy_rhs / sum) and a divide."""
+    gidx, eps = _edge_gated_args(graph, b, s, d, c, eps)
+    if gidx.num_edges() == 0:
+        tie = b[:0].sum() + s[:0].sum() + d[:0].sum()
+        return b.new_zeros((gidx.num_dst, b.shape[1])) + tie, c + tie
+    if not _edge_gated_kernel_ok(gidx, b, s, d, c):
+        sparse.backend_for(b)  # no CPU backend: DGLError
+        return _edge_gated_composed(gidx, b, s, d, c, eps)
+    return EdgeGatedSum.apply(gidx, b, s, d, c, eps)
 
 
 class MultiAggregate(torch.autograd.Function):

@@ -1403,6 +1403,59 @@ class HipBackend(object):
                                                     _ptr(ws), _stream(dev)))
         return d_x, d_w
 
+    # ---- edge-gated aggregation (csrc/edgegate.hip)
+    @staticmethod
+    def edge_gate_supported(csr, D):
+        """Shapes mgx_edge_gate_* takes: those of gine_supported."""
+        return bool(_lib.lib().mgx_edge_gate_supported(ctypes.byref(csr.c_struct()), D))
+
+    def edge_gate_fwd(self, csc, b2d, s2d, d2d, c2d, eps):
+        """b2d, s2d [n_src, D], d2d [n_dst, D], c2d [E, D] by edge id (any layout: what the kernels cannot read in place is copied,
+        dense16) -> (h [n_dst, D], e_hat [E, D] by edge id, den [n_dst, D])."""
+        dev = self._check_dev(csc.indptr, b2d, s2d, d2d, c2d)
+        b2d, s2d, d2d, c2d = dense16(b2d), dense16(s2d), dense16(d2d), dense16(c2d)
+        D = int(b2d.shape[1])
+        h = torch.empty((csc.num_rows, D), dtype=torch.float32, device=dev)
+        den = torch.empty((csc.num_rows, D), dtype=torch.float32, device=dev)
+        e_hat = torch.empty((csc.nnz, D), dtype=torch.float32, device=dev)
+        plan = csc.plan()
+        ws = self._row_ws(_lib.lib().mgx_edge_gate_workspace, plan, D, dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="edge_gate_fwd", D=D, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
+            _lib.check(_lib.lib().mgx_edge_gate_fwd(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), D, _ptr(b2d), _ptr(s2d), _ptr(d2d),
+                                                    _ptr(c2d), ctypes.c_float(eps), _ptr(h), _ptr(e_hat), _ptr(den), _ptr(ws), _stream(dev)))
+        return h, e_hat, den
+
+    def edge_gate_bwd(self, csc, csr, b2d, e_hat, h, den, eps, d_h, d_e_hat, need_b, need_s, need_d, need_c):
+        """The in-CSR walk (d_c by edge id, d_d, the by-product gn [n_dst, D]) and then the out-CSR walk (d_s, d_b); d_h [n_dst, D] and
+        d_e_hat [E, D] may each be None (not both) -> (d_b, d_s, d_d, d_c), None where not needed.  d_c is formed for d_s as well."""
+        dev = self._check_dev(csc.indptr, csr.indptr, b2d, e_hat, h, den, d_h, d_e_hat)
+        D = int(b2d.shape[1])
+        b2d, d_h, d_e_hat = dense16(b2d), dense16(d_h), dense16(d_e_hat)
+
+        def new(rows, want):
+            return torch.empty((rows, D), dtype=torch.float32, device=dev) if want else None
+        has_dh = d_h is not None
+        walk_b = need_b and has_dh  # without d_h no gradient reaches b: zeros, and neither walk forms sig
+        d_c, d_d, d_s = new(csc.nnz, need_c or need_s), new(csc.num_rows, need_d), new(csr.num_rows, need_s)
+        d_b = new(csr.num_rows, walk_b) if walk_b or not need_b else torch.zeros_like(b2d)
+        gn = None
+        lib = _lib.lib()
+        if d_c is not None or d_d is not None or walk_b:
+            gn = new(csc.num_rows, has_dh)
+            plan = csc.plan()
+            ws = self._row_ws(lib.mgx_edge_gate_workspace, plan, D, dev) if need_d else None
+            with torch.cuda.device(dev), timed_call(dev, kernel="edge_gate_bwd_dst", D=D, nnz=csc.nnz, n_src=csc.num_cols, n_dst=csc.num_rows):
+                _lib.check(lib.mgx_edge_gate_bwd_dst(ctypes.byref(csc.c_struct()), self._plan_ptr(plan), D, _ptr(b2d), _ptr(e_hat), _ptr(h),
+                                                     _ptr(den), ctypes.c_float(eps), _ptr(d_h), _ptr(d_e_hat), _ptr(gn), _ptr(d_c),
+                                                     _ptr(d_d), _ptr(ws), _stream(dev)))
+        if need_s or walk_b:
+            plan = csr.plan()
+            ws = self._row_ws(lib.mgx_edge_gate_workspace, plan, D, dev)
+            with torch.cuda.device(dev), timed_call(dev, kernel="edge_gate_bwd_src", D=D, nnz=csr.nnz, n_src=csr.num_rows, n_dst=csr.num_cols):
+                _lib.check(lib.mgx_edge_gate_bwd_src(ctypes.byref(csr.c_struct()), self._plan_ptr(plan), D, _ptr(e_hat), _ptr(gn), _ptr(d_c),
+                                                     _ptr(d_s), _ptr(d_b if walk_b else None), _ptr(ws), _stream(dev)))
+        return d_b, d_s, d_d, (d_c if need_c else None)
+
     @staticmethod
     def head_dot_supported(H, F):
         return H * F <= 256 and (F <= 64 or F in (128, 256))

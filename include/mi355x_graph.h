@@ -727,6 +727,41 @@ int32_t mgx_multi_agg_bwd(const mgx_csr* csr /* transpose: rows = sources */, co
                           const float* g_max, const int32_t* arg_max, const float* g_min, const int32_t* arg_min,
                           float* d_x /* or NULL */, float* d_w /* or NULL */, void* workspace, void* stream);
 
+/* Edge-gated aggregation (ResGatedGCN; upstream's dgl.nn.GatedGCNConv) with ONE E-sized tensor each way (csrc/edgegate.hip):
+ *   e_hat[e,:] = (s[u,:] + d[v,:]) + c[e,:]   for e: u -> v, in this order of additions; c and e_hat by EDGE ID as in mgx_gine_*
+ *   sig = 1 / (1 + exp(-e_hat)),   den[v,:] = sum_{e into v} sig[e,:],   h[v,:] = (sum_{e into v} sig[e,:] * b[u,:]) / (den[v,:] + eps)
+ *   A destination without in-edges gets h = den = 0 exactly, also with eps = 0.
+ *   fwd:     ONE walk of the in-CSR `csc`: d[v] held per work item, s[u], b[u], c[eid] gathered per edge, e_hat[eid] stored once, the
+ *            numerator and den kept in registers, the division in the row epilogue.  The chunks of a split row leave both sums in
+ *            their slots; the merge adds them in slot order and divides afterwards.  Writes h, e_hat and den (kept for the backward).
+ *   bwd_dst: the in-CSR again.  Per row gn = d_h / (den + eps), gd = -gn * h; per edge, with sig recomputed from the stored e_hat,
+ *              t = (gn * b[u] + gd) * sig * (1 - sig) + d_e_hat[eid],   d_c[eid] = t (once per edge),   d_d[v] = sum_{e into v} t.
+ *            gn [num_rows, D] is written for bwd_src (0 for a row without in-edges).  d_h NULL: t = d_e_hat[eid] and b, e_hat, h, den,
+ *            gn are not touched.  d_e_hat NULL means 0; one of d_h, d_e_hat is required.  d_c and d_d may each be NULL.
+ *   bwd_src: ONE walk of the transpose `csr` (rows = sources, the same edge ids), where every edge is met exactly once:
+ *              d_s[u] = sum_{e out of u} d_c[eid],   d_b[u] = sum_{e out of u} sig[e] * gn[v]     (0 for a source without out-edges).
+ *            d_s and d_b may each be NULL; d_s needs d_c, d_b needs e_hat and gn (after a bwd_dst WITH d_h).
+ * b, s [csc->num_cols, D]; d, h, den, gn, d_h, d_d [csc->num_rows, D]; c, e_hat, d_e_hat, d_c [nnz, D]; d_s, d_b [csr->num_rows, D]:
+ * fp32, dense, 16-byte aligned, allocated by the caller.  eps is finite and >= 0.
+ * Supported (mgx_edge_gate_supported), the set of mgx_gine_supported: D % 4 == 0 and 4 <= D <= 256, 32-bit indices, nnz > 0, and
+ * max(num_rows, num_cols, nnz) * D * 4 below 4 GiB.  Errors as mgx_gine_*: a D that is no positive multiple of 4, NULL or misaligned
+ * operands, a bad eps and a malformed plan are MGX_ERR_INVALID_ARGUMENT, what lies outside the supported set MGX_ERR_UNSUPPORTED.
+ * plan: the CSR's mgx_spmm_plan or NULL; workspace: mgx_edge_gate_workspace(plan, D) bytes -- [slots, 2, D] -- NULL when the plan
+ * splits no row.  Nothing is read back to the host: every entry point can be captured in a graph.
+ * mgx_last_spmm_kernel(): "edge_gate_fwd" / "edge_gate_bwd_dst" / "edge_gate_bwd_src" after the respective launch.
+ * Deterministic: no atomics, lane groups merged in a fixed order, hub chunks in slot order.  Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_edge_gate_supported(const mgx_csr* csr, int64_t D);
+int64_t mgx_edge_gate_workspace(const mgx_spmm_plan* plan /* may be NULL */, int64_t D);
+int32_t mgx_edge_gate_fwd(const mgx_csr* csc, const mgx_spmm_plan* plan /* may be NULL */, int64_t D, const float* b, const float* s,
+                          const float* d, const float* c /* [nnz, D] by edge id */, float eps, float* h, float* e_hat /* [nnz, D] by edge id */,
+                          float* den, void* workspace, void* stream);
+int32_t mgx_edge_gate_bwd_dst(const mgx_csr* csc, const mgx_spmm_plan* plan /* may be NULL */, int64_t D, const float* b, const float* e_hat,
+                              const float* h, const float* den, float eps, const float* d_h /* or NULL */, const float* d_e_hat /* or NULL */,
+                              float* gn, float* d_c /* or NULL */, float* d_d /* or NULL */, void* workspace, void* stream);
+int32_t mgx_edge_gate_bwd_src(const mgx_csr* csr /* transpose: rows = sources */, const mgx_spmm_plan* plan /* may be NULL */, int64_t D,
+                              const float* e_hat, const float* gn, const float* d_c, float* d_s /* or NULL */, float* d_b /* or NULL */,
+                              void* workspace, void* stream);
+
 /* ------------------------------------------------------------------ GAT attention terms
  * el[n,h] = sum_f feat[n,h,f] * attn[h,f] -- GATConv's `(feat * attn_l).sum(-1)` (main_dgl_reddit_gat.py:10, UPSTREAM
  * dgl.nn.pytorch.GATConv.forward), one pass; attn_b/out_b (may be NULL) apply a second attention vector to the same
