@@ -105,6 +105,12 @@ SIGNATURES = {
                                    _vp]),
     "mgx_edge_filter_grad": (_i32, [_csr_p, _vp, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _fp, ctypes.c_float, _fp, _fp,
                                     _fp, _fp, _i64, _vp]),
+    "mgx_edge_mlp_supported": (_i32, [_csr_p, _i64, _i64, _i64, _i64]),
+    "mgx_edge_mlp_workspace": (_i64, [_i64, _i64]),
+    "mgx_edge_mlp_reduce": (_i32, [_csr_p, _vp, _i64, _i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _i32, _fp, _i64, _vp, _i64, _vp,
+                                   _vp]),
+    "mgx_edge_mlp_grad": (_i32, [_csr_p, _vp, _i64, _i64, _i64, _i64, _fp, _i64, _fp, _i64, _fp, _fp, _fp, _fp, _i32, _fp, _i64, _vp, _fp, _fp,
+                                 _fp, _fp, _fp, _fp, _i64, _vp]),
     "mgx_spgemm_supported": (_i32, [_csr_p, _csr_p]),
     "mgx_spgemm_workspace": (_i64, [_i64]),
     "mgx_spgemm_bound": (_i32, [_csr_p, _csr_p, _i64, _i64, _vp, _vp]),

@@ -48,6 +48,12 @@ NNCONV_ITEM_EDGES = 256  # CSR positions per workgroup of mgx_edge_bilinear: a m
 # ---- continuous-filter convolution (ops.edge_filter_sum, nn.CFConv)
 CFCONV_FUSED = True       # the chained MFMA GEMMs of csrc/cfconv.hip; False: expansion -> Linear, ssp, Linear, ssp over edges -> u_mul_e/sum|mean, [E, F] tensors each way
 CFCONV_ITEM_EDGES = 256   # CSR positions per wave of mgx_edge_filter_sum / _grad: a multiple of 16, at most 4096 (docs/LOG_cfconv.md has the sweep)
+# ---- a one- or two-layer MLP on every edge under a max or a sum (ops.edge_mlp_reduce, nn.PointNetConv with 2 or 3 layers)
+EDGE_MLP_FUSED = True       # the chained MFMA GEMMs of csrc/edgemlp.hip; False: u_sub_v -> relu -> (Linear, relu) over edges -> copy_e/max|sum, [E, H] tensors each way
+EDGE_MLP_GRAD_MAX_EDGES = 262144  # a call that asks for a gradient runs the kernels only on fewer edges than this: forward + backward they measured 1.36x
+                                  # faster than the composition at 78 336 edges and 0.79 - 0.84x at 262 144, 524 288 and 1 000 000 (docs/LOG_edgemlp.md);
+                                  # without a gradient they are 1.9 - 4.2x faster at every size and always run
+EDGE_MLP_ITEM_EDGES = 256   # CSR positions per wave of mgx_edge_mlp_reduce / _grad: a multiple of 16, at most 4096 (docs/LOG_edgemlp.md has the sweep)
 # ---- sparse x sparse product (ops.spgemm, dgl.adj_product_graph, dgl.metapath_reachable_graph)
 SPGEMM_FUSED = True  # the kernels of csrc/spgemm.hip; False: repeat_interleave -> unique -> index_add, every product materialised
 SPGEMM_T1 = 512      # rows of at most T1 products: a wave and 2 T1 hash slots in LDS each (a power of two in 64 .. 1024)

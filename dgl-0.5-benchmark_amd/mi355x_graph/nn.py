@@ -1367,6 +1367,8 @@ class PointNetConv(nn.Module):
     The first Linear is pulled to the nodes as EdgeConv's is: W [h_j | pos_j - pos_i] + b = (W_h h_j + W_p pos_j) - (W_p pos_i - b).
     With one layer and no batch norm (config.POINTNETCONV_FUSED) the ReLU commutes with the max, so the layer is a GEMM over the N
     points, the copy_u / max g-SpMM (gradient through its arg) and M-row arithmetic: no tensor of E rows exists in either direction.
+    With two or three layers and no batch norm (the same switch) the remaining Linears run inside ops.edge_mlp_reduce (csrc/edgemlp.hip
+    for the widths it takes: no tensor of E rows forward).
     With more layers or batch norm: the u_sub_v g-SDDMM of the two node projections, the remaining Linears over the edges, copy_e / max.
     The repeated first point of a padded ball changes nothing under the max."""
 
@@ -1404,6 +1406,9 @@ class PointNetConv(nn.Module):
                 g.srcdata["u"] = u
                 g.update_all(fn.copy_u("u", "m"), fn.max("m", "m"))
                 rst = F.relu(g.dstdata["m"] - v)
+            elif len(self.layers) in (2, 3) and not self.batch_norm and config.POINTNETCONV_FUSED:
+                rest = self.layers[1:]
+                rst = ops.edge_mlp_reduce(g, u, v, [layer.weight for layer in rest], [layer.bias for layer in rest], "max")
             else:
                 g.srcdata["u"], g.dstdata["v"] = u, v
                 g.apply_edges(fn.u_sub_v("u", "v", "e"))

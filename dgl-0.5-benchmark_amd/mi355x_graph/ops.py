@@ -21,7 +21,7 @@ from . import sparse
 from . import config
 from .graph import DGLGraph, GraphIndex
 
-__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "edge_filter_sum", "edge_filter_sum_fused", "lstm_aggregate", "lstm_aggregate_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "edge_gated_sum", "edge_gated_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
+__all__ = ["gspmm", "rel_gspmm", "gsddmm", "edge_softmax", "gat_attention", "gat_fused", "dot_attention", "dot_attention_fused", "gatv2_attention", "gatv2_attention_fused", "edge_bilinear", "edge_bilinear_fused", "edge_filter_sum", "edge_filter_sum_fused", "edge_mlp_reduce", "edge_mlp_reduce_fused", "lstm_aggregate", "lstm_aggregate_fused", "spgemm", "spgemm_fused", "gine_sum", "gine_sum_fused", "edge_gated_sum", "edge_gated_sum_fused", "multi_aggregate", "multi_aggregate_fused", "segment_reduce", "segment_softmax", "segment_attention", "segment_attention_fused", "segment_topk", "segment_topk_fused", "segment_knn", "segment_knn_fused", "segment_knn_query", "segment_knn_query_fused", "segment_fps", "segment_fps_fused", "segment_ball_query", "segment_ball_query_fused", "segment_mm", "segment_mm_fused", "gather_mm", "gather_mm_fused", "segment_mha", "segment_mha_fused", "copy_u_sum", "copy_u_mean", "u_mul_e_sum",
            "copy_e_sum", "u_add_v", "u_dot_v"]
 
 
@@ -782,6 +782,125 @@ def edge_filter_sum(graph, x, ef, w1, b1, w2, b2, rbf=None, reduce="sum"):
     if not _edge_filter_kernel_ok(gidx, x, ef, w1, centers):
         return _edge_filter_composed(gidx, x, ef, w1, b1, w2, b2, centers, gamma, reduce)
     return EdgeFilterSum.apply(gidx, x, ef, w1, b1, w2, b2, centers, gamma, reduce == "mean")
+
+
+class EdgeMlpReduce(torch.autograd.Function):
+    """out[i] = max | sum over the in-edges p of i of e_L[p], e_0 = relu(u[src] - v[dst]), e_l = relu(e_{l-1} W_l^T + b_l), with the edge
+    network inside the kernel (csrc/edgemlp.hip): chained MFMA GEMMs per tile of 16 edges, nothing of size E forward.  Saves its inputs and,
+    under max, the arg positions [M, H_L]; backward recomputes the stages in one launch that leaves e_{l-1} and d pre_l [E, H] for mgx_xty /
+    mgx_column_sum and d e_0 [E, H0] for the two summing g-SpMMs, freed on return."""
+
+    @staticmethod
+    def forward(ctx, gidx, u, v, sum_, L, *params):
+        weights = [w.contiguous() for w in params[:L]]
+        biases = [None if b is None else b.contiguous() for b in params[L:]]
+        out, arg = sparse.backend_for(u).edge_mlp_reduce(gidx.csc(), u, v, weights, biases, sum_)
+        ctx.gidx, ctx.sum, ctx.L, ctx.given = gidx, sum_, L, [b is not None for b in biases]
+        ctx.save_for_backward(*([u, v] + weights + [b for b in biases if b is not None] + ([] if sum_ else [arg])))
+        return out
+
+    @staticmethod
+    @once_differentiable  # raw kernels inside: second-order gradients would silently be wrong
+    def backward(ctx, d_out):
+        saved, L = list(ctx.saved_tensors), ctx.L
+        u, v, weights = saved[0], saved[1], saved[2:2 + L]
+        rest = saved[2 + L:]
+        biases = [rest.pop(0) if given else None for given in ctx.given]
+        arg = None if ctx.sum else rest.pop(0)
+        be, need = sparse.backend_for(u), ctx.needs_input_grad
+        e0, de0, e1, dp1, dpl = be.edge_mlp_grad(ctx.gidx.csc(), u, v, weights, biases, ctx.sum, d_out, arg)
+        d_u = _raw_gspmm(ctx.gidx.csr(), "copy_rhs", "sum", None, de0)[0] if need[1] else None
+        d_v = -_raw_gspmm(ctx.gidx.csc(), "copy_rhs", "sum", None, de0)[0] if need[2] else None
+        grads = [None] * (2 * L)  # d W_1 .. d W_L, d b_1 .. d b_L
+        # mgx_xty at every E, as EdgeFilterSum does: its partial tiles are added in a fixed order, so a rerun gives the same bits
+        for l, (dy, z) in enumerate(((dpl, e0),) if L == 1 else ((dp1, e0), (dpl, e1))):
+            want_w, want_b = need[5 + l], ctx.given[l] and need[5 + L + l]
+            if want_w and want_b:
+                grads[l], grads[L + l] = be.xty(dy, z, colsum=True)
+            elif want_w:
+                grads[l] = be.xty(dy, z)
+            elif want_b:
+                grads[L + l] = be.column_sum(dy)
+        return (None, d_u, d_v, None, None) + tuple(grads)
+
+
+def _edge_mlp_args(graph, u, v, weights, biases, reduce):
+    """(graph index, weights, biases as lists) of an edge_mlp_reduce call, or DGLError."""
+    if not isinstance(graph, (DGLGraph, GraphIndex)):
+        raise DGLError("edge_mlp_reduce: expected a DGLGraph, got %s" % type(graph).__name__)
+    gidx = _gidx(graph)
+    if reduce not in ("max", "sum"):
+        raise DGLError("edge_mlp_reduce: reduce must be 'max' or 'sum', got %r" % (reduce,))
+    if not isinstance(weights, (list, tuple)) or len(weights) < 1:
+        raise DGLError("edge_mlp_reduce: weights must be a list of at least one [H_l, H_{l-1}] tensor, got %r" % (weights,))
+    weights = list(weights)
+    biases = [None] * len(weights) if biases is None else list(biases) if isinstance(biases, (list, tuple)) else None
+    if biases is None or len(biases) != len(weights):
+        raise DGLError("edge_mlp_reduce: biases must be a list with one entry (a tensor or None) per weight")
+    _want_tensor("edge_mlp_reduce", "u [N_src, H0], v [N_dst, H0] and weights [H_l, H_{l-1}]", (u, v) + tuple(weights), 2)
+    if u.shape[0] != gidx.num_src or v.shape[0] != gidx.num_dst or v.shape[1] != u.shape[1] or u.shape[1] < 1:
+        raise DGLError("edge_mlp_reduce: expected u [%d, H0] and v [%d, H0], got %s and %s"
+                       % (gidx.num_src, gidx.num_dst, tuple(u.shape), tuple(v.shape)))
+    fan = int(u.shape[1])
+    for w, b in zip(weights, biases):
+        if w.shape[1] != fan or w.shape[0] < 1:
+            raise DGLError("edge_mlp_reduce: expected a weight [H, %d], got %s" % (fan, tuple(w.shape)))
+        fan = int(w.shape[0])
+        if b is not None:
+            _want_tensor("edge_mlp_reduce", "a bias [H] or None", b, 1)
+            if b.shape[0] != fan:
+                raise DGLError("edge_mlp_reduce: expected a bias [%d] or None, got %s" % (fan, tuple(b.shape)))
+    if any(t is not None and t.device != u.device for t in [v] + weights + biases):
+        raise DGLError("edge_mlp_reduce: operands on different devices")
+    return gidx, weights, biases
+
+
+def _edge_mlp_kernel_ok(gidx, u, v, weights, biases):
+    if not _device_kernels(u, config.EDGE_MLP_FUSED, "edge_mlp_reduce", "edge_mlp_grad") or gidx.num_edges() == 0:
+        return False
+    if (gidx.num_edges() >= config.EDGE_MLP_GRAD_MAX_EDGES and torch.is_grad_enabled()
+            and any(t is not None and t.requires_grad for t in [u, v] + weights + biases)):
+        return False  # the measured losing region: forward + backward on this many edges
+    if any(t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16 for t in (u, v)):
+        return False  # the kernels read 16 bytes per lane along a row
+    return sparse.backend_for(u).edge_mlp_supported(gidx.csc(), [int(u.shape[1])] + [int(w.shape[0]) for w in weights])
+
+
+def edge_mlp_reduce_fused(graph, u, v, weights, biases=None, reduce="max"):
+    """True when edge_mlp_reduce(graph, u, v, weights, biases, reduce) runs the fused kernels (else it is the operators one by one)."""
+    try:
+        gidx, weights, biases = _edge_mlp_args(graph, u, v, weights, biases, reduce)
+        return _edge_mlp_kernel_ok(gidx, u, v, weights, biases)
+    except DGLError:
+        return False
+
+
+def _edge_mlp_composed(gidx, u, v, weights, biases, reduce):
+    """u_sub_v -> relu -> (Linear, relu) over the edges -> copy_e / max|sum: an [E, H] tensor per step, all kept for backward."""
+    e = torch.relu(gsddmm(gidx, "sub", u, v, "u", "v"))
+    for w, b in zip(weights, biases):
+        e = torch.relu(torch.nn.functional.linear(e, w, b))
+    return gspmm(gidx, "copy_rhs", reduce, None, e)
+
+
+def edge_mlp_reduce(graph, u, v, weights, biases=None, reduce="max"):
+    """An MLP on every edge under a max or a sum (the PointNet++ set-abstraction message, DGCNN-style edge networks), the first Linear
+    already pulled to the nodes: e_0 = relu(u[src] - v[dst]), e_l = relu(e_{l-1} W_l^T + b_l) for l = 1 .. L, out[i] = reduce over the
+    in-edges of i of e_L, per column.
+
+    u: [N_src, H0], v: [N_dst, H0]; weights: a list of L >= 1 tensors [H_l, H_{l-1}] in nn.Linear's layout, biases: a list of [H_l]
+    tensors or None entries (None: no biases); fp32.  reduce "max" or "sum"; result [N_dst, H_L], exactly 0 for destinations without
+    in-edges.  Under max the gradient goes through the FIRST in-edge (in-CSR order) that attains a column's maximum, as copy_e / max's
+    does.  Differentiable in u, v and every parameter.  Device operands with L = 1 or 2, H0 and the hidden width multiples of 16 up to 128
+    and H_L one up to 256, u and v with unit column stride and 16-byte aligned rows, on an int32 graph run csrc/edgemlp.hip
+    (edge_mlp_reduce_fused): no E-sized tensor forward, transient [E, H] ones in backward; a call that asks for a gradient only on fewer
+    than config.EDGE_MLP_GRAD_MAX_EDGES edges (beyond, forward + backward measured slower than the composition).  Everything else -- CPU tensors under a
+    registered CPU backend, 64-bit graphs, other widths or depths, config.EDGE_MLP_FUSED = False -- takes the same values through the
+    operators."""
+    gidx, weights, biases = _edge_mlp_args(graph, u, v, weights, biases, reduce)
+    if not _edge_mlp_kernel_ok(gidx, u, v, weights, biases):
+        return _edge_mlp_composed(gidx, u, v, weights, biases, reduce)
+    return EdgeMlpReduce.apply(gidx, u, v, reduce == "sum", len(weights), *(weights + biases))
 
 
 class SpGEMM(torch.autograd.Function):

@@ -1230,6 +1230,56 @@ class HipBackend(object):
                                                        _stream(dev)))
         return h1, dp2, dp1, a
 
+    # ---- an MLP on every edge under a max or a sum (csrc/edgemlp.hip)
+    @staticmethod
+    def edge_mlp_supported(csc, widths):
+        """Shapes mgx_edge_mlp_* takes: int32 graph with edges, widths = [H0, H1] or [H0, H1, H2], multiples of 16, the last at most 256
+        and the others at most 128."""
+        L = len(widths) - 1
+        return bool(L in (1, 2) and _lib.lib().mgx_edge_mlp_supported(ctypes.byref(csc.c_struct()), L, int(widths[0]), int(widths[1]),
+                                                                      int(widths[-1])))
+
+    @staticmethod
+    def _edge_mlp_head(csc, u, v, weights, biases):
+        """the arguments both entry points start with; u and v as the predicate of ops.edge_mlp_reduce admits them"""
+        w2, b2 = (weights[1], biases[1]) if len(weights) == 2 else (None, None)
+        return (ctypes.byref(csc.c_struct()), _ptr(csc.row_of_position()), len(weights), int(u.shape[1]), int(weights[0].shape[0]),
+                int(weights[-1].shape[0]), _ptr(u), int(u.stride(0)), _ptr(v), int(v.stride(0)), _ptr(weights[0]), _ptr(biases[0]), _ptr(w2),
+                _ptr(b2))
+
+    def edge_mlp_reduce(self, csc, u, v, weights, biases, sum_):
+        """out[r] = max | sum over the positions p of row r of e_L[p], e_0 = relu(u[indices[p]] - v[r]), e_l = relu(e_{l-1} W_l^T + b_l);
+        weights (one or two, contiguous) and biases (None entries allowed) as lists.  -> (out [num_rows, H_L], zeros for a row without
+        positions; arg [num_rows, H_L] int32, the first position of every maximum, None for sum)."""
+        dev = self._check_dev(csc.indptr, u, v, *weights, *biases)
+        HL, item = int(weights[-1].shape[0]), int(config.EDGE_MLP_ITEM_EDGES)
+        out = torch.zeros((csc.num_rows, HL), dtype=torch.float32, device=dev)  # rows without edges are not written
+        arg = None if sum_ else torch.empty((csc.num_rows, HL), dtype=torch.int32, device=dev)
+        size = _lib.lib().mgx_edge_mlp_workspace(csc.nnz, item)
+        if size < 0:
+            raise DGLError("edge_mlp_reduce: config.EDGE_MLP_ITEM_EDGES must be a multiple of 16 in 16 .. 4096, got %r" % (item,))
+        ws = torch.empty(size // 4, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), timed_call(dev, kernel="edge_mlp_reduce", H0=int(u.shape[1]), HL=HL, nnz=csc.nnz):
+            _lib.check(_lib.lib().mgx_edge_mlp_reduce(*self._edge_mlp_head(csc, u, v, weights, biases), 1 if sum_ else 0, _ptr(out), HL,
+                                                      _ptr(arg), item, _ptr(ws), _stream(dev)))
+        return out, arg
+
+    def edge_mlp_grad(self, csc, u, v, weights, biases, sum_, g2d, arg):
+        """-> (e0 [E, H0], d e0 [E, H0], e1 | None, d pre1 | None [E, H1], d preL [E, H_L]): d e0 by edge id, the rest by position of the
+        in-CSR; e1 and d pre1 with two layers only.  g2d = d out, arg the forward's (None for sum)."""
+        dev = self._check_dev(csc.indptr, u, v, g2d, arg, *weights, *biases)
+        H0, H1, HL, E = int(u.shape[1]), int(weights[0].shape[0]), int(weights[-1].shape[0]), csc.nnz
+        g, ldg = self._eb_rows(g2d)
+        new = lambda width: torch.empty((E, width), dtype=torch.float32, device=dev)
+        e0, de0, dpl = new(H0), new(H0), new(HL)
+        e1, dp1 = (new(H1), new(H1)) if len(weights) == 2 else (None, None)
+        acc = None if HL <= 128 else dp1 if dp1 is not None else new(H0)  # the sum over the slabs of the last layer's columns
+        with torch.cuda.device(dev), timed_call(dev, kernel="edge_mlp_grad", H0=H0, HL=HL, nnz=E):
+            _lib.check(_lib.lib().mgx_edge_mlp_grad(*self._edge_mlp_head(csc, u, v, weights, biases), 1 if sum_ else 0, _ptr(g), ldg, _ptr(arg),
+                                                    _ptr(e0), _ptr(de0), _ptr(e1), _ptr(dp1), _ptr(dpl), _ptr(acc),
+                                                    int(config.EDGE_MLP_ITEM_EDGES), _stream(dev)))
+        return e0, de0, e1, dp1, dpl
+
     # ---- sparse x sparse product (csrc/spgemm.hip)
     @staticmethod
     def spgemm_supported(a, b):

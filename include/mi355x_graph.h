@@ -593,6 +593,34 @@ int32_t mgx_edge_filter_grad(const mgx_csr* csc, const int32_t* row_of_position,
                              float* h1, float* d_pre2, float* d_pre1, float* expansion /* may be NULL */, int64_t item_edges,
                              void* stream);
 
+/* A one- or two-layer MLP on every edge under a max or a sum (PointNet++ set abstraction, dgl.nn.PointNetConv), the edge network inside
+ * the kernel (csrc/edgemlp.hip), over the in-CSR `csc` with row_of_position [nnz] (the row of every position):
+ *   e_0[p] = relu(u[indices[p]] - v[row(p)]),   e_l = relu(e_{l-1} W_l^T + b_l),  l = 1 .. layers (1 or 2),
+ *   mgx_edge_mlp_reduce: out[r, f] = max (sum = 0) or sum (sum = 1) of e_L[p, f] over the positions p of row r; a row without positions is
+ *     NOT written (pass zeros).  Under max arg [num_rows, HL] (int32, dense) receives the FIRST position that attains the maximum.
+ *   mgx_edge_mlp_grad: recomputes the stages and forms, from g = d out and the forward's arg (max: a position takes g[r, f] where arg[r, f]
+ *     is that position and e_L > 0; sum: every position where e_L > 0), by position e0 [nnz, H0], d_preL [nnz, HL] and, with two layers, e1
+ *     and d_pre1 [nnz, H1]; by edge id d_e0 [nnz, H0] -- what mgx_xty / mgx_column_sum and the summing g-SpMMs turn into the gradients of the
+ *     weights, biases, u and v.  acc: [nnz, H1] (two layers; d_pre1 itself may be passed) or [nnz, H0] (one layer) when HL > 128, else NULL.
+ * u [num_cols, H0] and v [num_rows, H0]: row strides ldu / ldv multiples of 4 floats, 16-byte aligned bases.  w1 [H1 | HL, H0] and w2
+ * [HL, H1] dense in nn.Linear's layout, biases may be NULL; H1 is ignored with one layer.  item_edges: CSR positions per wave, a multiple of
+ * 16 in 16 .. 4096.  workspace: mgx_edge_mlp_workspace bytes (the partial rows and args of the rows that straddle items), -1 for a bad
+ * item_edges.  Supported (mgx_edge_mlp_supported; the rest is MGX_ERR_UNSUPPORTED): 32-bit indices, nnz > 0, H0 and H1 multiples of 16 in
+ * 16 .. 128, HL one in 16 .. 256, fewer than 2^27 edges and 2^30 rows.  mgx_last_spmm_kernel(): "edge_mlp_reduce" / "edge_mlp_grad".
+ * Deterministic: no atomics, fixed order.  Nothing is read back; the launch geometry depends on nnz, the widths and item_edges only.
+ * Purely additive: mgx_abi_version() stays 35. */
+int32_t mgx_edge_mlp_supported(const mgx_csr* csc, int64_t layers, int64_t H0, int64_t H1, int64_t HL);
+int64_t mgx_edge_mlp_workspace(int64_t nnz, int64_t item_edges);
+int32_t mgx_edge_mlp_reduce(const mgx_csr* csc, const int32_t* row_of_position, int64_t layers, int64_t H0, int64_t H1, int64_t HL,
+                            const float* u, int64_t ldu, const float* v, int64_t ldv, const float* w1, const float* b1 /* may be NULL */,
+                            const float* w2 /* NULL with one layer */, const float* b2 /* may be NULL */, int32_t sum, float* out, int64_t ldo,
+                            int32_t* arg /* may be NULL for sum */, int64_t item_edges, void* workspace, void* stream);
+int32_t mgx_edge_mlp_grad(const mgx_csr* csc, const int32_t* row_of_position, int64_t layers, int64_t H0, int64_t H1, int64_t HL,
+                          const float* u, int64_t ldu, const float* v, int64_t ldv, const float* w1, const float* b1 /* may be NULL */,
+                          const float* w2 /* NULL with one layer */, const float* b2 /* may be NULL */, int32_t sum, const float* g,
+                          int64_t ldg, const int32_t* arg /* may be NULL for sum */, float* e0, float* d_e0, float* e1, float* d_pre1,
+                          float* d_preL, float* acc /* may be NULL */, int64_t item_edges, void* stream);
+
 /* Sparse x sparse product C = A B of two CSR operands (csrc/spgemm.hip; ops.spgemm, dgl.adj_product_graph,
  * dgl.metapath_reachable_graph).  A is `a` (n rows, k columns), B is `b` (k rows, m columns); for graphs these are the OUT-CSRs, A[src,
  * dst].  Stored entries that repeat a (row, column) pair are separate entries that add.  C has one entry per structural non-zero (kept
